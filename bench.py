@@ -1,6 +1,6 @@
 """bench.py — headline benchmark of the MI355X Whisper-Medusa engine (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]     (N>1: launched by torch.distributed.run)
 
 One STEP = one pass of the whole hot path over one batch of synthetic 30 s clips per GPU:
 log-mel -> Whisper-large-v2 encoder + cross-KV projection -> Medusa-Linear-10 decode loop
@@ -9,9 +9,12 @@ log-mel -> Whisper-large-v2 encoder + cross-KV projection -> Medusa-Linear-10 de
 the timed region.  Streams shard data-parallel over ranks (no data-path collective); weights are
 packed on rank 0 and broadcast once over RCCL (outside the timed region).
 
-Prints ONE JSON line on rank 0: whole-job decoded tokens/s (+ RTF, iterations/s, tokens/iteration,
-the vanilla-greedy anchor), a `roofline` object for the decode iteration (algorithmic bytes of
-SURVEY.md §8d / hipEvent-timed iteration) and a `cpu_baseline` object (the oracle on the host cores).
+Prints ONE JSON line on rank 0: whole-job decoded tokens/s (+ RTF, iterations/s, tokens/iteration) and
+a `roofline` object for the decode iteration (algorithmic bytes of SURVEY.md §8d / hipEvent-timed
+iteration), all from the timed steps.  A plain run does nothing else.  --full adds the measurements
+that take runs of their own: the vanilla-greedy anchor, the layer-GEMM profile, the acceptance
+sensitivity rows, the other BASELINE configs and a `cpu_baseline` object (the oracle on the host cores).
+--dump-outputs DIR writes what the last timed step computed (rank 0's streams) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -296,6 +299,31 @@ def extra_config(name, heads, B, fp8, dev, logit_std, max_new, steps=8, f16=Fals
     return out
 
 
+DUMP_BUDGET = {"logmel": 16 << 20, "encoder_output": 40 << 20}     # bytes per array (64 MiB in all with the token ids)
+
+
+def _dump_sample(a, budget, seed):
+    """`a` itself if it fits `budget` bytes, else a fixed seeded sample of its flattened elements (same shape -> same positions)."""
+    if a.nbytes <= budget:
+        return a
+    idx = np.sort(np.random.default_rng(seed).integers(0, a.size, budget // a.itemsize))
+    return a.reshape(-1)[idx]
+
+
+def dump_outputs(path, last, eng, B):
+    """What the last timed step handed back: the token ids of every stream (prompt included, -1 after a stream's end; float64 holds
+    them exactly), and, with one context, the log-mel features and the encoder output it computed (float32)."""
+    os.makedirs(path, exist_ok=True)
+    seqs = last["seqs"]
+    ids = np.full((len(seqs), max(len(s) for s in seqs)), -1.0, dtype=np.float64)
+    for i, s in enumerate(seqs):
+        ids[i, : len(s)] = s
+    np.save(os.path.join(path, "tokens.npy"), ids)
+    if last.get("feats") is not None:
+        np.save(os.path.join(path, "logmel.npy"), _dump_sample(last["feats"].float().cpu().numpy(), DUMP_BUDGET["logmel"], 1))
+        np.save(os.path.join(path, "encoder_output.npy"), _dump_sample(eng.encoder_output(B).numpy(), DUMP_BUDGET["encoder_output"], 2))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -317,15 +345,23 @@ def main():
                     help="decode numerics contract (include/wm.h wm_config.act_fp16): bf16 hi/lo operand pairs (libwm.so) or one fp16 plane "
                          "(libwm_f16.so); default: the engine's (WM_ACT)")
     ap.add_argument("--bf16-cross-kv", action="store_true", help="with --fp8-weights: keep the decode loop on the bf16 cross-K/V cache (round 5's configs[4] leg; A/B)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the vanilla-greedy anchor, the layer-GEMM profile, the acceptance sensitivity rows, "
+                         "the other BASELINE configs and the CPU baseline (each can be left out again with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0: token ids, log-mel features, encoder output) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-vanilla", action="store_true",
-                    help="skip the vanilla-greedy anchor (PMC passes: only Medusa iterations in the counter totals)")
+                    help="with --full: skip the vanilla-greedy anchor and the layer-GEMM profile, and with them the sensitivity rows and the other configs "
+                         "(PMC passes: only Medusa iterations in the counter totals)")
     ap.add_argument("--cpu-iters", type=int, default=8, help="Medusa iterations of the CPU-baseline decode sample")
     ap.add_argument("--cpu-full", action="store_true", help="CPU baseline decodes the whole max-new budget (minutes)")
     ap.add_argument("--test-setup-delay-s", type=float, default=0.0, help=argparse.SUPPRESS)     # test harness only (tests/test_bench_dist.py)
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="skip the BASELINE configs[2] (Block, 32 streams) and configs[4] (fp8, 32 streams) legs and the sensitivity rows")
+                    help="with --full: skip the BASELINE configs[2] (Block, 32 streams) and configs[4] (fp8, 32 streams) legs and the sensitivity rows")
     args = ap.parse_args()
+    if not args.full:                        # a plain run measures the headline only
+        args.no_vanilla = args.no_cpu_baseline = args.no_extra_configs = True
 
     from whisper_medusa import MedusaConfig, WhisperMedusaModel, ACCEPT_TYPICAL
     from whisper_medusa import synth, weights, dist as wd
@@ -371,6 +407,7 @@ def main():
             for k in range(n_sets)]
     gp = synth.bench_gen_params(cfg, max_new_tokens=args.max_new, accept_mode=ACCEPT_TYPICAL)
     step_no = [0]
+    last = {}                                # what the latest step handed back (--dump-outputs)
 
     pool = None
     if args.micro_batches > 1:
@@ -382,11 +419,13 @@ def main():
         step_no[0] += 1
         if pool is not None:
             seqs = pool.run(wav, gp, from_wav=True)
+            last["seqs"] = seqs
             return sum(len(s) - len(gp.prompt) for s in seqs), pool.last_stats
         feats = eng.logmel(wav)
         eng.encode(feats)
         seqs = eng.decode(gp, B)
         st = eng.stats()
+        last["seqs"], last["feats"] = seqs, (feats if args.dump_outputs else None)
         return sum(len(s) - len(gp.prompt) for s in seqs), st
 
     for _ in range(args.warmup):
@@ -415,6 +454,8 @@ def main():
     elapsed = wd.max_over_ranks(time.perf_counter() - t0, dev)
     tokens_all = wd.sum_over_ranks(float(tokens), dev)
     per_rank_tokens = wd.gather_floats(float(tokens), dev)          # one entry per rank: every rank of the launch really decoded
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, eng, B)
 
     # ---- anchor: vanilla greedy decoding on the same engine / clips / budget (one untimed-region step) ----
     vanilla_tps = vanilla_ms_step = None

@@ -1,11 +1,12 @@
 #!/bin/bash
-# The batch / head-type / weight-format table of DESIGN.md §7: one bench.py JSON line per row into gpurun_out/sweep/.
-mkdir -p gpurun_out/sweep
+# The batch / head-type / weight-format table of DESIGN.md §7: one bench.py JSON line per row into $OUT (default bench_sweep/).
+OUT=${OUT:-bench_sweep}
+mkdir -p $OUT
 run() { # batch micro heads extra-flag tag
-  timeout 400 python bench.py --batch $1 --micro-batches $2 --heads $3 $4 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > gpurun_out/sweep/$5.json
-  python - "$5" <<'PY'
+  timeout 400 python bench.py --full --batch $1 --micro-batches $2 --heads $3 $4 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/$5.json
+  python - "$5" "$OUT/$5.json" <<'PY'
 import json, sys
-d = json.load(open(f"gpurun_out/sweep/{sys.argv[1]}.json"))
+d = json.load(open(sys.argv[2]))
 v = d["vanilla_anchor"]
 print(f"| {sys.argv[1]} | {d['value']:.0f} | {d['roofline']['ms_per_launch']:.2f} | {d['tokens_per_iter']:.2f} | {v['tokens_per_sec_per_gpu']:.0f} | {d['x_realtime']:.0f} | {d['roofline']['frac']:.3f} | {d['roofline']['prefill']['achieved']:.0f} |")
 PY

@@ -13,7 +13,7 @@ PY
 }
 echo "== pytest batched subset"; timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_tree.py -m gpu -q -x -p no:cacheprovider -k "many_streams or wide_batch or micro_batches or batch_equals or tree_decode_tokens" > $O/pytest.log 2>&1; echo rc $?; tail -4 $O/pytest.log
 echo "== pytest large twelve"; timeout 900 python -m pytest tests/test_gpu_large.py -m gpu -q -x -p no:cacheprovider -k "twelve or four_stream" > $O/pytest_large.log 2>&1; echo rc $?; tail -4 $O/pytest_large.log
-B="--batch 32 --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs"
+B="--full --batch 32 --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs"
 echo "== b32 tiled"; timeout 600 python bench.py $B > $O/b32_tiled.json 2> $O/b32_tiled.err; echo rc $?; show b32_tiled
 echo "== b32 rows_gemm"; WM_ROWS_TILED_MIN_MT=0 timeout 600 python bench.py $B > $O/b32_rows.json 2> $O/b32_rows.err; echo rc $?; show b32_rows
 echo "== b32 block tiled"; timeout 600 python bench.py $B --heads block > $O/b32_block.json 2> $O/b32_block.err; echo rc $?; show b32_block

@@ -13,7 +13,7 @@ try:
 except Exception as e: print("$1", "failed", e, open("$O/$1.err").read()[-800:])
 PY
 }
-B="--steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs"
+B="--full --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs"
 echo "== default"; timeout 300 python bench.py $B > $O/b1.json 2> $O/b1.err; show b1
 echo "== pf jobs 240"; WM_PF_JOBS=240 timeout 300 python bench.py $B > $O/b1_pf240.json 2> $O/b1_pf240.err; show b1_pf240
 echo "== pf jobs 480"; WM_PF_JOBS=480 timeout 300 python bench.py $B > $O/b1_pf480.json 2> $O/b1_pf480.err; show b1_pf480

@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r02c16; mkdir -p $O
-echo "== default bench"; ( time timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err ) 2>&1 | grep real; python - <<PY
+echo "== default bench"; ( time timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err ) 2>&1 | grep real; python - <<PY
 import json
 d=json.loads(open("$O/bench_default.json").read().strip().splitlines()[-1]); print(d["value"], d["roofline"]["ms_per_launch"], d["roofline"]["frac"], d["vanilla_anchor"], d["cpu_baseline"]["value"], d["cpu_baseline"]["parity_checked"])
 PY

@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r02c19; mkdir -p $O
-run() { tag=$1; shift; env "$@" timeout 300 python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/$tag.json 2> $O/$tag.err
+run() { tag=$1; shift; env "$@" timeout 300 python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/$tag.json 2> $O/$tag.err
 python - <<PY
 import json
 try:

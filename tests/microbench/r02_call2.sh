@@ -6,7 +6,7 @@ O=gpurun_out/r02c2; mkdir -p $O
 python whisper-medusa_amd/build.py > $O/build.log 2>&1; python whisper-medusa_amd/build.py --timeline >> $O/build.log 2>&1; tail -2 $O/build.log
 echo "== diag new"; timeout 300 python tests/microbench/diag_m10block.py > $O/diag_new.log 2>&1; echo rc $?; tail -30 $O/diag_new.log
 echo "== diag v1"; WM_ABI_ANY=1 WM_LIB=tests/microbench/libwm_v1.so timeout 300 python tests/microbench/diag_m10block.py > $O/diag_v1.log 2>&1; echo rc $?; tail -12 $O/diag_v1.log
-B="--steps 6 --warmup 2 --no-cpu-baseline --no-extra-configs"
+B="--full --steps 6 --warmup 2 --no-cpu-baseline --no-extra-configs"
 echo "== bench new"; timeout 600 python bench.py $B > $O/bench_new.json 2> $O/bench_new.err; echo rc $?; python - <<PY
 import json
 for f in ("bench_new",):

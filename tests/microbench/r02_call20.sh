@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r02c20; mkdir -p $O
 echo "== pytest batched"; timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_tree.py -m gpu -q -x -p no:cacheprovider -k "many_streams or wide_batch or micro_batches or batch_equals or tree_decode_tokens or decode_tokens_bit_exact or fp8_decoder" > $O/pytest.log 2>&1; echo rc $?; tail -3 $O/pytest.log
 echo "== pytest large"; timeout 900 python -m pytest tests/test_gpu_large.py -m gpu -q -x -p no:cacheprovider -k "twelve or four_stream or block_decode" > $O/pytest_large.log 2>&1; echo rc $?; tail -3 $O/pytest_large.log
-run() { tag=$1; shift; env "$@" timeout 300 python bench.py --batch 32 --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/$tag.json 2> $O/$tag.err
+run() { tag=$1; shift; env "$@" timeout 300 python bench.py --full --batch 32 --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/$tag.json 2> $O/$tag.err
 python - <<PY
 import json
 try:

@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/r02c24; mkdir -p $O
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo rc $?
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo rc $?
 python - <<PY
 import json
 d=json.loads(open("$O/bench_default.json").read().strip().splitlines()[-1])

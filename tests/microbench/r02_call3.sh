@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/r02c3; mkdir -p $O
 python whisper-medusa_amd/build.py > $O/build.log 2>&1; python whisper-medusa_amd/build.py --timeline >> $O/build.log 2>&1; tail -2 $O/build.log
-B="--steps 6 --warmup 2 --no-cpu-baseline --no-extra-configs"
+B="--full --steps 6 --warmup 2 --no-cpu-baseline --no-extra-configs"
 show() { python - <<PY
 import json
 try:

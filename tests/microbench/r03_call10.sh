@@ -12,8 +12,8 @@ timeout 900 python -m pytest tests/test_gpu_large.py -m gpu -q -p no:cacheprovid
 echo "== encoder (32 clips, 1 clip)"
 timeout 600 python tests/microbench/r03_sweep.py --enc --enc-now --out $O/enc.json > $O/enc.log 2>&1; echo rc $?; grep "^encoder" $O/enc.log
 echo "== bench 32 streams / 1 stream"
-timeout 600 python bench.py --batch 32 --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32.json 2> $O/b32.err; echo rc $?
-timeout 600 python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b1.json 2> $O/b1.err; echo rc $?
+timeout 600 python bench.py --full --batch 32 --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32.json 2> $O/b32.err; echo rc $?
+timeout 600 python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b1.json 2> $O/b1.err; echo rc $?
 python - <<PY
 import json
 for n in ("b32", "b1"):

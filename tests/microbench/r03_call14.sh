@@ -20,7 +20,7 @@ timeout 400 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES --kernel-trace -d /tmp/mf -
 DB=$(find /tmp/mf -name "*.db" | head -1); python $R/tests/mfma_summary.py $DB $O/r03_pmc_mfma_busy_bench_b32.md 2>/dev/null | head -12
 cd $R
 echo "== bench default"
-( time timeout 600 python bench.py > $O/r03_bench_default.json 2> $O/bench.err ) 2>&1 | grep real
+( time timeout 600 python bench.py --full > $O/r03_bench_default.json 2> $O/bench.err ) 2>&1 | grep real
 python - <<PY
 import json
 try:

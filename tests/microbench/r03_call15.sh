@@ -14,7 +14,7 @@ DB=$(find /tmp/pmc1 -name "*.db" | head -1); python $R/tests/pmc_summary.py $DB 
 cp $O/r03_pmc_traffic.json $R/profiles/r03_pmc_traffic.json
 cd $R
 echo "== bench b1"
-timeout 200 python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/b1.json 2> $O/b1.err; echo rc $?
+timeout 200 python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/b1.json 2> $O/b1.err; echo rc $?
 python - <<PY
 import json
 d = json.loads(open("$O/b1.json").read().strip().splitlines()[-1]); r = d["roofline"]

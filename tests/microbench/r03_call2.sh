@@ -24,7 +24,7 @@ for k, a in sorted(agg.items(), key=lambda kv: -kv[1][1])[:24]:
     tot = a[1] + a[2]
     print(f"{k[0]:60s} grid {k[1]:>9s} n {a[0]:6d} hit {a[1]:.3e} miss {a[2]:.3e} hit-rate {a[1] / tot if tot else 0:.3f}")
 PY
-run() { tag=$1; shift; env "$@" timeout 300 python bench.py --batch 32 --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/$tag.json 2> $O/$tag.err
+run() { tag=$1; shift; env "$@" timeout 300 python bench.py --full --batch 32 --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/$tag.json 2> $O/$tag.err
 python - <<PY
 import json
 try:

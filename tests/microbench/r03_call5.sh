@@ -7,7 +7,7 @@ O=$R/gpurun_out/r03c5; mkdir -p $O
 echo "== pytest batched"; timeout 600 python -m pytest tests/test_gpu_parity.py -m gpu -q -x -p no:cacheprovider -k "many_streams or wide_batch or batch_equals or encoder_output" > $O/pytest.log 2>&1; echo rc $?; tail -3 $O/pytest.log
 echo "== pytest large"; timeout 900 python -m pytest tests/test_gpu_large.py -m gpu -q -x -p no:cacheprovider -k "twelve or big_batch" > $O/pytest_large.log 2>&1; echo rc $?; tail -3 $O/pytest_large.log
 echo "== encoder (32 clips)"; timeout 400 python tests/microbench/r03_sweep.py --enc --enc-only-batch --enc-knobs --out $O/enc.json > $O/enc.log 2>&1; echo rc $?; grep -E "^encoder" $O/enc.log
-run() { tag=$1; b=$2; shift; shift; env "$@" timeout 300 python bench.py --batch $b --steps 3 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/$tag.json 2> $O/$tag.err
+run() { tag=$1; b=$2; shift; shift; env "$@" timeout 300 python bench.py --full --batch $b --steps 3 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/$tag.json 2> $O/$tag.err
 python - <<PY
 import json
 try:

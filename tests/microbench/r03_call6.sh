@@ -8,7 +8,7 @@ echo "== pytest trees"; timeout 900 python -m pytest tests/test_gpu_tree.py -m g
 echo "== pytest parity (decode, single tile paths untouched?)"; timeout 600 python -m pytest tests/test_gpu_parity.py -m gpu -q -x -p no:cacheprovider -k "decode_tokens or carry or batch_equals or many_streams or forward" > $O/pytest.log 2>&1; echo rc $?; tail -3 $O/pytest.log
 echo "== pytest large tree + linear"; timeout 900 python -m pytest tests/test_gpu_large.py -m gpu -q -x -p no:cacheprovider -k "candidate_tree or linear_decode_loop or big_batch" > $O/pytest_large.log 2>&1; echo rc $?; tail -4 $O/pytest_large.log
 echo "== encoder (32 clips)"; timeout 400 python tests/microbench/r03_sweep.py --enc --enc-only-batch --enc-knobs --out $O/enc.json > $O/enc.log 2>&1; echo rc $?; grep -E "^encoder" $O/enc.log
-run() { tag=$1; b=$2; shift; shift; env "$@" timeout 300 python bench.py --batch $b --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/$tag.json 2> $O/$tag.err
+run() { tag=$1; b=$2; shift; shift; env "$@" timeout 300 python bench.py --full --batch $b --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/$tag.json 2> $O/$tag.err
 python - <<PY
 import json
 try:

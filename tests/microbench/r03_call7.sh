@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r03c7; mkdir -p $O
 echo "== pytest encoder"; timeout 600 python -m pytest tests/test_gpu_parity.py -m gpu -q -x -p no:cacheprovider -k "encoder_output or cross_kv or fp8_mfma or silence" > $O/pytest.log 2>&1; echo rc $?; tail -3 $O/pytest.log
 echo "== pytest large encoder"; timeout 900 python -m pytest tests/test_gpu_large.py -m gpu -q -x -p no:cacheprovider -k "big_batch or end_to_end" > $O/pytest_large.log 2>&1; echo rc $?; tail -4 $O/pytest_large.log
-run() { tag=$1; b=$2; shift; shift; env "$@" timeout 300 python bench.py --batch $b --steps 3 --warmup 1 --no-cpu-baseline --no-extra-configs $EXTRA > $O/$tag.json 2> $O/$tag.err
+run() { tag=$1; b=$2; shift; shift; env "$@" timeout 300 python bench.py --full --batch $b --steps 3 --warmup 1 --no-cpu-baseline --no-extra-configs $EXTRA > $O/$tag.json 2> $O/$tag.err
 python - <<PY
 import json
 try:

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r03c8; mkdir -p $O
 echo "== smoke"; timeout 300 python -c "import __graft_entry__ as g; g.build(); g.smoke()" > $O/smoke.log 2>&1; echo rc $?; tail -2 $O/smoke.log
 echo "== pytest -m gpu (all)"; ( time timeout 1500 python -m pytest tests -m gpu -q -p no:cacheprovider > $O/pytest_all.log 2>&1 ) 2>&1 | grep real; echo rc $?; tail -12 $O/pytest_all.log
-echo "== default bench"; ( time timeout 1200 python bench.py > $O/bench_default.json 2> $O/bench_default.err ) 2>&1 | grep real; python - <<PY
+echo "== default bench"; ( time timeout 1200 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err ) 2>&1 | grep real; python - <<PY
 import json
 try:
     d=json.loads(open("$O/bench_default.json").read().strip().splitlines()[-1])

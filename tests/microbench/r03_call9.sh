@@ -23,7 +23,7 @@ echo "== mfma busy b32"
 timeout 600 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES --kernel-trace -d /tmp/mf -o mf -- python $R/bench.py --batch 32 --steps 1 --warmup 1 --no-cpu-baseline --no-vanilla --no-extra-configs > $O/mf.log 2>&1; echo rc $?
 DB=$(find /tmp/mf -name "*.db" | head -1); python $R/tests/mfma_summary.py $DB $O/r03_pmc_mfma_busy_bench_b32.md 2>/dev/null | head -14
 echo "== cpu baseline, whole budget"
-cd $R; ( time timeout 1500 python bench.py --steps 2 --warmup 1 --cpu-full --no-extra-configs > $O/r03_bench_cpu_full.json 2> $O/cpu_full.err ) 2>&1 | grep real
+cd $R; ( time timeout 1500 python bench.py --full --steps 2 --warmup 1 --cpu-full --no-extra-configs > $O/r03_bench_cpu_full.json 2> $O/cpu_full.err ) 2>&1 | grep real
 python - <<PY
 import json
 try:

@@ -8,8 +8,8 @@ timeout 60 tests/microbench/bin/mfma128_probe > $O/mfma128.txt 2>&1; echo probe 
 timeout 120 tests/microbench/bin/xcd_barrier > $O/xcd_barrier.txt 2>&1; echo barrier rc $?; cat $O/xcd_barrier.txt
 for arm in base r4p; do
   if [ $arm = base ]; then unset WM_LIB; else export WM_LIB=$PKG/libwm_r4p.so; fi
-  timeout 150 python bench.py --batch 32 --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32_$arm.json 2> $O/b32_$arm.err; echo $arm b32 rc $?
-  timeout 120 python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b1_$arm.json 2> $O/b1_$arm.err; echo $arm b1 rc $?
+  timeout 150 python bench.py --full --batch 32 --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32_$arm.json 2> $O/b32_$arm.err; echo $arm b32 rc $?
+  timeout 120 python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b1_$arm.json 2> $O/b1_$arm.err; echo $arm b1 rc $?
 done
 python - <<PY
 import json

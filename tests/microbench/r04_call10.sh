@@ -5,7 +5,7 @@ O=$GRAFT_REPO_ROOT/gpurun_out/r04c10; mkdir -p $O
 timeout 500 python -m pytest tests/test_gpu_parity.py -m gpu -q -p no:cacheprovider -x -k "merged_step or batch or streams or carry or micro_batches or bit_exact" > $O/pytest.log 2>&1; echo pytest rc $?; tail -5 $O/pytest.log
 for arm in step lock; do
   if [ $arm = lock ]; then export WM_NO_STEP=1; else unset WM_NO_STEP; fi
-  timeout 200 python bench.py --batch 32 --steps 2 --warmup 1 --no-cpu-baseline > $O/b32_$arm.json 2> $O/b32_$arm.err; echo $arm rc $?
+  timeout 200 python bench.py --full --batch 32 --steps 2 --warmup 1 --no-cpu-baseline > $O/b32_$arm.json 2> $O/b32_$arm.err; echo $arm rc $?
 done
 unset WM_NO_STEP
 python - <<PY

@@ -10,7 +10,7 @@ timeout 120 python tests/microbench/r04_gemm_time.py base 2>&1 | grep "^\[" | te
 WM_LIB=$R/whisper-medusa_amd/whisper_medusa/libwm_share.so timeout 120 python tests/microbench/r04_gemm_time.py share 2>&1 | grep "^\[" | tee -a $O/gemm_time.txt
 for arm in share; do
   if [ $arm = share ]; then export WM_LIB=$R/whisper-medusa_amd/whisper_medusa/libwm_share.so; else unset WM_LIB; fi
-  timeout 200 python bench.py --batch 32 --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32_$arm.json 2> $O/b32_$arm.err; echo $arm rc $?
+  timeout 200 python bench.py --full --batch 32 --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32_$arm.json 2> $O/b32_$arm.err; echo $arm rc $?
 done
 unset WM_LIB
 python - <<PY

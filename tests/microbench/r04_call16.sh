@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r04c16; mkdir -p $O
 for arm in lntail; do
   if [ $arm = lntail ]; then export WM_LIB=$R/whisper-medusa_amd/whisper_medusa/libwm_lntail.so; else unset WM_LIB; fi
-  timeout 200 python bench.py --batch 32 --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32_$arm.json 2> $O/b32_$arm.err; echo $arm rc $?
+  timeout 200 python bench.py --full --batch 32 --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32_$arm.json 2> $O/b32_$arm.err; echo $arm rc $?
 done
 unset WM_LIB
 python - <<PY

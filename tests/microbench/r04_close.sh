@@ -19,7 +19,7 @@ DB=$(find /tmp/kt32 -name "*.db" | head -1); python $R/tests/prof_summary.py $DB
 cd $R
 cp $O/r04_pmc_traffic.json $R/profiles/r04_pmc_traffic.json
 echo "== bench default"
-( time timeout 900 python bench.py > $O/r04_bench_default.json 2> $O/bench.err ) 2>&1 | grep real
+( time timeout 900 python bench.py --full > $O/r04_bench_default.json 2> $O/bench.err ) 2>&1 | grep real
 python - <<PY
 import json
 try:

@@ -12,7 +12,7 @@ echo "== gemm times"; timeout 300 python tests/microbench/r05_gemm_time.py 2>&1 
 echo "== bench arms"
 for arm in old lds ldstail; do
   case $arm in old) export WM_ROWS_LDS=0 WM_LN_TAIL=0;; lds) export WM_ROWS_LDS=1 WM_LN_TAIL=0;; ldstail) export WM_ROWS_LDS=1 WM_LN_TAIL=1;; esac
-  timeout 240 python bench.py --batch 32 --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32_$arm.json 2> $O/b32_$arm.err; echo $arm rc $?
+  timeout 240 python bench.py --full --batch 32 --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32_$arm.json 2> $O/b32_$arm.err; echo $arm rc $?
 done
 unset WM_ROWS_LDS WM_LN_TAIL
 python - <<PY

@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 O=$GRAFT_REPO_ROOT/gpurun_out/r05c10; mkdir -p $O
 timeout 500 python -m pytest tests/test_gpu_parity.py tests/test_gpu_large.py -m gpu -q -p no:cacheprovider -x -k "merged_step or batch or streams or micro_batches or wide" > $O/pytest.log 2>&1; echo pytest rc $?; tail -3 $O/pytest.log
 for sub in 1 4 2 8; do
-  WM_LN_SUB=$sub timeout 200 python bench.py --batch 32 --steps 3 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32_sub$sub.json 2> $O/b32_sub$sub.err; echo sub $sub rc $?
+  WM_LN_SUB=$sub timeout 200 python bench.py --full --batch 32 --steps 3 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32_sub$sub.json 2> $O/b32_sub$sub.err; echo sub $sub rc $?
 done
 python - <<PY
 import json

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r05c11; mkdir -p $O
 for arm in base rt2 base rt2; do
   if [ $arm = rt2 ]; then export WM_PLAN_RT2_MAXN16=1048576; else unset WM_PLAN_RT2_MAXN16; fi
-  timeout 200 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/b1_$arm.json 2> $O/b1_$arm.err; echo $arm rc $?
+  timeout 200 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/b1_$arm.json 2> $O/b1_$arm.err; echo $arm rc $?
   python - <<PY
 import json
 try:

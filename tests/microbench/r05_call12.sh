@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 O=$GRAFT_REPO_ROOT/gpurun_out/r05c12; mkdir -p $O
 for arm in off on off on; do
   if [ $arm = off ]; then export WM_PREFETCH_SMALL=0; else unset WM_PREFETCH_SMALL; fi
-  timeout 200 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/b1_$arm.json 2> $O/b1_$arm.err; echo $arm rc $?
+  timeout 200 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/b1_$arm.json 2> $O/b1_$arm.err; echo $arm rc $?
   python - <<PY
 import json
 try:

@@ -22,7 +22,7 @@ for rep in 1 2; do
 for arm in base new; do
   unset WM_LIB WM_PREFETCH_SMALL
   if [ $arm = base ]; then export WM_LIB=$L/libwm_base.so; fi
-  timeout 200 python bench.py --batch 32 --steps 3 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32_$arm$rep.json 2> $O/b32_$arm$rep.err
+  timeout 200 python bench.py --full --batch 32 --steps 3 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32_$arm$rep.json 2> $O/b32_$arm$rep.err
   python - <<PY
 import json
 try:

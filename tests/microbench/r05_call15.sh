@@ -9,8 +9,8 @@ for rep in 1 2 3; do
 for arm in base new; do
   unset WM_LIB
   if [ $arm = base ]; then export WM_LIB=$L/libwm_base.so; fi
-  timeout 200 python bench.py --batch 32 --steps 3 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32_$arm$rep.json 2> $O/b32_$arm$rep.err
-  timeout 200 python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/b1_$arm$rep.json 2> $O/b1_$arm$rep.err
+  timeout 200 python bench.py --full --batch 32 --steps 3 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32_$arm$rep.json 2> $O/b32_$arm$rep.err
+  timeout 200 python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/b1_$arm$rep.json 2> $O/b1_$arm$rep.err
   python - <<PY
 import json
 for tag in ("b32", "b1"):

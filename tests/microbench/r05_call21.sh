@@ -11,7 +11,7 @@ timeout 200 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d /tmp/pmc1 -o pmc1 -- py
 DB=$(find /tmp/pmc1 -name "*.db" | head -1); python $R/tests/pmc_summary.py $DB $O/r05_pmc_fetch_size_bench_b1.md $O/r05_pmc_traffic.json $O/r05_pmc_traffic_noprefetch.json | tail -1
 cd $R
 cp $O/r05_pmc_traffic.json profiles/r05_pmc_traffic.json
-timeout 300 python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-extra-configs | python -c "
+timeout 300 python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-extra-configs | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print(d['value'], r['ms_per_launch'], r['frac'], 'traffic', r['traffic'], r['traffic_source'].get('stale'))"

@@ -8,7 +8,7 @@ for cfg in linear block fp8; do
   extra=""
   if [ $cfg = block ]; then extra="--heads block"; fi
   if [ $cfg = fp8 ]; then extra="--fp8-weights"; fi
-  timeout 300 python bench.py --batch 32 --steps 8 --warmup 1 --no-cpu-baseline --no-extra-configs $extra > $O/b32_$cfg$rep.json 2> $O/b32_$cfg$rep.err
+  timeout 300 python bench.py --full --batch 32 --steps 8 --warmup 1 --no-cpu-baseline --no-extra-configs $extra > $O/b32_$cfg$rep.json 2> $O/b32_$cfg$rep.err
   python - <<PY
 import json
 try:

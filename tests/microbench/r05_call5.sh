@@ -11,7 +11,7 @@ for arm in shipped hybrid81 hybrid_auto; do
     hybrid81) export WM_LIB=$R/whisper-medusa_amd/whisper_medusa/libwm_rowslds.so WM_ROWS_LDS=1 WM_LN_TAIL=0 WM_RL_MIN_N16=160 WM_RL_NW=8 WM_RL_FT=1;;
     hybrid_auto) export WM_LIB=$R/whisper-medusa_amd/whisper_medusa/libwm_rowslds.so WM_ROWS_LDS=1 WM_LN_TAIL=0 WM_RL_MIN_N16=160;;
   esac
-  timeout 240 python bench.py --batch 32 --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32_$arm.json 2> $O/b32_$arm.err; echo $arm rc $?
+  timeout 240 python bench.py --full --batch 32 --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32_$arm.json 2> $O/b32_$arm.err; echo $arm rc $?
 done
 unset WM_LIB WM_ROWS_LDS WM_LN_TAIL WM_RL_MIN_N16 WM_RL_NW WM_RL_FT
 python - <<PY

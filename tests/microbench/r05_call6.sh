@@ -14,7 +14,7 @@ for cfgname in linear block fp8; do
   for arm in 0 1; do
     export WM_ROWS_NORM=$arm
     case $cfgname in linear) X="";; block) X="--heads block";; fp8) X="--fp8-weights";; esac
-    timeout 240 python bench.py --batch 32 --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs $X > $O/b32_${cfgname}_$arm.json 2> $O/b32_${cfgname}_$arm.err; echo $cfgname $arm rc $?
+    timeout 240 python bench.py --full --batch 32 --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs $X > $O/b32_${cfgname}_$arm.json 2> $O/b32_${cfgname}_$arm.err; echo $cfgname $arm rc $?
   done
 done
 unset WM_ROWS_NORM

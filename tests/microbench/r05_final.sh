@@ -34,7 +34,7 @@ cp $O/r05_pmc_traffic.json $R/profiles/r05_pmc_traffic.json
 echo "== slow test set (live fp32 tables, 3- and 8-stream tree)"
 ( time WM_SLOW=1 timeout 900 python -m pytest tests -m "gpu and slow" -q -p no:cacheprovider --durations=10 > $O/pytest_slow.log 2>&1 ) 2>&1 | grep real; tail -14 $O/pytest_slow.log
 echo "== bench default"
-( time timeout 900 python bench.py > $O/r05_bench_default.json 2> $O/bench.err ) 2>&1 | grep real
+( time timeout 900 python bench.py --full > $O/r05_bench_default.json 2> $O/bench.err ) 2>&1 | grep real
 python - <<PY
 import json
 try:

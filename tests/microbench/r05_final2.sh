@@ -30,7 +30,7 @@ tail -20 $O/pytest_gpu.log | cut -c1-300
 ( time timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 ) 2>&1 | grep real; tail -2 $O/smoke.log | cut -c1-200
 cp gpurun_out/gpu_suite_durations.json $O/ 2>/dev/null; cp gpurun_out/parity_report.json $O/ 2>/dev/null
 echo "== bench default"
-( time timeout 900 python bench.py > $O/r05_bench_default.json 2> $O/bench.err ) 2>&1 | grep real
+( time timeout 900 python bench.py --full > $O/r05_bench_default.json 2> $O/bench.err ) 2>&1 | grep real
 python - <<PY
 import json
 try:

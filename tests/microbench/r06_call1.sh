@@ -12,7 +12,7 @@ done
 for rep in 1 2; do
 for arm in base nolo noln nolonoln; do
   if [ $arm = base ]; then unset WM_LIB; else export WM_LIB=$P/libwm_$arm.so; fi
-  timeout 300 python bench.py --batch 32 --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32_$arm$rep.json 2> $O/b32_$arm$rep.err
+  timeout 300 python bench.py --full --batch 32 --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32_$arm$rep.json 2> $O/b32_$arm$rep.err
   python - <<PY
 import json
 try:

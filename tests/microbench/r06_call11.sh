@@ -5,7 +5,7 @@ O=$GRAFT_REPO_ROOT/gpurun_out/r06c11; mkdir -p $O
 ( time timeout 1500 python -m pytest tests -m gpu -q -p no:cacheprovider > $O/pytest_gpu.log 2>&1 ) 2>&1 | grep real; echo pytest rc $?
 grep -h "^FAILED\|^ERROR\|passed\|failed" $O/pytest_gpu.log | cut -c1-300 | tail -20
 grep -h "parity ties" $O/pytest_gpu.log | cut -c1-400
-( time timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err ) 2>&1 | grep real
+( time timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err ) 2>&1 | grep real
 tail -c 600 $O/bench_default.err
 python - <<PY
 import json

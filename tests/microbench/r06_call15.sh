@@ -14,7 +14,7 @@ for tt in 2 4; do
 done
 for tt in 2 4; do
   echo "== bench --batch 32 WM_ROWS_TT=$tt"
-  WM_ROWS_TT=$tt WM_LIB_F16=$P/libwm_tt4.so timeout 400 python bench.py --batch 32 --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/bench_b32_tt$tt.json 2> $O/bench_b32_tt$tt.err
+  WM_ROWS_TT=$tt WM_LIB_F16=$P/libwm_tt4.so timeout 400 python bench.py --full --batch 32 --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/bench_b32_tt$tt.json 2> $O/bench_b32_tt$tt.err
   python - <<PY
 import json
 d = json.loads(open("$O/bench_b32_tt$tt.json").read().strip().splitlines()[-1])

@@ -20,7 +20,7 @@ timeout 200 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES --kernel-trace -d /tmp/mf -
 DB=$(find /tmp/mf -name "*.db" | head -1); python $R/tests/mfma_summary.py $DB $O/r06_pmc_mfma_busy_bench_b32.md 2>/dev/null | head -8
 cd $R
 echo "== bench default"
-( time timeout 900 python bench.py > $O/r06_bench_default.json 2> $O/bench.err ) 2>&1 | grep real
+( time timeout 900 python bench.py --full > $O/r06_bench_default.json 2> $O/bench.err ) 2>&1 | grep real
 python - <<PY
 import json
 try:

@@ -12,8 +12,8 @@ done
 for rep in 1 2; do
 for fold in 1 0; do
   export WM_LN_FOLD=$fold
-  timeout 300 python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/b1_$fold$rep.json 2> $O/b1_$fold$rep.err
-  timeout 300 python bench.py --batch 32 --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32_$fold$rep.json 2> $O/b32_$fold$rep.err
+  timeout 300 python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/b1_$fold$rep.json 2> $O/b1_$fold$rep.err
+  timeout 300 python bench.py --full --batch 32 --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32_$fold$rep.json 2> $O/b32_$fold$rep.err
   python - <<PY
 import json
 for tag in ("b1", "b32"):

@@ -11,7 +11,7 @@ grep -h "^FAILED\|^ERROR\|passed\|failed" $O/pytest_par.log | cut -c1-300 | tail
 grep -h "^FAILED\|^ERROR\|passed\|failed\|sibling hits" $O/pytest_large.log | cut -c1-300 | tail -12
 for rep in 1 2; do
   for sib in 5 0; do
-    WM_SIBLINGS=$sib timeout 400 python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/b1_sib${sib}_$rep.json 2> $O/b1_sib${sib}_$rep.err
+    WM_SIBLINGS=$sib timeout 400 python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/b1_sib${sib}_$rep.json 2> $O/b1_sib${sib}_$rep.err
     python - <<PY
 import json
 d = json.loads(open("$O/b1_sib${sib}_$rep.json").read().strip().splitlines()[-1])

@@ -14,7 +14,7 @@ grep "k_sib_cand\|k_kv_compact\|k_accept\|k_set_cand" $O/kernel_trace_sib5.md | 
 cd $GRAFT_REPO_ROOT
 for rep in 1 2; do
   for sib in 5 0; do
-    WM_SIBLINGS=$sib timeout 400 python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/b1_sib${sib}_$rep.json 2> $O/b1_sib${sib}_$rep.err
+    WM_SIBLINGS=$sib timeout 400 python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/b1_sib${sib}_$rep.json 2> $O/b1_sib${sib}_$rep.err
     python - <<PY
 import json
 d = json.loads(open("$O/b1_sib${sib}_$rep.json").read().strip().splitlines()[-1])

@@ -33,7 +33,7 @@ DB=$(find /tmp/mf -name "*.db" | head -1); python $R/tests/mfma_summary.py $DB $
 cd $R
 cp $O/r06_pmc_traffic.json $R/profiles/r06_pmc_traffic.json
 echo "== bench default"
-( time timeout 900 python bench.py > $O/r06_bench_default.json 2> $O/bench.err ) 2>&1 | grep real
+( time timeout 900 python bench.py --full > $O/r06_bench_default.json 2> $O/bench.err ) 2>&1 | grep real
 python - <<PY
 import json
 try:

@@ -13,7 +13,7 @@ done
 for rep in 1 2; do
 for arm in "1 1" "0 1" "1 0"; do
   set -- $arm; export WM_LN_FOLD=$1 WM_PREFETCH=$2
-  timeout 300 python bench.py --batch 32 --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32_$1$2$rep.json 2> $O/b32_$1$2$rep.err
+  timeout 300 python bench.py --full --batch 32 --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32_$1$2$rep.json 2> $O/b32_$1$2$rep.err
   python - <<PY
 import json
 try:

@@ -7,7 +7,7 @@ P=$GRAFT_REPO_ROOT/whisper-medusa_amd/whisper_medusa
 for rep in 1 2; do
   for lib in f16 prev; do
     WM_LIB_F16=$P/libwm_$lib.so timeout 300 python tests/microbench/r06_sib_cost.py 2>&1 | grep "^WM_SIBLINGS" | sed "s/^/[$lib] /" | tee -a $O/sib_cost.log
-    WM_LIB_F16=$P/libwm_$lib.so timeout 400 python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/b1_${lib}_$rep.json 2> $O/b1_${lib}_$rep.err
+    WM_LIB_F16=$P/libwm_$lib.so timeout 400 python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/b1_${lib}_$rep.json 2> $O/b1_${lib}_$rep.err
     python - <<PY
 import json
 d = json.loads(open("$O/b1_${lib}_$rep.json").read().strip().splitlines()[-1])
@@ -17,7 +17,7 @@ PY
   done
 done
 for lib in f16 prev; do
-  WM_LIB_F16=$P/libwm_$lib.so timeout 400 python bench.py --batch 32 --steps 8 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/b32_$lib.json 2> $O/b32_$lib.err
+  WM_LIB_F16=$P/libwm_$lib.so timeout 400 python bench.py --full --batch 32 --steps 8 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/b32_$lib.json 2> $O/b32_$lib.err
   python - <<PY
 import json
 d = json.loads(open("$O/b32_$lib.json").read().strip().splitlines()[-1])

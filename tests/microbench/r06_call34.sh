@@ -8,8 +8,8 @@ P=$GRAFT_REPO_ROOT/whisper-medusa_amd/whisper_medusa
 grep -h "^FAILED\|^ERROR\|passed\|failed" $O/pytest_fp8.log | cut -c1-300 | tail -5
 for rep in 1 2; do
   for lib in f16 prev; do
-    WM_LIB_F16=$P/libwm_$lib.so timeout 400 python bench.py --batch 32 --fp8-weights --steps 8 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/b32_${lib}_$rep.json 2> $O/b32_${lib}_$rep.err
-    WM_LIB_F16=$P/libwm_$lib.so timeout 400 python bench.py --fp8-weights --steps 8 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/b1_${lib}_$rep.json 2> $O/b1_${lib}_$rep.err
+    WM_LIB_F16=$P/libwm_$lib.so timeout 400 python bench.py --full --batch 32 --fp8-weights --steps 8 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/b32_${lib}_$rep.json 2> $O/b32_${lib}_$rep.err
+    WM_LIB_F16=$P/libwm_$lib.so timeout 400 python bench.py --full --fp8-weights --steps 8 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/b1_${lib}_$rep.json 2> $O/b1_${lib}_$rep.err
     python - <<PY
 import json
 for tag in ("b32", "b1"):

@@ -12,8 +12,8 @@ for act in f16 hilo; do
 done
 for rep in 1 2; do
 for act in f16 hilo; do
-  timeout 300 python bench.py --act $act --steps 8 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/b1_$act$rep.json 2> $O/b1_$act$rep.err
-  timeout 300 python bench.py --act $act --batch 32 --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32_$act$rep.json 2> $O/b32_$act$rep.err
+  timeout 300 python bench.py --full --act $act --steps 8 --warmup 2 --no-cpu-baseline --no-extra-configs > $O/b1_$act$rep.json 2> $O/b1_$act$rep.err
+  timeout 300 python bench.py --full --act $act --batch 32 --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/b32_$act$rep.json 2> $O/b32_$act$rep.err
   python - <<PY
 import json
 for tag in ("b1", "b32"):

@@ -12,7 +12,7 @@ for arm in "fp8" "fp8 --bf16-cross-kv" "block"; do
   set -- $arm
   extra="--fp8-weights"; [ "$1" = block ] && extra="--heads block"; [ -n "$2" ] && extra="$extra $2"
   tag=$(echo $arm | tr -d ' -')
-  timeout 300 python bench.py --batch 32 --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs $extra > $O/b32_$tag$rep.json 2> $O/b32_$tag$rep.err
+  timeout 300 python bench.py --full --batch 32 --steps 4 --warmup 1 --no-cpu-baseline --no-extra-configs $extra > $O/b32_$tag$rep.json 2> $O/b32_$tag$rep.err
   python - <<PY
 import json
 try:

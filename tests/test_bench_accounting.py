@@ -94,3 +94,30 @@ def test_committed_traffic_counters_were_taken_on_the_committed_decode_sources()
     tj = json.load(open(files[-1]))
     assert tj["kernels_sha"] == bench.kernels_sha(), f"{os.path.basename(files[-1])} is stale: re-run the FETCH_SIZE pass or undo the source edit"
     assert tj["medusa_iteration_bytes"] > 3e9
+
+
+def test_dump_outputs_writes_the_last_step_within_the_size_budget(tmp_path):
+    """--dump-outputs: token ids of every stream (float64, -1 after a stream's end), log-mel features and encoder output (float32);
+    an array over its budget becomes a seeded sample of the same positions on every run, and all of it stays within 64 MB."""
+    import numpy as np
+    import torch
+    b = _bench()
+
+    class Eng:
+        def encoder_output(self, B):
+            return torch.arange(B * 1500 * 1280, dtype=torch.float32).reshape(B, 1500, 1280)
+    B = 8
+    last = {"seqs": [[1, 2, 3, 4], [1, 2]] + [[5] * 6] * (B - 2), "feats": torch.ones(B, 80, 3000)}
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), last, Eng(), B)
+    out = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("tokens", "logmel", "encoder_output")}
+    assert out["tokens"].dtype == np.float64 and out["tokens"].shape == (B, 6)
+    assert out["tokens"][0].tolist() == [1, 2, 3, 4, -1, -1] and out["tokens"][1].tolist() == [1, 2, -1, -1, -1, -1]
+    assert out["logmel"].dtype == out["encoder_output"].dtype == np.float32
+    assert out["logmel"].shape == (B, 80, 3000)                              # under its budget: whole
+    assert out["encoder_output"].ndim == 1 and out["encoder_output"].size < B * 1500 * 1280      # over it: a sample
+    assert np.array_equal(out["encoder_output"], np.load(tmp_path / "b" / "encoder_output.npy"))
+    assert sum(a.nbytes for a in out.values()) <= 64e6
+    last_pool = {"seqs": last["seqs"]}                                       # micro-batched contexts: the token ids only
+    b.dump_outputs(str(tmp_path / "c"), last_pool, Eng(), B)
+    assert sorted(p.name for p in (tmp_path / "c").iterdir()) == ["tokens.npy"]
