@@ -178,8 +178,24 @@ int wm_encode(wm_ctx* ctx, const float* feats, int B);
  * is in the state wm_encode leaves.  Not available on an enc_fp8 context (WM_ERR_ARG). */
 int wm_set_encoder_output(wm_ctx* ctx, const float* hidden, int B);
 
+/* Whisper timestamp rules for one decode (additive to ABI v9).  Stands in for the `return_timestamps=True` branch the reference leaves
+ * as a TODO (model.py:1171-1175): HF WhisperGenerationMixin.generate builds a WhisperTimeStampLogitsProcessor(generation_config,
+ * begin_index) (transformers generation/logits_process.py) and runs it after the other processors on every step.  The engine applies
+ * it inside its select kernels to every logits row with that row's OWN prefix: base / head rows the committed ids[:L], verify row i
+ * ids[:L] + c_0 .. c_i.  Timestamp token t means (t - timestamp_begin) * time_precision seconds. */
+typedef struct wm_timestamp_params {
+    int32_t timestamp_begin;             /* first timestamp token = no_timestamps_token_id + 1; the timestamps are [timestamp_begin, vocab) */
+    int32_t no_timestamps_token_id;      /* always masked */
+    int32_t max_initial_timestamp_index; /* generation_config.max_initial_timestamp_index; < 0 = none */
+    int32_t begin_index;                 /* the processor's begin_index (ids[begin_index:] are the sampled tokens); < 0: the wm_gen_params one */
+} wm_timestamp_params;
+
 /* ---- F3..F14 the Medusa decode loop (replaces _medusa_greedy_search, model.py:404-835) ---- */
 int wm_decode_begin(wm_ctx* ctx, const wm_gen_params* gp, int B);
+/* wm_decode_begin with the timestamp rules on (ts != NULL; NULL = wm_decode_begin).  WM_ERR_ARG (wm_last_error says why): a candidate tree
+ * (medusa_choices with top-k > 1), timestamp_begin != no_timestamps_token_id + 1, eos / the first prompt token not below timestamp_begin,
+ * or fewer than 2 timestamp tokens in the vocabulary.  Replaces generate(return_timestamps=True) of the reference / HF. */
+int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* ts, int B);
 /* Runs up to max_iters iterations (each = base pass + verify pass + accept), replayed from a
  * hipGraph after the first; returns the number of unfinished streams in *n_unfinished.
  * Several streams with candidate chains run the merged-step schedule: max_iters then counts STEPS (one pass each:
@@ -202,6 +218,16 @@ int wm_get_encoder_output(wm_ctx* ctx, int B, float* out /* HOST */);
  * before wm_decode_begin, or begin again afterwards. */
 int wm_forward_logits(wm_ctx* ctx, int B, const int32_t* tokens /* HOST [B][T] */, int T, int pos0,
                       int disable_medusa, float* logits_out);
+/* Timestamp parity tap: R caller-given logits rows (HOST float32 [R][vocab]) through the decode loop's state fold and select kernels
+ * (k_select1_ts / k_select2_ts), as verify rows whose prefixes are prefixes[r][0 .. lens[r]) (HOST int32 [R][Tmax]).  The
+ * suppress and begin-suppress lists of gp apply with cur_len = lens[0] for every row (the reference's one-length convention), the
+ * exponential decay does not; the sampling temperature is gp->temperature.  Outputs (HOST, [R] each): the processed arg-max, p(probe_tokens[r]) under the softmax at 1/T, the entropy
+ * H = -sum p log(p + 1e-5) (medusa_utils.py:566-568), and 1 where the log-softmax decision masked all text.  What it stands in for: HF
+ * WhisperTimeStampLogitsProcessor.__call__ on one row plus the typical-acceptance statistics.  Overwrites the decode state like
+ * wm_forward_logits (begin again afterwards).  Any R >= 1 (worked in groups of 15). */
+int wm_select_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* ts, int R, const float* logits, const int32_t* prefixes,
+                   int Tmax, const int32_t* lens, const int32_t* probe_tokens, int32_t* out_argmax, float* out_p_probe, float* out_entropy,
+                   int32_t* out_ts_forced);
 /* cross K/V of one kv-layer/stream/head: HOST float32 [n_ctx][64] each */
 int wm_get_cross_kv(wm_ctx* ctx, int kv_layer, int stream, int head, float* k_out, float* v_out);
 /* Times `reps` launches of one decode-path kernel class in its current shape with hipEvents on

@@ -635,6 +635,69 @@ __device__ __forceinline__ float proc_logit(float x, int n, int cur_len, const G
     return x;
 }
 
+// ---- Whisper timestamp rules (wm_decode_begin_ts; HF WhisperTimeStampLogitsProcessor.__call__, applied after the processors above) ----
+// A row's per-token masks come from its prefix ids[:len] through a compact state (TsDev); the row-global log-softmax decision
+// (logsumexp of the timestamps > the best text token -> all text masked) is finished by every consumer from the slice partials of the
+// two regions [0, tb) and [tb, V).
+__device__ __forceinline__ float ts_mask(float v, int n, int4 rec, const GenDev& gp, const TsDev& ts)
+{
+    if (n == ts.nots) return -INFINITY;
+    if (n >= ts.tb) return (n < rec.x || n > rec.y) ? -INFINITY : v;
+    return ((rec.z & 2) || ((rec.z & 1) && n < gp.eos)) ? -INFINITY : v;
+}
+// the row's record: base / head rows of stream s from the committed state at L; verify row i from k_cand_fin's fold
+__device__ __forceinline__ int4 ts_row_record(const GenDev& gp, const TsDev& ts, int ts_verify, int s, int i, int cur_len)
+{
+    return ts_verify ? ts.ver[s * WM_CAND_STRIDE + i] : ts_record(ts.st[s], cur_len, gp.begin, ts.tb, gp.V, ts.mit);
+}
+struct TsSel { float mx; int mi; float z; int forced; };
+// finish a row from its SEL_SP x 2 slice partials: the decision, then (arg-max, max, softmax denominator at 1/T) of what it leaves
+__device__ __forceinline__ TsSel ts_finish(const float* p1, const float* p1t, float inv_temp)
+{
+    float mt = -INFINITY, ms = -INFINITY; int it = 0x7fffffff, is = 0x7fffffff;
+    for (int k = 0; k < SEL_SP; ++k) {
+        const float v = p1[4 * k]; const int idx = __float_as_int(p1[4 * k + 1]);
+        if (v > mt || (v == mt && idx < it)) { mt = v; it = idx; }
+        const float u = p1t[4 * k]; const int iu = __float_as_int(p1t[4 * k + 1]);
+        if (u > ms || (u == ms && iu < is)) { ms = u; is = iu; }
+    }
+    float zt = 0.f, zs = 0.f, zs1 = 0.f;
+    for (int k = 0; k < SEL_SP; ++k) {
+        const float v = p1[4 * k], u = p1t[4 * k];
+        if (v != -INFINITY) zt += p1[4 * k + 2] * expf((v - mt) * inv_temp);
+        if (u != -INFINITY) { zs += p1t[4 * k + 2] * expf((u - ms) * inv_temp); zs1 += p1t[4 * k + 3] * expf(u - ms); }
+    }
+    TsSel r;
+    r.forced = (ms != -INFINITY && ms + logf(zs1) > mt) ? 1 : 0;     // logsumexp(ts) > max(text), both shifted by the same log Z
+    if (r.forced) { r.mx = ms; r.mi = is; r.z = zs; }
+    else if (ms > mt) { r.mx = ms; r.mi = is; r.z = zs + (mt == -INFINITY ? 0.f : zt * expf((mt - ms) * inv_temp)); }
+    else { r.mx = mt; r.mi = it; r.z = zt + (ms == -INFINITY ? 0.f : zs * expf((ms - mt) * inv_temp)); }
+    return r;
+}
+__device__ __forceinline__ void block_argmax(float& mx, int& mi, float* sv, int* si, int tid)
+{
+    const int lane = tid & 63, w = tid >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(mx, o, 64); const int oi = __shfl_xor(mi, o, 64);
+        if (ov > mx || (ov == mx && oi < mi)) { mx = ov; mi = oi; }
+    }
+    __syncthreads();
+    if (lane == 0) { sv[w] = mx; si[w] = mi; }
+    __syncthreads();
+    mx = sv[0]; mi = si[0];
+#pragma unroll
+    for (int k = 1; k < 4; ++k) if (sv[k] > mx || (sv[k] == mx && si[k] < mi)) { mx = sv[k]; mi = si[k]; }
+}
+__device__ __forceinline__ float block_sum(float z, float* sz, int tid)
+{
+    z = wave_sum(z);
+    __syncthreads();
+    if ((tid & 63) == 0) sz[tid >> 6] = z;
+    __syncthreads();
+    return (sz[0] + sz[1]) + (sz[2] + sz[3]);
+}
+
 // Sibling rows (wm_config.sibling_rows; one stream): the tokens of nodes K+1 .. K+S of the verify pass = head 1's top-2 .. top-(S+1) processed
 // logits (descending, lower index first on equal values), leaves under the root at position L + 1.  They never enter the acceptance rule
 // (medusa_utils.py:526-641 runs on the chain); k_accept only asks whether the next root — argmax v_0 after an accept length of 0 — is one of them.
@@ -672,33 +735,44 @@ __device__ __forceinline__ void sib_insert(float (&tv)[6], int (&ti)[6], float v
     }
 }
 
-// NEED_Z = false (candidate stage: only the arg-max is consumed) skips the second sweep, the slice's softmax denominator
-template <bool NEED_Z = true>
-__global__ void __launch_bounds__(256)
-k_select1(const float* __restrict__ logits, GenDev gp, const unsigned char* __restrict__ mask, const float* __restrict__ exppen,
-          const int* __restrict__ L, int rps, float* __restrict__ part1, const int4* __restrict__ rowinfo = nullptr,
-          float2* __restrict__ sibpart = nullptr)
+// NEED_Z = false (candidate stage: only the arg-max is consumed) skips the second sweep, the slice's softmax denominator.
+// TS (timestamp rules on): the row's record masks, and the slice keeps two partial sets — text [0, tb) in part1, timestamps [tb, V) in
+// ts.part1t — whose consumers finish the row-global decision (ts_finish); the timestamp region's sum at temperature 1 is always taken.
+// ts_verify: the rows are verify rows (records from k_cand_fin), else base / head rows (record from the committed state at L).
+template <bool NEED_Z, bool TS>
+__device__ __forceinline__ void
+select1_body(const float* __restrict__ logits, const GenDev& gp, const unsigned char* __restrict__ mask, const float* __restrict__ exppen,
+             const int* __restrict__ L, int rps, float* __restrict__ part1, const int4* __restrict__ rowinfo, float2* __restrict__ sibpart,
+             const TsDev& ts, int ts_verify)
 {
     __shared__ float sv[4]; __shared__ int si[4]; __shared__ float sz[4];
     const int row = blockIdx.y, sp = blockIdx.x;
-    int s = row / rps;
+    int s = row / rps, ri_i = row - s * rps;
     const bool sibrow = sibpart != nullptr && row - s * rps == 1;       // head 1's row of a stream whose verify pass carries sibling rows
     if (rowinfo) {                          // merged-step schedule: dense rows; only a stream's verify rows are scored
         const int4 ri = rowinfo[row];
         if (ri.w != 2) return;
-        s = ri.x;
+        s = ri.x; ri_i = ri.y;
     }
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int cur_len = L[s];
     const float* x = logits + (size_t)row * gp.Vpad;
     const int per = (gp.V + SEL_SP - 1) / SEL_SP, n0 = sp * per, n1 = min(gp.V, n0 + per);
+    int4 rec = make_int4(0, 0, 0, 0);
+    if (TS) rec = ts_row_record(gp, ts, ts_verify, s, ri_i, cur_len);
+    auto pl = [&](int n) {
+        float v = proc_logit(x[n], n, cur_len, gp, mask, exppen);
+        if (TS) v = ts_mask(v, n, rec, gp, ts);
+        return v;
+    };
     float mx = -INFINITY; int mi = 0x7fffffff;
     if (sibrow) {
-        // the slice's six best (the first of them is the slice arg-max the chain needs)
+        // the slice's six best (the first of them is the slice arg-max the chain needs; timestamp rules on: the siblings are chosen under
+        // the row's masks without the log-softmax decision, the chain's candidate comes from the region partials below)
         float tv[6]; int ti[6];
 #pragma unroll
         for (int j = 0; j < 6; ++j) { tv[j] = -INFINITY; ti[j] = 0x7fffffff; }
-        for (int n = n0 + tid; n < n1; n += 256) sib_insert(tv, ti, proc_logit(x[n], n, cur_len, gp, mask, exppen), n);
+        for (int n = n0 + tid; n < n1; n += 256) sib_insert(tv, ti, pl(n), n);
         float2* mine = sibpart + ((size_t)s * SEL_SP + sp) * 6;
         float m0 = -INFINITY; int i0 = 0x7fffffff;
         for (int j = 0; j < 6; ++j) {
@@ -709,7 +783,7 @@ k_select1(const float* __restrict__ logits, GenDev gp, const unsigned char* __re
         }
         __syncthreads();
         mx = m0; mi = i0;
-    } else {
+    } else if (!TS) {
         for (int n = n0 + tid; n < n1; n += 256) {
             const float v = proc_logit(x[n], n, cur_len, gp, mask, exppen);
             if (v > mx || (v == mx && n < mi)) { mx = v; mi = n; }
@@ -724,6 +798,32 @@ k_select1(const float* __restrict__ logits, GenDev gp, const unsigned char* __re
         mx = sv[0]; mi = si[0];
 #pragma unroll
         for (int k = 1; k < 4; ++k) if (sv[k] > mx || (sv[k] == mx && si[k] < mi)) { mx = sv[k]; mi = si[k]; }
+    }
+    if (TS) {
+        // two regions: the boundary tb falls inside a slice, so the test is per element
+        float mt = -INFINITY, ms = -INFINITY; int it = 0x7fffffff, is = 0x7fffffff;
+        for (int n = n0 + tid; n < n1; n += 256) {
+            const float v = pl(n);
+            if (n < ts.tb) { if (v > mt || (v == mt && n < it)) { mt = v; it = n; } }
+            else if (v > ms || (v == ms && n < is)) { ms = v; is = n; }
+        }
+        block_argmax(mt, it, sv, si, tid);
+        block_argmax(ms, is, sv, si, tid);
+        float zt = 0.f, zs = 0.f, zs1 = 0.f;
+        for (int n = (NEED_Z ? n0 : max(n0, ts.tb)) + tid; n < n1; n += 256) {
+            const float v = pl(n);
+            if (v == -INFINITY) continue;
+            if (n < ts.tb) zt += expf((v - mt) * gp.inv_temp);
+            else { if (NEED_Z) zs += expf((v - ms) * gp.inv_temp); zs1 += expf(v - ms); }
+        }
+        zt = block_sum(zt, sz, tid); zs = block_sum(zs, sz, tid); zs1 = block_sum(zs1, sz, tid);
+        if (tid == 0) {
+            float* o = part1 + ((size_t)row * SEL_SP + sp) * 4;
+            o[0] = mt; o[1] = __int_as_float(it); o[2] = zt;
+            float* q = ts.part1t + ((size_t)row * SEL_SP + sp) * 4;
+            q[0] = ms; q[1] = __int_as_float(is); q[2] = zs; q[3] = zs1;
+        }
+        return;
     }
     float z = 0.f;
     if (NEED_Z && mx != -INFINITY)
@@ -740,11 +840,30 @@ k_select1(const float* __restrict__ logits, GenDev gp, const unsigned char* __re
     }
 }
 
+// the kernels: timestamps off keeps the name and arguments of the plain kernel; k_select1_ts adds the rules' state (TsDev)
+template <bool NEED_Z = true>
 __global__ void __launch_bounds__(256)
-k_select2(const float* __restrict__ logits, GenDev gp, const unsigned char* __restrict__ mask, const float* __restrict__ exppen,
-          const int* __restrict__ L, const int* __restrict__ cand, int rps, int out_row0, const float* __restrict__ part1,
-          float* __restrict__ part2, int* __restrict__ amax, float* __restrict__ pc, const TreeDev* __restrict__ tree,
-          const int4* __restrict__ rowinfo = nullptr)
+k_select1(const float* __restrict__ logits, GenDev gp, const unsigned char* __restrict__ mask, const float* __restrict__ exppen,
+          const int* __restrict__ L, int rps, float* __restrict__ part1, const int4* __restrict__ rowinfo = nullptr,
+          float2* __restrict__ sibpart = nullptr)
+{
+    select1_body<NEED_Z, false>(logits, gp, mask, exppen, L, rps, part1, rowinfo, sibpart, TsDev{}, 0);
+}
+template <bool NEED_Z>
+__global__ void __launch_bounds__(256)
+k_select1_ts(const float* __restrict__ logits, GenDev gp, const unsigned char* __restrict__ mask, const float* __restrict__ exppen,
+             const int* __restrict__ L, int rps, float* __restrict__ part1, const int4* __restrict__ rowinfo, float2* __restrict__ sibpart,
+             TsDev ts, int ts_verify)
+{
+    select1_body<NEED_Z, true>(logits, gp, mask, exppen, L, rps, part1, rowinfo, sibpart, ts, ts_verify);
+}
+
+template <bool TS>
+__device__ __forceinline__ void
+select2_body(const float* __restrict__ logits, const GenDev& gp, const unsigned char* __restrict__ mask, const float* __restrict__ exppen,
+             const int* __restrict__ L, const int* __restrict__ cand, int rps, int out_row0, const float* __restrict__ part1,
+             float* __restrict__ part2, int* __restrict__ amax, float* __restrict__ pc, const TreeDev* __restrict__ tree,
+             const int4* __restrict__ rowinfo, const TsDev& ts)
 {
     __shared__ float sh[4];
     const int row = blockIdx.y, sp = blockIdx.x;
@@ -759,22 +878,36 @@ k_select2(const float* __restrict__ logits, GenDev gp, const unsigned char* __re
     const float* x = logits + (size_t)row * gp.Vpad;
     const float* p1 = part1 + (size_t)row * SEL_SP * 4;
     float mx = -INFINITY; int mi = 0x7fffffff;
+    float invz;
+    int4 rec = make_int4(0, 0, 0, 0); int forced = 0;
+    if (TS) {
+        // verify rows only: the record k_cand_fin folded from c_0 .. c_i; text masked when the row's decision says so
+        const TsSel f = ts_finish(p1, ts.part1t + (size_t)row * SEL_SP * 4, gp.inv_temp);
+        mx = f.mx; mi = f.mi; invz = 1.0f / f.z; forced = f.forced;
+        rec = ts.ver[s * WM_CAND_STRIDE + i];
+    } else {
 #pragma unroll
-    for (int k = 0; k < SEL_SP; ++k) {
-        const float v = p1[4 * k]; const int idx = __float_as_int(p1[4 * k + 1]);
-        if (v > mx || (v == mx && idx < mi)) { mx = v; mi = idx; }
-    }
-    float z = 0.f;
+        for (int k = 0; k < SEL_SP; ++k) {
+            const float v = p1[4 * k]; const int idx = __float_as_int(p1[4 * k + 1]);
+            if (v > mx || (v == mx && idx < mi)) { mx = v; mi = idx; }
+        }
+        float z = 0.f;
 #pragma unroll
-    for (int k = 0; k < SEL_SP; ++k) {
-        const float v = p1[4 * k];
-        z += (v == -INFINITY) ? 0.f : p1[4 * k + 2] * expf((v - mx) * gp.inv_temp);
+        for (int k = 0; k < SEL_SP; ++k) {
+            const float v = p1[4 * k];
+            z += (v == -INFINITY) ? 0.f : p1[4 * k + 2] * expf((v - mx) * gp.inv_temp);
+        }
+        invz = 1.0f / z;
     }
-    const float invz = 1.0f / z;
+    auto pl = [&](int n) {
+        float v = proc_logit(x[n], n, cur_len, gp, mask, exppen);
+        if (TS) { v = ts_mask(v, n, rec, gp, ts); if (forced && n < ts.tb) v = -INFINITY; }
+        return v;
+    };
     const int per = (gp.V + SEL_SP - 1) / SEL_SP, n0 = sp * per, n1 = min(gp.V, n0 + per);
     float hs = 0.f;
     for (int n = n0 + tid; n < n1; n += 256) {
-        const float v = proc_logit(x[n], n, cur_len, gp, mask, exppen);
+        const float v = pl(n);
         const float p = (v == -INFINITY) ? 0.f : expf((v - mx) * gp.inv_temp) * invz;
         hs += p * logf(p + 1e-5f);
     }
@@ -786,6 +919,7 @@ k_select2(const float* __restrict__ logits, GenDev gp, const unsigned char* __re
         part2[(size_t)orow * SEL_SP + sp] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
         if (sp == 0) {
             amax[orow] = mi;
+            if (TS) ts.forced[orow] = forced;
             if (tree) {
                 // candidate tree: this row is node i's distribution; every child's token is scored under it (pc indexed by child)
                 if (i == 0) pc[out_row0 + s * rps] = 0.f;
@@ -800,7 +934,7 @@ k_select2(const float* __restrict__ logits, GenDev gp, const unsigned char* __re
                 float pcv = 0.f;
                 if (i + 1 < rps) {
                     const int c = cand[s * WM_CAND_STRIDE + i + 1];
-                    const float vc = proc_logit(x[c], c, cur_len, gp, mask, exppen);
+                    const float vc = pl(c);
                     pcv = (vc == -INFINITY) ? 0.f : expf((vc - mx) * gp.inv_temp) * invz;
                 }
                 pc[orow] = pcv;
@@ -809,7 +943,23 @@ k_select2(const float* __restrict__ logits, GenDev gp, const unsigned char* __re
     }
 }
 
-// argmax of each row from the slice partials (base pass candidates / vanilla token)
+__global__ void __launch_bounds__(256)
+k_select2(const float* __restrict__ logits, GenDev gp, const unsigned char* __restrict__ mask, const float* __restrict__ exppen,
+          const int* __restrict__ L, const int* __restrict__ cand, int rps, int out_row0, const float* __restrict__ part1,
+          float* __restrict__ part2, int* __restrict__ amax, float* __restrict__ pc, const TreeDev* __restrict__ tree,
+          const int4* __restrict__ rowinfo = nullptr)
+{
+    select2_body<false>(logits, gp, mask, exppen, L, cand, rps, out_row0, part1, part2, amax, pc, tree, rowinfo, TsDev{});
+}
+__global__ void __launch_bounds__(256)
+k_select2_ts(const float* __restrict__ logits, GenDev gp, const unsigned char* __restrict__ mask, const float* __restrict__ exppen,
+             const int* __restrict__ L, const int* __restrict__ cand, int rps, int out_row0, const float* __restrict__ part1,
+             float* __restrict__ part2, int* __restrict__ amax, float* __restrict__ pc, const int4* __restrict__ rowinfo, TsDev ts)
+{
+    select2_body<true>(logits, gp, mask, exppen, L, cand, rps, out_row0, part1, part2, amax, pc, nullptr, rowinfo, ts);
+}
+
+// argmax of each row from the slice partials (base pass candidates / vanilla token); k_select_argmax_ts: after the row's decision
 __global__ void k_select_argmax(const float* __restrict__ part1, int nrows, int out_row0, int* __restrict__ amax)
 {
     const int row = blockIdx.x * blockDim.x + threadIdx.x;
@@ -821,6 +971,14 @@ __global__ void k_select_argmax(const float* __restrict__ part1, int nrows, int 
         if (v > mx || (v == mx && idx < mi)) { mx = v; mi = idx; }
     }
     amax[out_row0 + row] = mi;
+}
+__global__ void k_select_argmax_ts(const float* __restrict__ part1, int nrows, int out_row0, int* __restrict__ amax, TsDev ts)
+{
+    const int row = blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= nrows) return;
+    const TsSel f = ts_finish(part1 + (size_t)row * SEL_SP * 4, ts.part1t + (size_t)row * SEL_SP * 4, 1.0f);
+    amax[out_row0 + row] = f.mi;
+    ts.forced[out_row0 + row] = f.forced;
 }
 
 // batched hidden-state carry, Medusa-Block: rows of carrying streams take the saved block-layer output
@@ -837,20 +995,37 @@ __global__ void k_rows_take_carried(float* __restrict__ dst, const float* __rest
 
 // Candidates of the base pass: cand[s][i] = argmax of head i (medusa_utils.py:446-458, top-1 chain), from the slice partials in ONE launch (one
 // block per stream): row i's arg-max over its SEL_SP slices -> amax, cand[s][i] (rounds 1-5: k_select_argmax + a k_set_cand launch); with sibling rows, the S + 1 best of head 1's SEL_SP x 6 slice winners -> cand[s][K+1 ..].
-__global__ void __launch_bounds__(256)
-k_cand_fin(const float* __restrict__ part1, GenDev gp, int* __restrict__ amax, int* __restrict__ cand, const float2* __restrict__ sibpart)
+// TS (timestamp rules): each row's arg-max after its decision; then the verify rows' records: row i follows c_0 .. c_i, so the committed
+// state is folded with those candidates (prefix length L + i + 1)
+template <bool TS>
+__device__ __forceinline__ void
+cand_fin_body(const float* __restrict__ part1, const GenDev& gp, int* __restrict__ amax, int* __restrict__ cand, const float2* __restrict__ sibpart,
+              const TsDev& ts)
 {
     __shared__ float sv[4]; __shared__ int si[4];
     const int s = blockIdx.x, tid = threadIdx.x, rps = gp.K + 1;
     if (tid < rps) {
         const float* p1 = part1 + (size_t)(s * rps + tid) * SEL_SP * 4;
         float mx = -INFINITY; int mi = 0x7fffffff;
-        for (int k = 0; k < SEL_SP; ++k) {
-            const float v = p1[4 * k]; const int idx = __float_as_int(p1[4 * k + 1]);
-            if (v > mx || (v == mx && idx < mi)) { mx = v; mi = idx; }
-        }
+        if (TS) mi = ts_finish(p1, ts.part1t + (size_t)(s * rps + tid) * SEL_SP * 4, 1.0f).mi;
+        else
+            for (int k = 0; k < SEL_SP; ++k) {
+                const float v = p1[4 * k]; const int idx = __float_as_int(p1[4 * k + 1]);
+                if (v > mx || (v == mx && idx < mi)) { mx = v; mi = idx; }
+            }
         amax[s * rps + tid] = mi;
         cand[s * WM_CAND_STRIDE + tid] = mi;
+    }
+    if (TS) {
+        __syncthreads();
+        if (tid == 0) {
+            int4 st = ts.st[s];
+            const int len = ts.L[s];
+            for (int i = 0; i < rps; ++i) {
+                st = ts_fold(st, cand[s * WM_CAND_STRIDE + i], ts.tb);
+                ts.ver[s * WM_CAND_STRIDE + i] = ts_record(st, len + i + 1, gp.begin, ts.tb, gp.V, ts.mit);
+            }
+        }
     }
     if (gp.sib <= 0 || sibpart == nullptr) return;
     float tv[6]; int ti[6];
@@ -865,6 +1040,18 @@ k_cand_fin(const float* __restrict__ part1, GenDev gp, int* __restrict__ amax, i
         sib_block_pop(tv, ti, sv, si, tid, mx, mi);
         if (tid == 0 && j > 0) cand[s * WM_CAND_STRIDE + gp.K + j] = (mi == 0x7fffffff) ? -1 : mi;      // (-1: fewer than j + 1 unsuppressed tokens — never a hit)
     }
+}
+
+__global__ void __launch_bounds__(256)
+k_cand_fin(const float* __restrict__ part1, GenDev gp, int* __restrict__ amax, int* __restrict__ cand, const float2* __restrict__ sibpart)
+{
+    cand_fin_body<false>(part1, gp, amax, cand, sibpart, TsDev{});
+}
+__global__ void __launch_bounds__(256)
+k_cand_fin_ts(const float* __restrict__ part1, GenDev gp, int* __restrict__ amax, int* __restrict__ cand, const float2* __restrict__ sibpart,
+              TsDev ts)
+{
+    cand_fin_body<true>(part1, gp, amax, cand, sibpart, ts);
 }
 
 // merged-step schedule: what every stream contributes to this step's pass, as DENSE rows.  carry[s] (k_accept of the previous step /
@@ -902,13 +1089,15 @@ k_step_begin(const int* __restrict__ carry, const int* __restrict__ L, const int
 // Then emit tokens, keep the accepted provisional KV rows by advancing kvlen (model.py:378-402), apply
 // the stop rules (model.py:774-793).
 // ---------------------------------------------------------------------------------------------
-__global__ void k_accept(GenDev gp, const int* __restrict__ cand, const int* __restrict__ amax, const float* __restrict__ pc,
-                         const float* __restrict__ part2, int* __restrict__ ids, int* __restrict__ L, int* __restrict__ kvlen,
-                         int* __restrict__ finished, int* __restrict__ niter, long long* __restrict__ hist, int* __restrict__ done, int B,
-                         int* __restrict__ carry, const float* __restrict__ hf, float* __restrict__ hf_keep, int d,
-                         int* __restrict__ hostflags, const float* __restrict__ hb, float* __restrict__ hb_keep,
-                         const int4* __restrict__ sinfo = nullptr, int* __restrict__ sel_src = nullptr, int* __restrict__ sel_n = nullptr,
-                         int* __restrict__ sel_base = nullptr)
+// TS (timestamp rules): the emitted tokens are folded into the stream's committed state (ts.st) for the next base / head rows
+template <bool TS>
+__device__ __forceinline__ void
+accept_body(const GenDev& gp, const int* __restrict__ cand, const int* __restrict__ amax, const float* __restrict__ pc,
+            const float* __restrict__ part2, int* __restrict__ ids, int* __restrict__ L, int* __restrict__ kvlen,
+            int* __restrict__ finished, int* __restrict__ niter, long long* __restrict__ hist, int* __restrict__ done, int B,
+            int* __restrict__ carry, const float* __restrict__ hf, float* __restrict__ hf_keep, int d,
+            int* __restrict__ hostflags, const float* __restrict__ hb, float* __restrict__ hb_keep,
+            const int4* __restrict__ sinfo, int* __restrict__ sel_src, int* __restrict__ sel_n, int* __restrict__ sel_base, const TsDev& ts)
 {
     const int s = blockIdx.x, lane = threadIdx.x;
     if (finished[s]) { if (sel_n && lane == 0) sel_n[s] = 0; return; }
@@ -980,6 +1169,11 @@ __global__ void k_accept(GenDev gp, const int* __restrict__ cand, const int* __r
     if (sel_n != nullptr && lane < 16) sel_src[s * 16 + lane] = (lane == 1 && sib_row >= 0) ? sib_row : lane;
     if (lane == 0) {
         const int Ln = Lcur + n_emit;
+        if (TS) {
+            int4 st = ts.st[s];
+            for (int j = 0; j < n_emit; ++j) st = ts_fold(st, (a == 0 && j == 1) ? amax[row0] : cand[s * WM_CAND_STRIDE + j], ts.tb);
+            ts.st[s] = st;
+        }
         L[s] = Ln;
         kvlen[s] = (a == 0 && sib_row < 0) ? Lcur + 1 : (do_carry ? Ln : Lcur + a);
         if (carry) carry[s] = do_carry ? 1 : 0;
@@ -996,6 +1190,25 @@ __global__ void k_accept(GenDev gp, const int* __restrict__ cand, const int* __r
         if (hostflags) { hostflags[0] = do_carry ? 1 : 0; hostflags[1] = fin ? 1 : 0; }   // host-mapped (single-stream runs)
     }
 }
+
+#define WM_ACCEPT_PARAMS                                                                                                        \
+    GenDev gp, const int* __restrict__ cand, const int* __restrict__ amax, const float* __restrict__ pc, const float* __restrict__ part2,  \
+    int* __restrict__ ids, int* __restrict__ L, int* __restrict__ kvlen, int* __restrict__ finished, int* __restrict__ niter,             \
+    long long* __restrict__ hist, int* __restrict__ done, int B, int* __restrict__ carry, const float* __restrict__ hf,                    \
+    float* __restrict__ hf_keep, int d, int* __restrict__ hostflags, const float* __restrict__ hb, float* __restrict__ hb_keep
+__global__ void k_accept(WM_ACCEPT_PARAMS, const int4* __restrict__ sinfo = nullptr, int* __restrict__ sel_src = nullptr,
+                         int* __restrict__ sel_n = nullptr, int* __restrict__ sel_base = nullptr)
+{
+    accept_body<false>(gp, cand, amax, pc, part2, ids, L, kvlen, finished, niter, hist, done, B, carry, hf, hf_keep, d, hostflags, hb, hb_keep,
+                       sinfo, sel_src, sel_n, sel_base, TsDev{});
+}
+__global__ void k_accept_ts(WM_ACCEPT_PARAMS, const int4* __restrict__ sinfo, int* __restrict__ sel_src, int* __restrict__ sel_n,
+                            int* __restrict__ sel_base, TsDev ts)
+{
+    accept_body<true>(gp, cand, amax, pc, part2, ids, L, kvlen, finished, niter, hist, done, B, carry, hf, hf_keep, d, hostflags, hb, hb_keep,
+                      sinfo, sel_src, sel_n, sel_base, ts);
+}
+#undef WM_ACCEPT_PARAMS
 
 // ---------------------------------------------------------------------------------------------
 // Candidate trees (medusa_choices with top-k > 1; generate_candidates, medusa_utils.py:424-458).
@@ -1173,13 +1386,16 @@ k_kv_compact(bf16_t* __restrict__ kc, bf16_t* __restrict__ vc, const int* __rest
     }
 }
 
-__global__ void k_accept_vanilla1(GenDev gp, int B, const int* __restrict__ amax, int* __restrict__ ids, int* __restrict__ L,
-                                  int* __restrict__ kvlen, int* __restrict__ finished, int* __restrict__ niter,
-                                  long long* __restrict__ hist, int* __restrict__ done)
+template <bool TS>
+__device__ __forceinline__ void
+accept_vanilla1_body(const GenDev& gp, int B, const int* __restrict__ amax, int* __restrict__ ids, int* __restrict__ L,
+                     int* __restrict__ kvlen, int* __restrict__ finished, int* __restrict__ niter,
+                     long long* __restrict__ hist, int* __restrict__ done, const TsDev& ts)
 {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= B || finished[s]) return;
     const int Lcur = L[s], tok = amax[s];
+    if (TS) ts.st[s] = ts_fold(ts.st[s], tok, ts.tb);
     if (Lcur < gp.Tids) ids[(size_t)s * gp.Tids + Lcur] = tok;
     L[s] = Lcur + 1; kvlen[s] = Lcur; niter[s] += 1;
     atomicAdd(reinterpret_cast<unsigned long long*>(hist + 16), 1ull);
@@ -1187,6 +1403,19 @@ __global__ void k_accept_vanilla1(GenDev gp, int B, const int* __restrict__ amax
         finished[s] = 1;
         if (atomicAdd(done + 1, 1) == B - 1) done[0] = 1;
     }
+}
+
+__global__ void k_accept_vanilla1(GenDev gp, int B, const int* __restrict__ amax, int* __restrict__ ids, int* __restrict__ L,
+                                  int* __restrict__ kvlen, int* __restrict__ finished, int* __restrict__ niter,
+                                  long long* __restrict__ hist, int* __restrict__ done)
+{
+    accept_vanilla1_body<false>(gp, B, amax, ids, L, kvlen, finished, niter, hist, done, TsDev{});
+}
+__global__ void k_accept_vanilla1_ts(GenDev gp, int B, const int* __restrict__ amax, int* __restrict__ ids, int* __restrict__ L,
+                                     int* __restrict__ kvlen, int* __restrict__ finished, int* __restrict__ niter,
+                                     long long* __restrict__ hist, int* __restrict__ done, TsDev ts)
+{
+    accept_vanilla1_body<true>(gp, B, amax, ids, L, kvlen, finished, niter, hist, done, ts);
 }
 
 // blocks per (stream, head) of the cross-attention: one per 256-key split while that is what fills the chip
@@ -1572,20 +1801,34 @@ int wm_dec_iteration(wm_ctx* ctx, int Mper_base)
     hipStream_t st = ctx->stream;
     const int B = ctx->Bdec, K = ctx->K, rps = K + 1;
     const GenDev gp = ctx->gp;
+    const TsDev ts = ctx->ts;
     if (gp.vanilla) {
         const int chunk = B;
         for (int b0 = 0; b0 < B; b0 += chunk) {
             const int nb = min(chunk, B - b0);
             int rc = wm_dec_pass(ctx, b0, nb, Mper_base, 0, 0, 0);
             if (rc) return rc;
+            if (ts.on) {            // (committed-state records: ts.st of stream b0 + row)
+                TsDev tsb = ts; tsb.st += b0;
+                k_select1_ts<false><<<dim3(SEL_SP, nb), dim3(256), 0, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L + b0, 1,
+                                                                               ctx->part1, nullptr, nullptr, tsb, 0);
+                WM_HIP(hipGetLastError());
+                k_select_argmax_ts<<<dim3((nb + 63) / 64), dim3(64), 0, st>>>(ctx->part1, nb, b0, ctx->amax, ts);
+                WM_HIP(hipGetLastError());
+                continue;
+            }
             hipLaunchKernelGGL(k_select1<false>, dim3(SEL_SP, nb), dim3(256), 0, st, ctx->logits, gp, ctx->supmask, ctx->exppen,
                                ctx->L + b0, 1, ctx->part1);
             WM_HIP(hipGetLastError());
             hipLaunchKernelGGL(k_select_argmax, dim3((nb + 63) / 64), dim3(64), 0, st, ctx->part1, nb, b0, ctx->amax);
             WM_HIP(hipGetLastError());
         }
-        hipLaunchKernelGGL(k_accept_vanilla1, dim3((B + 63) / 64), dim3(64), 0, st, gp, B, ctx->amax, ctx->ids, ctx->L,
-                           ctx->kvlen, ctx->finished, ctx->niter, ctx->hist, ctx->done);
+        if (ts.on)
+            k_accept_vanilla1_ts<<<dim3((B + 63) / 64), dim3(64), 0, st>>>(gp, B, ctx->amax, ctx->ids, ctx->L, ctx->kvlen, ctx->finished,
+                                                                               ctx->niter, ctx->hist, ctx->done, ts);
+        else
+            hipLaunchKernelGGL(k_accept_vanilla1, dim3((B + 63) / 64), dim3(64), 0, st, gp, B, ctx->amax, ctx->ids, ctx->L,
+                               ctx->kvlen, ctx->finished, ctx->niter, ctx->hist, ctx->done);
         WM_HIP(hipGetLastError());
         return WM_OK;
     }
@@ -1608,6 +1851,7 @@ int wm_dec_iter_rest(wm_ctx* ctx, int Mper_base)
     hipStream_t st = ctx->stream;
     const int B = ctx->Bdec, K = ctx->K, rps = K + 1, nb = B;
     const GenDev gp = ctx->gp;
+    const TsDev ts = ctx->ts;
     const bool carry = ctx->host_carry;
     ctx->hf_cur = ctx->hf;
     g_skinny_done = ctx->use_done ? ctx->done : nullptr;
@@ -1621,11 +1865,19 @@ int wm_dec_iter_rest(wm_ctx* ctx, int Mper_base)
     } else {
         // slice partials of every head's row (head 1's slices also keep their six best when the verify pass carries sibling rows), then ONE
         // block per stream turns them into the chain's candidates (+ the sibling tokens)
-        hipLaunchKernelGGL(k_select1<false>, dim3(SEL_SP, nb * rps), dim3(256), 0, st, ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, rps, ctx->part1,
-                           (const int4*)nullptr, gp.sib > 0 ? ctx->sibpart : nullptr);
-        WM_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_cand_fin, dim3(nb), dim3(256), 0, st, ctx->part1, gp, ctx->amax, ctx->cand, gp.sib > 0 ? ctx->sibpart : nullptr);
-        WM_HIP(hipGetLastError());
+        if (ts.on) {
+            k_select1_ts<false><<<dim3(SEL_SP, nb * rps), dim3(256), 0, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, rps, ctx->part1,
+                                                                                 nullptr, gp.sib > 0 ? ctx->sibpart : nullptr, ts, 0);
+            WM_HIP(hipGetLastError());
+            k_cand_fin_ts<<<dim3(nb), dim3(256), 0, st>>>(ctx->part1, gp, ctx->amax, ctx->cand, gp.sib > 0 ? ctx->sibpart : nullptr, ts);
+            WM_HIP(hipGetLastError());
+        } else {
+            hipLaunchKernelGGL(k_select1<false>, dim3(SEL_SP, nb * rps), dim3(256), 0, st, ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, rps, ctx->part1,
+                               (const int4*)nullptr, gp.sib > 0 ? ctx->sibpart : nullptr);
+            WM_HIP(hipGetLastError());
+            hipLaunchKernelGGL(k_cand_fin, dim3(nb), dim3(256), 0, st, ctx->part1, gp, ctx->amax, ctx->cand, gp.sib > 0 ? ctx->sibpart : nullptr);
+            WM_HIP(hipGetLastError());
+        }
     }
     // (d) verify pass over the candidates (chain: positions L..L+K; tree: node n at L + depth(n), ancestor-masked), then
     //     posterior statistics of every row
@@ -1640,6 +1892,30 @@ int wm_dec_iter_rest(wm_ctx* ctx, int Mper_base)
     } else
         rc = wm_dec_pass(ctx, 0, nb, vr, 1, 0, 1);
     if (rc) return rc;
+    if (ts.on) {            // (chain only: timestamps with a candidate tree are refused by wm_decode_begin_ts)
+        k_select1_ts<true><<<dim3(SEL_SP, nb * vr), dim3(256), 0, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, vr, ctx->part1,
+                                                                           nullptr, nullptr, ts, 1);
+        WM_HIP(hipGetLastError());
+        if (gp.accept_mode == WM_ACCEPT_TYPICAL)
+            k_select2_ts<<<dim3(SEL_SP, nb * vr), dim3(256), 0, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, ctx->cand, vr, 0,
+                                                                         ctx->part1, ctx->part2, ctx->amax, ctx->pc, nullptr, ts);
+        else
+            k_select_argmax_ts<<<dim3((nb * vr + 63) / 64), dim3(64), 0, st>>>(ctx->part1, nb * vr, 0, ctx->amax, ts);
+        WM_HIP(hipGetLastError());
+        k_accept_ts<<<dim3(B), dim3(64), 0, st>>>(gp, ctx->cand, ctx->amax, ctx->pc, ctx->part2, ctx->ids, ctx->L, ctx->kvlen, ctx->finished,
+                                                     ctx->niter, ctx->hist, ctx->done, B, (carry || ctx->dev_carry) ? ctx->carry : nullptr, ctx->hf,
+                                                     carry ? ctx->hf : ctx->hf_keep, ctx->d, carry ? ctx->hostflags_dev : nullptr,
+                                                     ctx->block ? ctx->hblk : nullptr, carry ? ctx->hblk : ctx->hb_keep, nullptr,
+                                                     gp.sib > 0 ? ctx->sel_src : nullptr, gp.sib > 0 ? ctx->sel_n : nullptr,
+                                                     gp.sib > 0 ? ctx->sel_base : nullptr, ts);
+        WM_HIP(hipGetLastError());
+        if (gp.sib > 0) {
+            hipLaunchKernelGGL(k_kv_compact, dim3(ctx->H, B, ctx->nkv), dim3(256), 0, st, ctx->kc, ctx->vc, ctx->sel_src, ctx->sel_n, ctx->sel_base,
+                               ctx->H, ctx->Tal, ctx->maxB);
+            WM_HIP(hipGetLastError());
+        }
+        return WM_OK;
+    }
     hipLaunchKernelGGL(k_select1<true>, dim3(SEL_SP, nb * vr), dim3(256), 0, st, ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, vr, ctx->part1);
     WM_HIP(hipGetLastError());
     if (gp.accept_mode == WM_ACCEPT_TYPICAL)
@@ -1688,6 +1964,7 @@ int wm_dec_step(wm_ctx* ctx, int)
     hipStream_t st = ctx->stream;
     const int B = ctx->Bdec, K = ctx->K, rps = K + 1;
     const GenDev gp = ctx->gp;
+    const TsDev ts = ctx->ts;
     g_skinny_done = ctx->use_done ? ctx->done : nullptr;
     g_skinny_ntiles = nullptr;
     if (B > 1024) { ctx->err = "merged-step schedule: more than 1024 streams"; return WM_ERR_ARG; }
@@ -1700,10 +1977,18 @@ int wm_dec_step(wm_ctx* ctx, int)
     int rc = wm_dec_stage_heads(ctx, B, 1, 0, 1);
     ctx->hblk = hblk_rows;
     if (rc) return rc;
-    hipLaunchKernelGGL(k_select1<false>, dim3(SEL_SP, B * rps), dim3(256), 0, st, ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, rps, ctx->part1, (const int4*)nullptr, (float2*)nullptr);
-    WM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_cand_fin, dim3(B), dim3(256), 0, st, ctx->part1, gp, ctx->amax, ctx->cand, (const float2*)nullptr);       // arg-max of every row -> cand, one launch
-    WM_HIP(hipGetLastError());
+    if (ts.on) {
+        k_select1_ts<false><<<dim3(SEL_SP, B * rps), dim3(256), 0, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, rps, ctx->part1,
+                                                                            nullptr, nullptr, ts, 0);
+        WM_HIP(hipGetLastError());
+        k_cand_fin_ts<<<dim3(B), dim3(256), 0, st>>>(ctx->part1, gp, ctx->amax, ctx->cand, nullptr, ts);
+        WM_HIP(hipGetLastError());
+    } else {
+        hipLaunchKernelGGL(k_select1<false>, dim3(SEL_SP, B * rps), dim3(256), 0, st, ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, rps, ctx->part1, (const int4*)nullptr, (float2*)nullptr);
+        WM_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_cand_fin, dim3(B), dim3(256), 0, st, ctx->part1, gp, ctx->amax, ctx->cand, (const float2*)nullptr);       // arg-max of every row -> cand, one launch
+        WM_HIP(hipGetLastError());
+    }
     // (d) ONE pass over the dense rows: verify rows and base rows; the launches are sized for B * rps rows, token tiles beyond the step's
     //     rows exit at once (g_skinny_ntiles)
     g_skinny_ntiles = ctx->steprows + 1;
@@ -1712,6 +1997,22 @@ int wm_dec_step(wm_ctx* ctx, int)
     if (rc == WM_OK) rc = wm_dec_stage_heads(ctx, B * rps, 1, 0, 0);
     g_skinny_ntiles = nullptr;
     if (rc) return rc;
+    if (ts.on) {
+        k_select1_ts<true><<<dim3(SEL_SP, B * rps), dim3(256), 0, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, rps, ctx->part1,
+                                                                           ctx->rowinfo, nullptr, ts, 1);
+        WM_HIP(hipGetLastError());
+        if (gp.accept_mode == WM_ACCEPT_TYPICAL)
+            k_select2_ts<<<dim3(SEL_SP, B * rps), dim3(256), 0, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, ctx->cand, rps, 0,
+                                                                         ctx->part1, ctx->part2, ctx->amax, ctx->pc, ctx->rowinfo, ts);
+        else
+            k_select_argmax_ts<<<dim3((B * rps + 63) / 64), dim3(64), 0, st>>>(ctx->part1, B * rps, 0, ctx->amax, ts);
+        WM_HIP(hipGetLastError());
+        k_accept_ts<<<dim3(B), dim3(64), 0, st>>>(gp, ctx->cand, ctx->amax, ctx->pc, ctx->part2, ctx->ids, ctx->L, ctx->kvlen, ctx->finished,
+                                                     ctx->niter, ctx->hist, ctx->done, B, ctx->carry, ctx->hf, ctx->hf_keep, ctx->d, nullptr,
+                                                     ctx->block ? ctx->hblk : nullptr, ctx->hb_keep, ctx->sinfo, nullptr, nullptr, nullptr, ts);
+        WM_HIP(hipGetLastError());
+        return WM_OK;
+    }
     hipLaunchKernelGGL(k_select1<true>, dim3(SEL_SP, B * rps), dim3(256), 0, st, ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, rps, ctx->part1, (const int4*)ctx->rowinfo, (float2*)nullptr);
     WM_HIP(hipGetLastError());
     if (gp.accept_mode == WM_ACCEPT_TYPICAL)
@@ -1813,3 +2114,33 @@ extern "C" int wm_debug_timeline(wm_ctx* ctx, void* buf, unsigned* idx, unsigned
     return WM_OK;
 }
 #endif
+
+// ---- timestamp parity tap (wm_select_rows): caller-given rows through the decode loop's state fold and select kernels ----------------
+// row r: prefix pre[r][0 .. len[r]) -> committed state of ids[begin:len] (ts_fold) -> the row's record at prefix length len[r], stored
+// where k_cand_fin puts the records of stream 0's verify rows
+__global__ void k_ts_tap_build(const int* __restrict__ pre, const int* __restrict__ len, int R, int Tmax, GenDev gp, TsDev ts)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R) return;
+    int4 st = make_int4(0, 0, -1, 0);
+    const int n = len[r];
+    for (int t = max(gp.begin, 0); t < n; ++t) st = ts_fold(st, pre[(size_t)r * Tmax + t], ts.tb);
+    ts.ver[r] = ts_record(st, n, gp.begin, ts.tb, gp.V, ts.mit);
+}
+
+int wm_dec_select_rows(wm_ctx* ctx, const int* pre_dev, const int* len_dev, int R, int Tmax)
+{
+    hipStream_t st = ctx->stream;
+    const GenDev gp = ctx->gp;
+    const TsDev ts = ctx->ts;
+    hipLaunchKernelGGL(k_ts_tap_build, dim3(1), dim3(64), 0, st, pre_dev, len_dev, R, Tmax, gp, ts);
+    WM_HIP(hipGetLastError());
+    // one "stream" of R + 1 rows: row i's probe token is cand[i + 1] (k_select2's p(c_{i+1})), its record ts.ver[i]
+    k_select1_ts<true><<<dim3(SEL_SP, R), dim3(256), 0, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, R + 1, ctx->part1,
+                                                                 nullptr, nullptr, ts, 1);
+    WM_HIP(hipGetLastError());
+    k_select2_ts<<<dim3(SEL_SP, R), dim3(256), 0, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, ctx->cand, R + 1, 0,
+                                                           ctx->part1, ctx->part2, ctx->amax, ctx->pc, nullptr, ts);
+    WM_HIP(hipGetLastError());
+    return WM_OK;
+}

@@ -36,7 +36,8 @@ extern "C" void wm_destroy(wm_ctx* ctx)
                     ctx->ybuf, ctx->cml, ctx->co, ctx->ticket, ctx->logits, ctx->amax, ctx->pc, ctx->part1, ctx->part2, ctx->ids, ctx->L, ctx->kvlen,
                     ctx->finished, ctx->cand, ctx->niter, ctx->hist, ctx->supmask, ctx->exppen, ctx->tap_tok, ctx->done,
                     ctx->hf_keep, ctx->hb_keep, ctx->carry, ctx->rowinfo, ctx->sinfo, ctx->steprows, ctx->rs_table, ctx->tree, ctx->sibtree, ctx->sibpart, ctx->sel_src, ctx->sel_n, ctx->sel_base, ctx->exn8, ctx->exs,
-                    ctx->xn, ctx->lnstats, ctx->foldv, ctx->kx8, ctx->vx8, ctx->kxs, ctx->vxs};
+                    ctx->xn, ctx->lnstats, ctx->foldv, ctx->kx8, ctx->vx8, ctx->kxs, ctx->vxs,
+                    ctx->ts.st, ctx->ts.ver, ctx->ts.part1t, ctx->ts.forced};
     for (void* b : bufs) if (b) hipFree(b);
     if (ctx->ev0) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) hipEventDestroy(ctx->ev1);
@@ -241,6 +242,11 @@ extern "C" int wm_create(const wm_config* cfg, const wm_weights* w, int device, 
     CREATE_HIP(dev_alloc(&ctx->pc, B * WM_TREE_MAX_NODES, st));
     CREATE_HIP(dev_alloc(&ctx->part1, RW * 16 * 4, st));
     CREATE_HIP(dev_alloc(&ctx->part2, B * WM_TREE_MAX_NODES * 16, st));
+    // timestamp rules (wm_decode_begin_ts): committed state per stream, verify-row records, timestamp-region partials, decisions
+    CREATE_HIP(dev_alloc(&ctx->ts.st, B, st));
+    CREATE_HIP(dev_alloc(&ctx->ts.ver, std::max<size_t>(B, RW) * WM_CAND_STRIDE, st));
+    CREATE_HIP(dev_alloc(&ctx->ts.part1t, RW * 16 * 4, st));
+    CREATE_HIP(dev_alloc(&ctx->ts.forced, RW + B, st));
     const size_t Tids = ctx->Tal;
     CREATE_HIP(dev_alloc(&ctx->ids, B * Tids, st));
     CREATE_HIP(dev_alloc(&ctx->L, B, st));
@@ -297,7 +303,29 @@ extern "C" int wm_set_encoder_output(wm_ctx* ctx, const float* hidden, int B)
     return wm_enc_set_output(ctx, hidden, B);
 }
 
-extern "C" int wm_decode_begin(wm_ctx* ctx, const wm_gen_params* gp, int B)
+// the timestamp scalars of a decode / tap: ts == NULL -> off.  Validation errors go to ctx->err.
+static int ts_setup(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* ts, TsDev* out)
+{
+    TsDev t = ctx->ts;
+    t.on = 0; t.tb = 0; t.nots = -1; t.mit = -1; t.L = ctx->L;
+    if (ts) {
+        if (ctx->tn) { ctx->err = "timestamps: not supported with a candidate tree (medusa_choices with top-k > 1)"; return WM_ERR_ARG; }
+        const int tb = ts->timestamp_begin;
+        if (tb != ts->no_timestamps_token_id + 1 || tb < 1 || ctx->V - tb < 2) {
+            ctx->err = "timestamps: timestamp_begin must be no_timestamps_token_id + 1 with at least 2 timestamp tokens in the vocabulary";
+            return WM_ERR_ARG;
+        }
+        if (gp->eos_token_id >= tb || (gp->prompt_len > 0 && gp->prompt[0] >= tb)) {
+            ctx->err = "timestamps: eos and the start token must lie below timestamp_begin"; return WM_ERR_ARG; }
+        t.on = 1; t.tb = tb; t.nots = ts->no_timestamps_token_id; t.mit = ts->max_initial_timestamp_index < 0 ? -1 : ts->max_initial_timestamp_index;
+    }
+    *out = t;
+    return WM_OK;
+}
+
+extern "C" int wm_decode_begin(wm_ctx* ctx, const wm_gen_params* gp, int B) { return wm_decode_begin_ts(ctx, gp, nullptr, B); }
+
+extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* tsp, int B)
 {
     if (!ctx || !gp) return WM_ERR_ARG;
     WM_HIP(hipSetDevice(ctx->device));
@@ -319,6 +347,9 @@ extern "C" int wm_decode_begin(wm_ctx* ctx, const wm_gen_params* gp, int B)
     g.inv_temp = (gp->accept_mode == WM_ACCEPT_TYPICAL && gp->temperature > 0.f) ? 1.0f / gp->temperature : 1.0f;
     g.force_accept = gp->force_accept;
     g.begin = gp->begin_index >= 0 ? gp->begin_index : P;
+    TsDev ts{};
+    if (int rc = ts_setup(ctx, gp, tsp, &ts)) return rc;
+    if (ts.on && tsp->begin_index >= 0) g.begin = tsp->begin_index;
     g.accept_mode = gp->accept_mode; g.vanilla = gp->vanilla; g.K = K; g.V = ctx->V; g.Vpad = ctx->Vpad; g.Tids = Tids;
     ctx->fuse = std::getenv("WM_NO_CARRY") == nullptr;
     ctx->host_carry = ctx->fuse && B == 1 && !gp->vanilla;
@@ -328,10 +359,11 @@ extern "C" int wm_decode_begin(wm_ctx* ctx, const wm_gen_params* gp, int B)
     ctx->step_flow = ctx->dev_carry && ctx->tn == 0 && std::getenv("WM_NO_STEP") == nullptr;
     g.fuse = ctx->host_carry ? 1 : (ctx->dev_carry ? (ctx->step_flow ? 3 : 2) : 0);
     g.sib = (ctx->host_carry && ctx->tn == 0 && ctx->sib_cfg > 0 && std::getenv("WM_NO_SIBLINGS") == nullptr) ? ctx->sib_cfg : 0;
-    const bool same = ctx->graph && ctx->graph_B == B && std::memcmp(&g, &ctx->gp, sizeof(GenDev)) == 0;
+    const bool same = ctx->graph && ctx->graph_B == B && std::memcmp(&g, &ctx->gp, sizeof(GenDev)) == 0 && ts.on == ctx->ts.on &&
+                      ts.tb == ctx->ts.tb && ts.nots == ctx->ts.nots && ts.mit == ctx->ts.mit;
     if (!same && ctx->graph) { hipGraphExecDestroy(ctx->graph); ctx->graph = nullptr; }
     if (!same && ctx->graph_base) { hipGraphExecDestroy(ctx->graph_base); ctx->graph_base = nullptr; }
-    ctx->gp = g; ctx->Bdec = B;
+    ctx->gp = g; ctx->Bdec = B; ctx->ts = ts;
 
     std::vector<int> ids((size_t)B * Tids, gp->pad_token_id), L(B, P), zero(B, 0);
     for (int b = 0; b < B; ++b) for (int i = 0; i < P; ++i) ids[(size_t)b * Tids + i] = gp->prompt[i];
@@ -355,6 +387,13 @@ extern "C" int wm_decode_begin(wm_ctx* ctx, const wm_gen_params* gp, int B)
     ctx->use_done = true;
     WM_HIP(hipMemcpyAsync(ctx->supmask, mask.data(), mask.size(), hipMemcpyHostToDevice, st));
     WM_HIP(hipMemcpyAsync(ctx->exppen, pen.data(), pen.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    std::vector<int4> tst(B, make_int4(0, 0, -1, 0));
+    if (ts.on) {                           // the committed timestamp state of the prompt's sampled part, ids[begin:P] (HF slices input_ids[begin_index:])
+        int4 s0 = make_int4(0, 0, -1, 0);
+        for (int i = std::max(g.begin, 0); i < P; ++i) s0 = ts_fold(s0, gp->prompt[i], ts.tb);
+        std::fill(tst.begin(), tst.end(), s0);
+        WM_HIP(hipMemcpyAsync(ctx->ts.st, tst.data(), B * sizeof(int4), hipMemcpyHostToDevice, st));
+    }
     WM_HIP(hipStreamSynchronize(st));      // host vectors go out of scope
     ctx->hostflags[0] = 0; ctx->hostflags[1] = 0;
     ctx->began = true; ctx->first_done = false; ctx->iters = 0; ctx->ms_decode = 0.f; ctx->graph_replays = 0;
@@ -551,6 +590,72 @@ extern "C" int wm_get_cross_kv(wm_ctx* ctx, int kv_layer, int stream, int head, 
 }
 
 // forward(): one decoder pass over T tokens per stream at positions pos0.., K/V appended at row pos0.
+static constexpr int SEL_SP_HOST = 16;         // select slices per logits row (wm_decoder.hip SEL_SP)
+
+// Timestamp parity tap: caller-given rows through the decode loop's timestamp state fold and select kernels (include/wm.h).
+extern "C" int wm_select_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* tsp, int R, const float* logits,
+                              const int32_t* prefixes, int Tmax, const int32_t* lens, const int32_t* probe_tokens, int32_t* out_argmax,
+                              float* out_p_probe, float* out_entropy, int32_t* out_ts_forced)
+{
+    if (!ctx) return WM_ERR_ARG;
+    if (!gp || !tsp || R < 1 || !logits || !prefixes || Tmax < 1 || !lens || !probe_tokens || !out_argmax || !out_p_probe || !out_entropy ||
+        !out_ts_forced) { ctx->err = "wm_select_rows: bad arguments"; return WM_ERR_ARG; }
+    for (int r = 0; r < R; ++r)
+        if (lens[r] < 1 || lens[r] > Tmax || probe_tokens[r] < 0 || probe_tokens[r] >= ctx->V) {
+            ctx->err = "wm_select_rows: lens must be in [1, Tmax] and probe tokens inside the vocabulary"; return WM_ERR_ARG; }
+    if (gp->eos_token_id < 0 || gp->eos_token_id >= ctx->V) { ctx->err = "wm_select_rows: eos out of range"; return WM_ERR_ARG; }
+    WM_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    TsDev ts{};
+    if (int rc = ts_setup(ctx, gp, tsp, &ts)) return rc;
+    GenDev g{};
+    g.P = gp->prompt_len; g.eos = gp->eos_token_id; g.pad = gp->pad_token_id;
+    g.max_length = g.hard_max_length = ctx->Tmax; g.exp_start = -1;
+    g.thr = gp->posterior_threshold; g.alpha = gp->posterior_alpha;
+    g.inv_temp = gp->temperature > 0.f ? 1.0f / gp->temperature : 1.0f;
+    g.force_accept = -1;
+    g.begin = tsp->begin_index >= 0 ? tsp->begin_index : (gp->begin_index >= 0 ? gp->begin_index : gp->prompt_len);
+    g.accept_mode = WM_ACCEPT_TYPICAL; g.vanilla = 0; g.K = ctx->K; g.V = ctx->V; g.Vpad = ctx->Vpad; g.Tids = ctx->Tal;
+    ctx->gp = g; ctx->ts = ts; ctx->began = false;
+    std::vector<unsigned char> mask(ctx->Vpad, 0);
+    for (int i = 0; i < gp->n_suppress; ++i) if (gp->suppress[i] >= 0 && gp->suppress[i] < ctx->V) mask[gp->suppress[i]] |= 1;
+    for (int i = 0; i < gp->n_begin_suppress; ++i)
+        if (gp->begin_suppress[i] >= 0 && gp->begin_suppress[i] < ctx->V) mask[gp->begin_suppress[i]] |= 2;
+    WM_HIP(hipMemcpyAsync(ctx->supmask, mask.data(), mask.size(), hipMemcpyHostToDevice, st));
+    const int L0 = lens[0];
+    WM_HIP(hipMemcpyAsync(ctx->L, &L0, sizeof(int), hipMemcpyHostToDevice, st));
+    int* buf = nullptr;
+    WM_HIP(hipMalloc(reinterpret_cast<void**>(&buf), ((size_t)R * Tmax + R) * sizeof(int)));
+    int rc = WM_OK;
+    std::vector<float> h2(16 * SEL_SP_HOST);
+    for (int r0 = 0; r0 < R && rc == WM_OK; r0 += 15) {
+        const int n = std::min(15, R - r0);
+        hipError_t e = hipMemcpyAsync(buf, prefixes + (size_t)r0 * Tmax, (size_t)n * Tmax * sizeof(int), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(buf + (size_t)n * Tmax, lens + r0, n * sizeof(int), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(ctx->cand + 1, probe_tokens + r0, n * sizeof(int), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpy2DAsync(ctx->logits, (size_t)ctx->Vpad * sizeof(float), logits + (size_t)r0 * ctx->V,
+                                                  (size_t)ctx->V * sizeof(float), (size_t)ctx->V * sizeof(float), n, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) { ctx->err = std::string("wm_select_rows: ") + hipGetErrorString(e); rc = WM_ERR_HIP; break; }
+        rc = wm_dec_select_rows(ctx, buf, buf + (size_t)n * Tmax, n, Tmax);
+        if (rc) break;
+        e = hipMemcpyAsync(out_argmax + r0, ctx->amax, n * sizeof(int), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(out_p_probe + r0, ctx->pc, n * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(out_ts_forced + r0, ctx->ts.forced, n * sizeof(int), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(h2.data(), ctx->part2, (size_t)n * SEL_SP_HOST * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) { ctx->err = std::string("wm_select_rows: ") + hipGetErrorString(e); rc = WM_ERR_HIP; break; }
+        for (int r = 0; r < n; ++r) {
+            float hs = 0.f;
+            for (int k = 0; k < SEL_SP_HOST; ++k) hs += h2[(size_t)r * SEL_SP_HOST + k];     // (k_accept's order)
+            out_entropy[r0 + r] = -hs;
+        }
+    }
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(buf);
+    return rc;
+}
+
+
 // Uses (and overwrites) the decode-loop state: call it before wm_decode_begin, or begin again afterwards.
 extern "C" int wm_forward_logits(wm_ctx* ctx, int B, const int32_t* tokens, int T, int pos0, int disable_medusa, float* logits_out)
 {

@@ -1,6 +1,7 @@
 // wm_internal.h — engine context shared by the three translation units of libwm.so.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 #include "../../include/wm.h"
@@ -39,6 +40,38 @@ struct GenDev {
     int sib;        // sibling rows of this decode's verify pass (wm_config.sibling_rows; 0 unless one stream, chain candidates, hidden-state carry)
 };
 
+// Whisper timestamp rules (wm_decode_begin_ts; HF WhisperTimeStampLogitsProcessor).  Passed by value as the trailing
+// argument of the *_ts select / candidate / accept kernels (the plain kernels keep their arguments and code).
+//   state  int4 per stream: {last sampled token is a timestamp, penultimate one is, last timestamp token or -1, sampled tokens} of ids[begin:L]
+//   record int4 per logits row: {lo, hi, flags, 0}: timestamps outside [lo, hi] masked; flags bit 0 masks [0, eos), bit 1 masks [0, tb)
+struct TsDev {
+    int on, tb, nots, mit;          // timestamp_begin, <|notimestamps|>, max_initial_timestamp_index (< 0: none)
+    int4* st;                       // [maxB] committed state (k_accept / k_accept_vanilla1 keep it current)
+    int4* ver;                      // [max(maxB, Rcap)][WM_CAND_STRIDE] records of the verify rows (k_cand_fin folds c_0..c_i)
+    float* part1t;                  // [Rcap][SEL_SP][4] timestamp-region slice partials {max, first argmax, sum exp at 1/T, sum exp at 1}
+    int* forced;                    // [Rcap] the row's log-softmax decision masked all text (k_select2 / k_select_argmax)
+    const int* L;                   // ctx->L (k_cand_fin: prefix length of verify row i is L + i + 1)
+};
+
+// state after one more sampled token / the record of a row whose sampled prefix has state `st` (host: wm_decode_begin_ts, device: the select kernels)
+__host__ __device__ __forceinline__ int4 ts_fold(int4 st, int tok, int tb)
+{
+    st.y = st.x;                                // penultimate <- last
+    st.x = tok >= tb ? 1 : 0;
+    if (tok >= tb) st.z = tok;
+    st.w += 1;
+    return st;
+}
+// record of a row whose sampled prefix (ids[begin:len]) has state `st`
+__host__ __device__ __forceinline__ int4 ts_record(int4 st, int len, int begin, int tb, int V, int mit)
+{
+    const bool last = st.w >= 1 && st.x, penult = st.w < 2 || st.y;
+    int lo = tb, hi = V - 1, fl = 0;
+    if (last) { if (penult) lo = V; else fl |= 1; }          // pairs: after ts,ts text only; after text,ts no text below EOS
+    if (st.z >= 0) lo = std::max(lo, (last && !penult) ? st.z : st.z + 1);     // never decreasing, <|0.00|> not again
+    if (len == begin) { fl |= 2; if (mit >= 0) hi = std::min(hi, tb + mit); }  // first sampled token: a timestamp <= max_initial
+    return make_int4(lo, hi, fl, 0);
+}
 // Static tables of the candidate tree (device memory; medusa_utils.py:305-421).  Nodes are numbered depth by depth.
 struct TreeDev {
     int n_nodes, n_paths, K, pad_;
@@ -147,6 +180,7 @@ struct wm_ctx {
     int* done = nullptr;                   // [0] = all streams finished, [1] = number of finished streams
     bool use_done = false;
     GenDev gp{};
+    TsDev ts{};                            // timestamp rules of the current decode (ts.on = 0: off); buffers allocated in wm_create
     int Bdec = 0;
     bool began = false, first_done = false;
     long long iters = 0;
@@ -179,3 +213,6 @@ int wm_dec_iter_rest(wm_ctx* ctx, int Mper_base);
 int wm_dec_step(wm_ctx* ctx, int);   // heads, candidates, verify pass, accept
 int wm_dec_profile(wm_ctx* ctx, int kernel, int rows, int reps, float* ms, double* bytes);
 int wm_dec_fold_init(wm_ctx* ctx);   // c = W gamma, b' = b + W beta of every LayerNorm-fed decoder GEMM (needs ctx->foldv)
+// timestamp parity tap (wm_select_rows): R <= 15 rows already in ctx->logits, probe tokens in cand[1 .. R], cur_len in L[0];
+// prefixes DEV [R][Tmax], lengths DEV [R]
+int wm_dec_select_rows(wm_ctx* ctx, const int* pre_dev, const int* len_dev, int R, int Tmax);

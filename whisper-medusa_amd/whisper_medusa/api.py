@@ -25,6 +25,7 @@ from .config import MedusaConfig, GenParams, ACCEPT_TYPICAL, ACCEPT_GREEDY
 from .engine import Engine
 from . import weights as _weights
 from . import synth as _synth
+from . import timestamps as _timestamps
 
 
 class EngineKVCache:
@@ -432,9 +433,10 @@ class WhisperMedusaModel:
     # ---- generate ---------------------------------------------------------------------------
     def _gen_params(self, language, task, exponential_decay_length_penalty, max_new_tokens, max_length,
                     temperature, vanilla, posterior_threshold, posterior_alpha, suppress_tokens,
-                    begin_suppress_tokens, prompt_ids) -> GenParams:
+                    begin_suppress_tokens, prompt_ids, timestamps: bool = False) -> GenParams:
         cfg = self.config
-        prompt = _synth.default_prompt(cfg, language or "en", task or "transcribe")        # G1, model.py:1519-1537
+        # G1, model.py:1519-1537; timestamps: without <|notimestamps|> (HF _retrieve_init_tokens with return_timestamps)
+        prompt = _synth.default_prompt(cfg, language or "en", task or "transcribe", timestamps=timestamps)
         begin_suppress_index = None
         if prompt_ids is not None:
             # short-form conditioning (HF _prepare_decoder_input_ids): decoder_input_ids = cat([prompt_ids, init_tokens]);
@@ -468,7 +470,9 @@ class WhisperMedusaModel:
                          posterior_threshold=cfg.posterior_threshold if posterior_threshold is None else posterior_threshold,
                          posterior_alpha=cfg.posterior_alpha if posterior_alpha is None else posterior_alpha,
                          accept_mode=mode, temperature=1.0 if mode == ACCEPT_TYPICAL else 0.0, vanilla=bool(vanilla),
-                         begin_suppress_index=begin_suppress_index)
+                         begin_suppress_index=begin_suppress_index, timestamps=bool(timestamps),
+                         no_timestamps_token_id=cfg.no_timestamps_token_id if timestamps else -1,
+                         max_initial_timestamp_index=cfg.max_initial_timestamp_index if timestamps else None)
 
     @torch.no_grad()
     def generate(self, input_features: Optional[torch.Tensor] = None, generation_config=None, logits_processor=None,
@@ -523,7 +527,17 @@ class WhisperMedusaModel:
         if kwargs.get("do_sample"):
             raise NotImplementedError("sampling (do_sample=True) is not supported with medusa")      # model.py:1128-1156: no Medusa branch
         if return_timestamps:
-            raise NotImplementedError("return_timestamps is not supported with medusa for now")   # model.py:1171-1175
+            # model.py:1171-1175 raises for every checkpoint; the engine runs HF's WhisperTimeStampLogitsProcessor in its decode loop
+            #  where the vocabulary carries Whisper's timestamp block
+            if not self.config.supports_timestamps:
+                raise NotImplementedError("return_timestamps is not supported with medusa for this checkpoint: its vocabulary has no "
+                                          "timestamp block (vocab_size - no_timestamps_token_id - 1 != max_source_positions + 1)")
+            if self.config.is_tree:
+                raise NotImplementedError("return_timestamps is not supported with a candidate tree (medusa_choices with top-k > 1)")
+            if logits_processor or stopping_criteria:
+                raise NotImplementedError("return_timestamps is not supported together with logits_processor= / stopping_criteria= "
+                                          "(the host processor path)")
+            return_timestamps = True
         if no_speech_threshold is not None:
             raise NotImplementedError("no_speech_detection is not supported with medusa for now")  # model.py:1201-1205
         if kwargs.get("num_beams", 1) not in (None, 1):
@@ -541,13 +555,16 @@ class WhisperMedusaModel:
                 raise NotImplementedError("Longform generation is not supported yet")              # model.py:1213-1214
             return self._generate_longform(input_features, dict(kwargs, language=language, task=task, temperature=temperature,
                                                                 prompt_ids=prompt_ids, logits_processor=logits_processor,
-                                                                stopping_criteria=stopping_criteria))
+                                                                stopping_criteria=stopping_criteria,
+                                                                return_timestamps=bool(return_timestamps),
+                                                                return_segments=return_segments, time_precision=time_precision))
         if language is None and self.config.is_multilingual and kwargs.get("detect_language", True) and input_features.shape[0] >= 1 \
                 and not kwargs.get("_language_resolved"):
             return self._generate_detecting_language(input_features, dict(kwargs, task=task, temperature=temperature, prompt_ids=prompt_ids,
                                                                           return_dict_in_generate=return_dict_in_generate,
                                                                           return_segments=return_segments, logits_processor=logits_processor,
-                                                                          stopping_criteria=stopping_criteria))
+                                                                          stopping_criteria=stopping_criteria,
+                                                                          return_timestamps=bool(return_timestamps), time_precision=time_precision))
         B = input_features.shape[0]
         if B > self._max_batch:
             self.set_max_batch(B)
@@ -556,7 +573,8 @@ class WhisperMedusaModel:
                               temperature if not isinstance(temperature, (tuple, list)) else temperature[0],
                               kwargs.get("vanilla", False), kwargs.get("posterior_threshold"),
                               kwargs.get("posterior_alpha"), kwargs.get("suppress_tokens"),
-                              kwargs.get("begin_suppress_tokens"), prompt_ids)
+                              kwargs.get("begin_suppress_tokens"), prompt_ids, timestamps=bool(return_timestamps))
+        gp._time_precision = float(time_precision)
         if logits_processor or stopping_criteria:
             gp = lower_processors(gp, logits_processor, stopping_criteria)
         self._last_prompt = list(gp.prompt)
@@ -729,15 +747,21 @@ class WhisperMedusaModel:
         """Default: the padded LongTensor.  ``return_dict_in_generate`` / ``return_segments``: the reference's dict form
         ``{"sequences": ..., ["segments": ...]}`` (model.py:1747-1779; one segment per clip, short-form only)."""
         return self._wrap_outputs(self._pad(seqs, gp), [len(gp.prompt)] * len(seqs), gp.pad_token_id, gp.eos_token_id,
-                                  return_dict_in_generate, return_segments)
+                                  return_dict_in_generate, return_segments, timestamps=gp.timestamps,
+                                  time_precision=getattr(gp, "_time_precision", 0.02))
 
-    def _wrap_outputs(self, t, prompt_lens, pad, eos, return_dict_in_generate, return_segments):
+    def _wrap_outputs(self, t, prompt_lens, pad, eos, return_dict_in_generate, return_segments, timestamps=False, time_precision=0.02):
         """``return_dict_in_generate``: a GenerateEncoderDecoderOutput (model.py:812-823, :1715-1742); ``return_segments`` alone:
         the dict {"sequences", "segments"} of model.py:1764-1779 (one segment per clip, short-form only)."""
         if not return_dict_in_generate and not return_segments:
             return t
         segs = None
-        if return_segments and not return_dict_in_generate:
+        if return_segments and not return_dict_in_generate and timestamps:
+            # real segments: HF's _retrieve_segment over each row's generated ids (whisper_medusa/timestamps.py)
+            rows = t.cpu()
+            segs = [_timestamps.row_segments(rows[i].tolist(), P, eos, self.config.timestamp_begin, self.config.n_mel_frames,
+                                             time_precision, result=t[i]) for i, P in enumerate(prompt_lens)]
+        elif return_segments and not return_dict_in_generate:
             segs = [[{"start": torch.tensor(0.0), "end": torch.tensor(30.0 * self.config.max_source_positions / 1500.0),
                       "tokens": t[i, P:][t[i, P:] != pad] if pad != eos else t[i, P:],
                       "result": t[i]}] for i, P in enumerate(prompt_lens)]
@@ -786,6 +810,7 @@ class WhisperMedusaModel:
     def _generate_detecting_language(self, input_features, kw):
         langs = self.detect_language(input_features)
         rdg, rseg = kw.pop("return_dict_in_generate", None), kw.pop("return_segments", False)
+        rts, tprec = bool(kw.get("return_timestamps")), kw.get("time_precision", 0.02)
         groups: Dict[str, List[int]] = {}
         for i, l in enumerate(langs):
             groups.setdefault(l, []).append(i)
@@ -803,15 +828,20 @@ class WhisperMedusaModel:
         for i, r in enumerate(rows):
             t[i, : r.numel()] = r
         self.detected_languages = langs
-        return self._wrap_outputs(t, plens, self.config.pad_token_id, self.config.eos_token_id, rdg, rseg)
+        return self._wrap_outputs(t, plens, self.config.pad_token_id, self.config.eos_token_id, rdg, rseg, timestamps=rts,
+                                  time_precision=tprec)
 
     def _generate_longform(self, input_features, kw):
         """`chunk_longform=True`: clips longer than 30 s (the reference raises, model.py:1213-1214) are cut into 30 s windows,
         the windows of all clips are decoded as ONE batch of independent streams (that is what the engine's batch is), and
         each clip's windows are concatenated: prompt once, then the generated ids of every window without its EOS / padding.
-        No timestamps, no conditioning on the previous window (both unsupported with Medusa in the reference as well)."""
+        No conditioning on the previous window (unsupported with Medusa in the reference as well).  `return_timestamps=True`: every
+        window keeps its timestamp tokens (relative to the window); `return_segments=True` then gives each window's segments offset by
+        the window's start, j * n_mel_frames * 10 ms (the windows stay fixed: HF's sequential seek to the last timestamp is not done)."""
         cfg = self.config
         kw.pop("chunk_longform", None)
+        rseg, tprec = kw.pop("return_segments", False), kw.get("time_precision", 0.02)
+        rts = bool(kw.get("return_timestamps"))
         F = cfg.n_mel_frames
         B, _, T = input_features.shape
         n = -(-T // F)
@@ -842,7 +872,12 @@ class WhisperMedusaModel:
                 prompts[b] = list(self._last_prompt)
         eos, pad = cfg.eos_token_id, cfg.pad_token_id
         seqs = []
+        segs = [[] for _ in range(B)]
         for b in range(B):
+            if rts and rseg:
+                for j in range(n):
+                    segs[b] += _timestamps.row_segments(rows[b * n + j].tolist(), len(prompts[b]), eos, cfg.timestamp_begin, F, tprec,
+                                                        time_offset=j * F * 0.01, result=rows[b * n + j])
             ids = list(prompts[b])
             P = len(ids)
             for j in range(n):
@@ -856,6 +891,8 @@ class WhisperMedusaModel:
         t = torch.full((B, Tm), pad, dtype=torch.long, device=self.device)
         for i, s_ in enumerate(seqs):
             t[i, : len(s_)] = torch.tensor(s_, dtype=torch.long)
+        if rts and rseg:
+            return {"sequences": t, "segments": segs}
         return t
 
     @torch.no_grad()

@@ -152,6 +152,7 @@ class MedusaConfig:
     suppress_tokens: Optional[List[int]] = None
     begin_suppress_tokens: Optional[List[int]] = field(default_factory=lambda: [220, 50257])
     max_length: int = 448
+    max_initial_timestamp_index: Optional[int] = None     # WhisperTimeStampLogitsProcessor: None = no limit on the first timestamp
     posterior_threshold: float = 0.09   # medusa_utils.py:17
     posterior_alpha: float = 0.3        # medusa_utils.py:18
 
@@ -187,6 +188,19 @@ class MedusaConfig:
     @property
     def is_tree(self) -> bool:
         return [int(x) for x in self.medusa_choices] != [1] * (self.medusa_num_heads + 1)
+
+    @property
+    def timestamp_begin(self) -> int:
+        """First timestamp token <|0.00|> (HF WhisperTimeStampLogitsProcessor: no_timestamps_token_id + 1)."""
+        return self.no_timestamps_token_id + 1
+
+    @property
+    def supports_timestamps(self) -> bool:
+        """The vocabulary ends in one timestamp token per 20 ms encoder frame plus the end (large-v2: 51865 - 50364 = 1501, tiny.en:
+        51864 - 50363 = 1501), with EOS and the start token below it: what `return_timestamps=True` needs."""
+        tb = self.timestamp_begin
+        return (self.vocab_size - tb == self.max_source_positions + 1 and 0 <= self.eos_token_id < tb
+                and 0 <= self.decoder_start_token_id < tb)
 
     @property
     def is_block(self) -> bool:
@@ -225,7 +239,7 @@ class MedusaConfig:
                 g = json.load(f)
             for k in ("eos_token_id", "pad_token_id", "decoder_start_token_id", "is_multilingual",
                       "lang_to_id", "task_to_id", "no_timestamps_token_id", "suppress_tokens",
-                      "begin_suppress_tokens", "max_length", "posterior_threshold", "posterior_alpha"):
+                      "begin_suppress_tokens", "max_length", "max_initial_timestamp_index", "posterior_threshold", "posterior_alpha"):
                 if k in g and g[k] is not None:
                     d[k] = g[k]
         if "medusa_choices" not in d and "medusa_num_heads" in d:
@@ -294,6 +308,10 @@ class GenParams:
     # ^ sequence length at which SuppressTokensAtBeginLogitsProcessor fires.  None = len(prompt) (no prompt_ids: the prompt IS the
     #   init tokens).  With `prompt_ids` the reference passes begin_index = init_tokens.shape[1] (model.py:1537, 1551, 1640-1644),
     #   i.e. the number of init tokens WITHOUT the prepended previous-text ids, so the begin suppression never fires there.
+
+    timestamps: bool = False         # WhisperTimeStampLogitsProcessor in the decode loop (wm_decode_begin_ts); prompt without <|notimestamps|>
+    no_timestamps_token_id: int = -1               # (timestamps: timestamp_begin = no_timestamps_token_id + 1)
+    max_initial_timestamp_index: Optional[int] = None
 
     @property
     def begin_index(self) -> int:

@@ -44,6 +44,11 @@ class WmGenParams(C.Structure):
                 ("force_accept", C.c_int32)]
 
 
+class WmTimestampParams(C.Structure):
+    _fields_ = [("timestamp_begin", C.c_int32), ("no_timestamps_token_id", C.c_int32), ("max_initial_timestamp_index", C.c_int32),
+                ("begin_index", C.c_int32)]
+
+
 class WmStats(C.Structure):
     _fields_ = [("iterations", C.c_int64), ("iterations_launched", C.c_int64), ("tokens_emitted", C.c_int64),
                 ("accept_hist", C.c_int64 * 16),
@@ -53,7 +58,8 @@ class WmStats(C.Structure):
 
 EXPORTS = ["wm_create", "wm_destroy", "wm_last_error", "wm_abi_version", "wm_build_act_fp16", "wm_resample_len", "wm_resample", "wm_logmel", "wm_encode", "wm_set_encoder_output",
            "wm_decode_begin", "wm_decode_run", "wm_get_tokens", "wm_get_stats", "wm_sync",
-           "wm_get_encoder_output", "wm_forward_logits", "wm_get_cross_kv", "wm_profile_kernel"]
+           "wm_get_encoder_output", "wm_forward_logits", "wm_get_cross_kv", "wm_profile_kernel",
+           "wm_decode_begin_ts", "wm_select_rows"]
 
 _lib = {}
 
@@ -94,6 +100,9 @@ def load_library(path: Optional[str] = None, act_fp16: bool = False) -> C.CDLL:
     lib.wm_encode.argtypes = [vp, vp, i32]
     lib.wm_set_encoder_output.argtypes = [vp, vp, i32]
     lib.wm_decode_begin.argtypes = [vp, C.POINTER(WmGenParams), i32]
+    lib.wm_decode_begin_ts.argtypes = [vp, C.POINTER(WmGenParams), C.POINTER(WmTimestampParams), i32]
+    lib.wm_select_rows.argtypes = [vp, C.POINTER(WmGenParams), C.POINTER(WmTimestampParams), i32, f32p, i32p, i32, i32p, i32p,
+                                   i32p, f32p, f32p, i32p]
     lib.wm_decode_run.argtypes = [vp, i32, i32p]
     lib.wm_get_tokens.argtypes = [vp, i32, i32p, i32, i32p]
     lib.wm_get_stats.argtypes = [vp, C.POINTER(WmStats)]
@@ -231,7 +240,8 @@ class Engine:
         self._enc_stamp = object()
 
     # ---- F3..F14 ------------------------------------------------------------------------------
-    def decode(self, gp: GenParams, B: int, max_iters: int = 1 << 30, on_iteration=None) -> List[List[int]]:
+    @staticmethod
+    def _gen_struct(gp: GenParams):
         prompt, sup, bsup = _i32arr(gp.prompt), _i32arr(gp.suppress_tokens), _i32arr(gp.begin_suppress_tokens)
         g = WmGenParams(prompt, len(gp.prompt), gp.eos_token_id, gp.pad_token_id, sup, len(gp.suppress_tokens),
                         bsup, len(gp.begin_suppress_tokens), gp.max_length, gp.hard_max_length,
@@ -239,8 +249,22 @@ class Engine:
                         float(gp.exp_decay[1]) if gp.exp_decay is not None else 1.0,
                         gp.posterior_threshold, gp.posterior_alpha, gp.temperature if gp.temperature else 0.0,
                         gp.accept_mode, 1 if gp.vanilla else 0, int(gp.begin_index), int(getattr(gp, "force_accept", -1)))
+        return g, (prompt, sup, bsup)          # (the arrays the struct points into: keep them alive with it)
+
+    @staticmethod
+    def _ts_struct(gp: GenParams) -> WmTimestampParams:
+        mit = gp.max_initial_timestamp_index
+        return WmTimestampParams(int(gp.no_timestamps_token_id) + 1, int(gp.no_timestamps_token_id), -1 if mit is None else int(mit),
+                                 int(gp.begin_index))
+
+    def decode(self, gp: GenParams, B: int, max_iters: int = 1 << 30, on_iteration=None) -> List[List[int]]:
+        g, _keep = self._gen_struct(gp)
         self._kv_stamp = object()             # the decode loop rewrites the self-attention cache: forward()'s cache handles go stale
-        self._check(self.lib.wm_decode_begin(self.h, C.byref(g), B), "wm_decode_begin")
+        if gp.timestamps:                     # WhisperTimeStampLogitsProcessor in the loop (include/wm.h wm_decode_begin_ts)
+            ts = self._ts_struct(gp)
+            self._check(self.lib.wm_decode_begin_ts(self.h, C.byref(g), C.byref(ts), B), "wm_decode_begin_ts")
+        else:
+            self._check(self.lib.wm_decode_begin(self.h, C.byref(g), B), "wm_decode_begin")
         left = C.c_int32(0)
         if on_iteration is None:
             self._check(self.lib.wm_decode_run(self.h, max_iters, C.byref(left)), "wm_decode_run")
@@ -257,6 +281,29 @@ class Engine:
             if left.value == 0 or stop is True:                   # the callback may end the run (host-side stopping criteria)
                 break
         return [self.tokens(b) for b in range(B)]
+
+    def select_rows(self, gp: GenParams, logits: np.ndarray, prefixes: Sequence[Sequence[int]], probe_tokens: Sequence[int]) -> dict:
+        """Timestamp parity tap (wm_select_rows): rows ``logits [R, V]`` as verify rows with the given prefixes, through the decode loop's
+        state fold and select kernels.  Returns numpy arrays argmax, p_probe, entropy, ts_forced (the log-softmax decision masked all text)."""
+        x = np.ascontiguousarray(logits, dtype=np.float32)
+        R, V = x.shape
+        if V != self.cfg.vocab_size or len(prefixes) != R or len(probe_tokens) != R:
+            raise ValueError("select_rows: logits must be [R, vocab] with one prefix and one probe token per row")
+        Tmax = max(len(p) for p in prefixes)
+        pre = np.zeros((R, Tmax), dtype=np.int32)
+        for r, p in enumerate(prefixes):
+            pre[r, : len(p)] = p
+        lens = np.array([len(p) for p in prefixes], dtype=np.int32)
+        probe = np.ascontiguousarray(probe_tokens, dtype=np.int32)
+        am = np.zeros(R, np.int32); pp = np.zeros(R, np.float32); H = np.zeros(R, np.float32); fo = np.zeros(R, np.int32)
+        g, _keep = self._gen_struct(gp)
+        ts = self._ts_struct(gp)
+        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        self._kv_stamp = object()
+        self._check(self.lib.wm_select_rows(self.h, C.byref(g), C.byref(ts), R, x.ctypes.data_as(f32p), pre.ctypes.data_as(i32p), Tmax,
+                                            lens.ctypes.data_as(i32p), probe.ctypes.data_as(i32p), am.ctypes.data_as(i32p),
+                                            pp.ctypes.data_as(f32p), H.ctypes.data_as(f32p), fo.ctypes.data_as(i32p)), "wm_select_rows")
+        return dict(argmax=am, p_probe=pp, entropy=H, ts_forced=fo)
 
     def tokens(self, stream: int) -> List[int]:
         cap = self.cfg.max_target_positions + 16

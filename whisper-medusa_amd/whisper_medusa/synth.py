@@ -126,16 +126,17 @@ def synth_state_dict(cfg: MedusaConfig, seed: int = 0, device: str = "cpu",
     return sd
 
 
-def default_prompt(cfg: MedusaConfig, language: Optional[str] = "en", task: str = "transcribe") -> List[int]:
-    """Decoder prompt ids (G1; reference model.py:1519-1537 via HF ``_retrieve_init_tokens``)."""
+def default_prompt(cfg: MedusaConfig, language: Optional[str] = "en", task: str = "transcribe", timestamps: bool = False) -> List[int]:
+    """Decoder prompt ids (G1; reference model.py:1519-1537 via HF ``_retrieve_init_tokens``).  ``timestamps=True``: without
+    <|notimestamps|> (HF drops it when return_timestamps is set)."""
+    tail = [] if timestamps else [cfg.no_timestamps_token_id]
     if cfg.is_multilingual:
         from .config import language_token
         key = language_token(language or "en")
         if key not in cfg.lang_to_id:
             raise ValueError(f"Unsupported language: {language}")
-        return [cfg.decoder_start_token_id, cfg.lang_to_id[key], cfg.task_to_id[task],
-                cfg.no_timestamps_token_id]
-    return [cfg.decoder_start_token_id, cfg.no_timestamps_token_id]
+        return [cfg.decoder_start_token_id, cfg.lang_to_id[key], cfg.task_to_id[task]] + tail
+    return [cfg.decoder_start_token_id] + tail
 
 
 def bench_gen_params(cfg: MedusaConfig, max_new_tokens: int = 128, accept_mode: int = ACCEPT_TYPICAL,
