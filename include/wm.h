@@ -208,6 +208,29 @@ int wm_get_tokens(wm_ctx* ctx, int stream, int32_t* out /* HOST */, int cap, int
 int wm_get_stats(wm_ctx* ctx, wm_stats* out /* HOST */);
 int wm_sync(wm_ctx* ctx);
 
+/* ---- token-level timestamps (additive to ABI v9; csrc/wm_align.hip) ----
+ * Stands in for HF WhisperGenerationMixin._extract_token_timestamps (transformers generation_whisper.py; `return_token_timestamps=True`,
+ * which the reference refuses): HF reads the cross-attentions its autoregressive decode collected; a Medusa loop has none, so the engine
+ * replays the FINAL ids teacher-forced (a causal decoder gives every position the same query either way) and taps the alignment heads. */
+typedef struct wm_align_params {
+    const int32_t* heads;        /* HOST [n_heads][2] = (decoder layer, head): generation_config.alignment_heads.  Layers index Whisper's
+                                  * decoder layers (the Medusa-Block extra layer is never one) */
+    int32_t n_heads;             /* 1 .. 64 */
+    int32_t median_filter_width; /* odd, 1 .. 15; config.median_filter_width (7): HF _median_filter */
+    float time_precision;        /* 0.02; read as the decimal it was written from, so that frame * time_precision is HF's double product */
+} wm_align_params;
+/* Per stream b: ids tokens[b][0 .. lens[b]) (the stream's own end: EOS included, padding excluded), the first n_prompt[b] of them decoder
+ * input.  The N = lens - n_prompt - 1 rows of input positions n_prompt .. lens - 2 are aligned to F = n_ctx frames (num_frames[b] / 2 when
+ * given): softmax over all n_ctx frames, crop, z-score over the rows, median filter, mean over the heads, DTW (HF _dynamic_time_warping);
+ * out[b][t] = 0 for t < n_prompt, the time of the first frame of row t - n_prompt after it, the last value again for the last token and
+ * for t >= lens[b].  N <= 1: zeros (nothing is launched for that stream).  Needs wm_encode (else WM_ERR_STATE); WM_ERR_ARG for a layer /
+ * head out of range, an even width, lens[b] > n_tgt, n_prompt[b] > lens[b].  The scores read the bf16 cross-K, also on a cross_kv_fp8
+ * context (whose bf16 projection stays resident).  Overwrites the decode state like wm_forward_logits (begin again afterwards).  The
+ * probabilities live in a workspace allocated on first use and capped (512 MB; WM_ALIGN_WS_MB): the streams are worked in groups that fit. */
+int wm_token_timestamps(wm_ctx* ctx, const wm_align_params* ap, int B, const int32_t* tokens /* HOST [B][Tmax] */, int Tmax,
+                        const int32_t* lens /* HOST [B] */, const int32_t* n_prompt /* HOST [B] */, const int32_t* num_frames /* HOST [B] or NULL */,
+                        float* out /* HOST [B][Tmax] seconds */, float* ms /* hipEvent time of replay + alignment, may be NULL */);
+
 /* ---- parity taps (test-only views of intermediate state; no reference equivalent except
  * forward(), model.py:1223-1347) ---- */
 /* encoder output [B][n_ctx][d_model] as float32 to HOST */
@@ -228,6 +251,15 @@ int wm_forward_logits(wm_ctx* ctx, int B, const int32_t* tokens /* HOST [B][T] *
 int wm_select_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* ts, int R, const float* logits, const int32_t* prefixes,
                    int Tmax, const int32_t* lens, const int32_t* probe_tokens, int32_t* out_argmax, float* out_p_probe, float* out_entropy,
                    int32_t* out_ts_forced);
+/* Alignment parity taps: views of the last wm_token_timestamps call.  WM_ERR_STATE for a stream whose workspace group is no longer
+ * resident (only the last group is) or that had fewer than 2 rows.  Probabilities of alignment head a (the softmax of HF WhisperAttention's
+ * cross branch, modeling_whisper.py, before any crop): HOST float32 [N][n_ctx]. */
+int wm_get_align_probs(wm_ctx* ctx, int stream, int a, float* out);
+/* The matrix handed to the DTW (HF _extract_token_timestamps: normalised, median-filtered, averaged over the heads): HOST float32 [N][F]. */
+int wm_get_align_matrix(wm_ctx* ctx, int stream, float* out);
+/* HF _dynamic_time_warping on the NEGATION of `matrix` (HOST float32 [N][F]) by the engine's kernel: first_frame HOST [N] (time index of the
+ * first path element of every text row), the path in forward order (text_indices, time_indices; HOST, N + F entries of room) and its length. */
+int wm_dtw(wm_ctx* ctx, const float* matrix, int N, int F, int32_t* first_frame, int32_t* path_text, int32_t* path_time, int* path_len);
 /* cross K/V of one kv-layer/stream/head: HOST float32 [n_ctx][64] each */
 int wm_get_cross_kv(wm_ctx* ctx, int kv_layer, int stream, int head, float* k_out, float* v_out);
 /* Times `reps` launches of one decode-path kernel class in its current shape with hipEvents on

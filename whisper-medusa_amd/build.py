@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.environ.get("WM_CSRC", os.path.join(HERE, "csrc"))      # WM_CSRC: a patched copy of csrc/ (A/B variants of tests/microbench)
 OUT_DIR = os.path.join(HERE, "whisper_medusa")
 LIB = os.path.join(OUT_DIR, "libwm.so")
-SOURCES = ["wm_engine.hip", "wm_decoder.hip", "wm_encoder.hip"]
+SOURCES = ["wm_engine.hip", "wm_decoder.hip", "wm_encoder.hip", "wm_align.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # gfx950 can hand the first kernel arguments to a wave in SGPRs at launch (kernarg preload): the decode chain's kernels then
@@ -67,7 +67,7 @@ def build(force=False, verbose=True):
 
 
 def build_variant(lib, extra=(), suffix="", verbose=True):
-    """Compile the three sources (objects get `suffix`) and link them as `lib`.  The product build is build_variant(LIB);
+    """Compile the sources (objects get `suffix`) and link them as `lib`.  The product build is build_variant(LIB);
     A/B arms of tests/microbench call it with another path (`--variant NAME [-DFLAG ...]` -> libwm_NAME.so, loaded through WM_LIB)."""
     with cf.ThreadPoolExecutor(len(SOURCES)) as ex:
         objs = list(ex.map(lambda s: _compile(s, extra, suffix), SOURCES))

@@ -1493,7 +1493,7 @@ static int dec_layer(wm_ctx* ctx, const DecLayerW& w, int slot, float* h, int b0
     const bool fuse_shape = (cqp.nk == 8 && cqp.ksplit >= 1 && cqp.ksplit <= 5) || (cqp.nk == 4 && (cqp.ksplit == 1 || cqp.ksplit == 3));
     // (not under the merged-step schedule's dense rows: the fused instance reads q at stream * Mper + row)
     // (hi / lo builds only: the fused kernel multiplies bf16 weights by the hi / lo pair itself)
-    const bool fuse_cq = WM_ACT_PLANES == 2 && fuse_env && !x8 && !fold && R <= 16 && !f8 && fuse_shape && H * 4 == d / 16 && rowinfo == nullptr;       // single tile: nqt == 1
+    const bool fuse_cq = WM_ACT_PLANES == 2 && fuse_env && !x8 && !fold && R <= 16 && !f8 && fuse_shape && H * 4 == d / 16 && rowinfo == nullptr && !ctx->replay;       // single tile: nqt == 1
     const PfJob kvjob = (pf && nqt == 1 && ctx->NS % xgrid == 0 && ctx->Spad == ctx->NS * 256)
         ? PfJob{reinterpret_cast<const char*>(kx), reinterpret_cast<const char*>(vx), (unsigned)(ctx->NS / xgrid) * 256 * xkb,
                 (unsigned)(xgrid * H * nb), (unsigned long long)H * nb * ctx->Spad * xkb}
@@ -1690,6 +1690,31 @@ int wm_dec_stage_layers(wm_ctx* ctx, int b0, int nb, int Mper, int mode)
         if (rc) return rc;
     }
     return WM_OK;
+}
+
+// Teacher-forced replay (token timestamps, wm_align.hip): the embed + layer launches of a base pass (mode 0 above) for the first n_layers
+// layers, with a hook behind every layer.  No carry, no early exit on the decode's done flag: the caller has cleared both.
+int wm_dec_replay_layers(wm_ctx* ctx, int b0, int nb, int Mper, int n_layers, int (*after)(wm_ctx*, int, void*), void* arg)
+{
+    hipStream_t st = ctx->stream;
+    g_skinny_done = nullptr;
+    const int d = ctx->d, R = nb * Mper;
+    const int* base = ctx->kvlen + b0;
+    if (R > ctx->Rcap || Mper > 16 || Mper < 1 || n_layers > ctx->cfg.dec_layers) { ctx->err = "replay pass exceeds the row capacity of the context"; return WM_ERR_ARG; }
+    const float* eg = ctx->ln_fold ? ctx->dec[0].ln1_w : nullptr;
+    hipLaunchKernelGGL(k_embed, dim3(R), dim3(256), 0, st, ctx->h, ctx->tok_emb, ctx->dec_pos, base,
+                       ctx->ids + (size_t)b0 * ctx->gp.Tids, ctx->gp.Tids, 1, Mper, d, ctx->V, ctx->Tmax, (const int*)nullptr,
+                       (const int4*)nullptr, (const int*)nullptr, 0, eg, ctx->xn, (size_t)ctx->Rcap * d, ctx->lnstats, ctx->Rcap);
+    WM_HIP(hipGetLastError());
+    ctx->cur_anc = nullptr;
+    ctx->replay = true;
+    int rc = WM_OK;
+    for (int l = 0; l < n_layers && rc == WM_OK; ++l) {
+        rc = dec_layer(ctx, ctx->dec[l], l, ctx->h, b0, nb, Mper, base, false, nullptr, l + 1 < ctx->cfg.dec_layers ? &ctx->dec[l + 1] : nullptr);
+        if (rc == WM_OK && after) rc = after(ctx, l, arg);
+    }
+    ctx->replay = false;
+    return rc;
 }
 
 // ---- stage 2: final LayerNorm for all rows (-> hf); Medusa-Block: the extra decoder layer on the

@@ -39,6 +39,7 @@ extern "C" void wm_destroy(wm_ctx* ctx)
                     ctx->xn, ctx->lnstats, ctx->foldv, ctx->kx8, ctx->vx8, ctx->kxs, ctx->vxs,
                     ctx->ts.st, ctx->ts.ver, ctx->ts.part1t, ctx->ts.forced};
     for (void* b : bufs) if (b) hipFree(b);
+    wm_align_free(ctx);
     if (ctx->ev0) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) hipEventDestroy(ctx->ev1);
     if (ctx->own_stream && ctx->stream) hipStreamDestroy(ctx->stream);

@@ -192,6 +192,10 @@ struct wm_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool prefetch = true;           // in-launch next-operand prefetch blocks (WM_PREFETCH=0 turns them off)
     float ms_logmel = 0.f, ms_encode = 0.f, ms_decode = 0.f;
+
+    // ---- token timestamps (wm_align.hip): workspace of the last wm_token_timestamps call, allocated on first use ----
+    struct wm_align_state* align = nullptr;
+    bool replay = false;            // a teacher-forced replay pass is being enqueued: the cross-q launch must leave its fp32 rows in qbuf (no WM_FUSE_CQ)
 };
 
 // implemented in wm_encoder.hip
@@ -213,6 +217,12 @@ int wm_dec_iter_rest(wm_ctx* ctx, int Mper_base);
 int wm_dec_step(wm_ctx* ctx, int);   // heads, candidates, verify pass, accept
 int wm_dec_profile(wm_ctx* ctx, int kernel, int rows, int reps, float* ms, double* bytes);
 int wm_dec_fold_init(wm_ctx* ctx);   // c = W gamma, b' = b + W beta of every LayerNorm-fed decoder GEMM (needs ctx->foldv)
+// Teacher-forced replay pass of the token-timestamp path (wm_align.hip): embed + decoder layers [0, n_layers) over Mper (<= 16) tokens of
+// streams [b0, b0 + nb) at positions kvlen[s].. (tokens ids[s][kvlen[s] ..]), exactly the launches of a base pass; after(ctx, l, arg) runs
+// behind layer l, while ctx->qbuf still holds that layer's cross-attention query rows (fp32 [nb * Mper][d], scaled by 0.125).
+int wm_dec_replay_layers(wm_ctx* ctx, int b0, int nb, int Mper, int n_layers, int (*after)(wm_ctx*, int, void*), void* arg);
+// implemented in wm_align.hip
+void wm_align_free(wm_ctx* ctx);
 // timestamp parity tap (wm_select_rows): R <= 15 rows already in ctx->logits, probe tokens in cand[1 .. R], cur_len in L[0];
 // prefixes DEV [R][Tmax], lengths DEV [R]
 int wm_dec_select_rows(wm_ctx* ctx, const int* pre_dev, const int* len_dev, int R, int Tmax);

@@ -544,8 +544,16 @@ class WhisperMedusaModel:
             raise Exception("Beam search is not supported with medusa for now")                     # model.py:1153-1156
         if prefix_allowed_tokens_fn:
             raise NotImplementedError("prefix_allowed_tokens_fn is not supported by the HIP engine")
+        tt_req = None
         if return_token_timestamps:
-            raise NotImplementedError("token timestamps are not supported with medusa")
+            # HF WhisperGenerationMixin.generate -> _extract_token_timestamps (the reference raises); the engine replays the final ids and
+            # aligns them on the GPU
+            tt_req = self._token_ts_request(kwargs.get("alignment_heads"), generation_config, kwargs.get("num_frames"), logits_processor,
+                                            time_precision)
+        tt_side = kwargs.pop("_tt_req", None)       # called by the language / long-form wrappers: plain tensor back, timestamps in self._last_tt
+        if tt_side is not None:
+            tt_req = tt_side
+        tt_side = tt_side is not None
         if input_features is None:
             raise ValueError("input_features is required")
         if input_features.dim() != 3:
@@ -556,14 +564,14 @@ class WhisperMedusaModel:
             return self._generate_longform(input_features, dict(kwargs, language=language, task=task, temperature=temperature,
                                                                 prompt_ids=prompt_ids, logits_processor=logits_processor,
                                                                 stopping_criteria=stopping_criteria,
-                                                                return_timestamps=bool(return_timestamps),
+                                                                return_timestamps=bool(return_timestamps), _tt_req=tt_req,
                                                                 return_segments=return_segments, time_precision=time_precision))
         if language is None and self.config.is_multilingual and kwargs.get("detect_language", True) and input_features.shape[0] >= 1 \
                 and not kwargs.get("_language_resolved"):
             return self._generate_detecting_language(input_features, dict(kwargs, task=task, temperature=temperature, prompt_ids=prompt_ids,
                                                                           return_dict_in_generate=return_dict_in_generate,
                                                                           return_segments=return_segments, logits_processor=logits_processor,
-                                                                          stopping_criteria=stopping_criteria,
+                                                                          stopping_criteria=stopping_criteria, _tt_req=tt_req, _tt_outer=tt_side,
                                                                           return_timestamps=bool(return_timestamps), time_precision=time_precision))
         B = input_features.shape[0]
         if B > self._max_batch:
@@ -587,15 +595,21 @@ class WhisperMedusaModel:
             n_ctx = 1
         if n_ctx > 1 and B >= 2:
             pool = self._get_pool(n_ctx)
-            seqs = pool.run(feats, gp)                                      # F1..F14 per micro-batch, concurrently
+            tsf = None
+            if tt_req is not None:
+                tsf = lambda e, sq, lo: self._token_ts_run(e, sq, gp, tt_req, lo)       # noqa: E731
+            seqs = pool.run(feats, gp, **({"token_ts": tsf} if tsf is not None else {}))      # F1..F14 per micro-batch, concurrently
             self.last_stats = pool.last_stats
-            return self._outputs(seqs, gp, return_dict_in_generate, return_segments)
+            tt = self._token_ts_tensor(pool.last_token_timestamps, seqs, gp) if tt_req is not None else None
+            return self._outputs(seqs, gp, return_dict_in_generate, return_segments, tt, tt_side)
         eng = self.engine
         streamer = kwargs.get("streamer")
         host_crit = getattr(gp, "_host_criteria", None)
         if streamer is not None and B != 1:
             raise ValueError("streamer only supports batch size 1")        # HF streamers are batch-1
         if getattr(gp, "_host_processors", None):
+            if tt_req is not None:
+                raise NotImplementedError("return_token_timestamps is not supported on the host processor path (logits_processor=)")
             seqs = self._decode_host_processors(feats, gp, streamer, host_crit)
             return self._outputs(seqs, gp, return_dict_in_generate, return_segments)
         # language detection just encoded exactly these clips on this engine (one language group, same order): its encoder output and
@@ -640,7 +654,55 @@ class WhisperMedusaModel:
         else:
             seqs = eng.decode(gp, B)                                        # F3..F14
         self.last_stats = eng.stats()
-        return self._outputs(seqs, gp, return_dict_in_generate, return_segments)
+        tt = None
+        if tt_req is not None:
+            rows, ms = self._token_ts_run(eng, seqs, gp, tt_req, 0)
+            self.last_stats["ms_token_timestamps"] = ms
+            tt = self._token_ts_tensor(rows, seqs, gp)
+        return self._outputs(seqs, gp, return_dict_in_generate, return_segments, tt, tt_side)
+
+    # ---- token-level timestamps (HF _extract_token_timestamps; engine: csrc/wm_align.hip) ----------------------------------------------
+    def _token_ts_request(self, alignment_heads, generation_config, num_frames, logits_processor, time_precision) -> dict:
+        heads = alignment_heads
+        if heads is None and generation_config is not None:
+            heads = getattr(generation_config, "alignment_heads", None)
+        if heads is None:
+            heads = self.config.alignment_heads
+        if heads is None:
+            # HF raises ValueError here; the class is the one this path has always raised for token timestamps
+            raise NotImplementedError("token timestamps need alignment heads and this checkpoint has no `alignment_heads` in its generation "
+                                      "config: pass generate(alignment_heads=[[layer, head], ..])")
+        heads = self.config.check_alignment_heads(heads)
+        if logits_processor:
+            raise NotImplementedError("return_token_timestamps is not supported together with logits_processor= (the host processor path)")
+        if num_frames is not None and not isinstance(num_frames, int):
+            num_frames = [int(v) for v in (num_frames.tolist() if hasattr(num_frames, "tolist") else num_frames)]
+        return dict(heads=heads, width=int(self.config.median_filter_width), num_frames=num_frames, time_precision=float(time_precision))
+
+    @staticmethod
+    def _own_end(s: List[int], gp: GenParams) -> List[int]:
+        """The stream's ids up to and including its first generated EOS (what _pad keeps)."""
+        P = len(gp.prompt)
+        return s[: s.index(gp.eos_token_id, P) + 1] if gp.eos_token_id in s[P:] else s
+
+    def _token_ts_run(self, eng, seqs, gp: GenParams, req: dict, lo: int):
+        """Token timestamps of the streams ``seqs`` an engine context has just decoded (streams lo .. of the batch) -> (rows, ms)."""
+        own = [self._own_end(s, gp) for s in seqs]
+        nf = req["num_frames"]
+        if isinstance(nf, list):
+            nf = nf[lo: lo + len(own)]
+        out, ms = eng.token_timestamps(own, len(gp.prompt), req["heads"], req["width"], req["time_precision"], nf)
+        return [out[b, : len(s)].copy() for b, s in enumerate(own)], ms
+
+    def _token_ts_tensor(self, rows, seqs, gp: GenParams) -> torch.Tensor:
+        """float32 [B, T] next to _pad's ids: positions after a stream's end repeat its last value."""
+        T = max(len(self._own_end(s, gp)) for s in seqs)
+        t = torch.zeros(len(rows), T, dtype=torch.float32)
+        for i, r in enumerate(rows):
+            t[i, : len(r)] = torch.from_numpy(np.asarray(r, dtype=np.float32))
+            if len(r):
+                t[i, len(r):] = float(r[-1])
+        return t.to(self.device)
 
     # ---- arbitrary logits processors: the reference's loop with the passes on the engine --------------------------------------------
     @staticmethod
@@ -743,16 +805,34 @@ class WhisperMedusaModel:
         self.last_stats = dict(iterations=n_iter, iterations_launched=n_iter, tokens_emitted=n_tok, accept_hist=hist, host_processors=len(procs))
         return seqs
 
-    def _outputs(self, seqs, gp, return_dict_in_generate, return_segments):
+    def _outputs(self, seqs, gp, return_dict_in_generate, return_segments, token_timestamps=None, tt_side=False):
         """Default: the padded LongTensor.  ``return_dict_in_generate`` / ``return_segments``: the reference's dict form
         ``{"sequences": ..., ["segments": ...]}`` (model.py:1747-1779; one segment per clip, short-form only)."""
+        if tt_side:          # an inner call of the language / long-form wrappers: they wrap the outputs themselves
+            self._last_tt = token_timestamps
+            token_timestamps = None
         return self._wrap_outputs(self._pad(seqs, gp), [len(gp.prompt)] * len(seqs), gp.pad_token_id, gp.eos_token_id,
                                   return_dict_in_generate, return_segments, timestamps=gp.timestamps,
-                                  time_precision=getattr(gp, "_time_precision", 0.02))
+                                  time_precision=getattr(gp, "_time_precision", 0.02), token_timestamps=token_timestamps)
 
-    def _wrap_outputs(self, t, prompt_lens, pad, eos, return_dict_in_generate, return_segments, timestamps=False, time_precision=0.02):
+    def _wrap_outputs(self, t, prompt_lens, pad, eos, return_dict_in_generate, return_segments, timestamps=False, time_precision=0.02,
+                      token_timestamps=None):
         """``return_dict_in_generate``: a GenerateEncoderDecoderOutput (model.py:812-823, :1715-1742); ``return_segments`` alone:
         the dict {"sequences", "segments"} of model.py:1764-1779 (one segment per clip, short-form only)."""
+        if token_timestamps is not None:
+            # HF forces return_dict_in_generate with return_token_timestamps: sequences + token_timestamps [B, T]; with return_segments every
+            # segment also carries the slice of its own tokens (HF's long-form output shape)
+            out = GenerateEncoderDecoderOutput(t, token_timestamps=token_timestamps)
+            if return_segments:
+                segs = self._wrap_outputs(t, prompt_lens, pad, eos, False, True, timestamps, time_precision)["segments"]
+                for i, P in enumerate(prompt_lens):
+                    o = P
+                    for sg in segs[i]:
+                        n = int(sg["tokens"].numel())
+                        sg["token_timestamps"] = token_timestamps[i, o: o + n]
+                        o += n
+                out["segments"] = segs
+            return out
         if not return_dict_in_generate and not return_segments:
             return t
         segs = None
@@ -816,20 +896,40 @@ class WhisperMedusaModel:
             groups.setdefault(l, []).append(i)
         rows: List[Optional[torch.Tensor]] = [None] * len(langs)
         plens = [0] * len(langs)
+        req, outer = kw.pop("_tt_req", None), kw.pop("_tt_outer", False)
+        tts: List[Optional[torch.Tensor]] = [None] * len(langs)
+        ms_tt = 0.0
         for l, idx in groups.items():
             # one group = every clip in its original order: the engine still holds the encoder pass detect_language() ran
             reuse = {"_encoded_batch": len(langs)} if len(groups) == 1 else {}
+            if req is not None:         # per-stream num_frames follow their clips into the group
+                nf = req["num_frames"]
+                reuse["_tt_req"] = dict(req, num_frames=[nf[i] for i in idx] if isinstance(nf, list) else nf)
             out = self.generate(input_features[idx], language=l, _language_resolved=True, **reuse, **kw)
+            if req is not None:
+                ms_tt += self.last_stats.get("ms_token_timestamps", 0.0)
             for j, i in enumerate(idx):
                 rows[i] = out[j]
                 plens[i] = len(self._last_prompt)
+                if req is not None:
+                    tts[i] = self._last_tt[j]
         T = max(r.numel() for r in rows)
         t = torch.full((len(rows), T), self.config.pad_token_id, dtype=torch.long, device=self.device)
         for i, r in enumerate(rows):
             t[i, : r.numel()] = r
         self.detected_languages = langs
+        tt = None
+        if req is not None:
+            tt = torch.zeros(len(rows), T, dtype=torch.float32, device=self.device)
+            for i, r in enumerate(tts):
+                tt[i, : r.numel()] = r
+                tt[i, r.numel():] = r[-1]
+            self.last_stats["ms_token_timestamps"] = ms_tt
+            if outer:
+                self._last_tt = tt
+                tt = None
         return self._wrap_outputs(t, plens, self.config.pad_token_id, self.config.eos_token_id, rdg, rseg, timestamps=rts,
-                                  time_precision=tprec)
+                                  time_precision=tprec, token_timestamps=tt)
 
     def _generate_longform(self, input_features, kw):
         """`chunk_longform=True`: clips longer than 30 s (the reference raises, model.py:1213-1214) are cut into 30 s windows,
@@ -862,16 +962,25 @@ class WhisperMedusaModel:
             langs = [kw.get("language")] * B
         kw.pop("language", None)
         rows, prompts = [None] * (B * n), [None] * B
+        req = kw.pop("_tt_req", None)
+        if req is not None and req["num_frames"] is not None:
+            raise NotImplementedError("num_frames= is not supported together with chunk_longform=True (the windows are fixed)")
+        wtt = [None] * (B * n)
+        ms_tt = 0.0
         for l in sorted(set(langs), key=lambda v: (v is None, v or "")):
             clips = [b for b in range(B) if langs[b] == l]
             widx = [b * n + j for b in clips for j in range(n)]
-            o = self.generate(win[widx], language=l, **kw)
+            o = self.generate(win[widx], language=l, **kw, **({"_tt_req": req} if req is not None else {}))
+            if req is not None:
+                ms_tt += self.last_stats.get("ms_token_timestamps", 0.0)
             for q, wi in enumerate(widx):
                 rows[wi] = o[q]
+                if req is not None:
+                    wtt[wi] = self._last_tt[q].cpu()
             for b in clips:
                 prompts[b] = list(self._last_prompt)
         eos, pad = cfg.eos_token_id, cfg.pad_token_id
-        seqs = []
+        seqs, all_tt = [], []
         segs = [[] for _ in range(B)]
         for b in range(B):
             if rts and rseg:
@@ -880,17 +989,41 @@ class WhisperMedusaModel:
                                                         time_offset=j * F * 0.01, result=rows[b * n + j])
             ids = list(prompts[b])
             P = len(ids)
+            tts = [0.0] * P
             for j in range(n):
                 row = rows[b * n + j][P:].tolist()
-                for t in row:
+                for q, t in enumerate(row):
                     if t == eos or t == pad:
                         break
                     ids.append(t)
+                    if req is not None:       # the window's own value, offset by the window's start (float32 sum, as the tensor holds it)
+                        tts.append(float(wtt[b * n + j][P + q] + torch.tensor(j * F * 0.01, dtype=torch.float32)))
             seqs.append(ids + [eos])
+            all_tt.append(tts + [tts[-1]])
+            if req is not None and rts and rseg:      # each segment's slice of its own window's values, offset like its start / end
+                k = 0
+                for j in range(n):
+                    o = P
+                    nseg = len(_timestamps.row_segments(rows[b * n + j].tolist(), P, eos, cfg.timestamp_begin, F, tprec))
+                    for sg in segs[b][k: k + nseg]:
+                        m = int(sg["tokens"].numel())
+                        sg["token_timestamps"] = wtt[b * n + j][o: o + m] + torch.tensor(j * F * 0.01, dtype=torch.float32)
+                        o += m
+                    k += nseg
         Tm = max(len(s_) for s_ in seqs)
         t = torch.full((B, Tm), pad, dtype=torch.long, device=self.device)
         for i, s_ in enumerate(seqs):
             t[i, : len(s_)] = torch.tensor(s_, dtype=torch.long)
+        if req is not None:
+            tt = torch.zeros(B, Tm, dtype=torch.float32)
+            for i, r in enumerate(all_tt):
+                tt[i, : len(r)] = torch.tensor(r, dtype=torch.float32)
+                tt[i, len(r):] = r[-1]
+            self.last_stats["ms_token_timestamps"] = ms_tt
+            out = GenerateEncoderDecoderOutput(t, token_timestamps=tt.to(self.device))
+            if rts and rseg:
+                out["segments"] = segs
+            return out
         if rts and rseg:
             return {"sequences": t, "segments": segs}
         return t

@@ -155,9 +155,17 @@ class MedusaConfig:
     max_initial_timestamp_index: Optional[int] = None     # WhisperTimeStampLogitsProcessor: None = no limit on the first timestamp
     posterior_threshold: float = 0.09   # medusa_utils.py:17
     posterior_alpha: float = 0.3        # medusa_utils.py:18
+    # token-level timestamps (generate(return_token_timestamps=True); HF generation_config.alignment_heads / config.median_filter_width):
+    # [[decoder layer, head], ..] whose cross-attention tracks the audio; None = the checkpoint names none
+    alignment_heads: Optional[List[List[int]]] = None
+    median_filter_width: int = 7
 
     # ------------------------------------------------------------------
     def __post_init__(self):
+        if self.alignment_heads is not None:
+            self.alignment_heads = self.check_alignment_heads(self.alignment_heads)
+        if not (isinstance(self.median_filter_width, int) and 1 <= self.median_filter_width <= 15 and self.median_filter_width % 2 == 1):
+            raise ValueError("median_filter_width must be an odd number in 1..15")
         if self.medusa_heads_type not in (HEADS_LINEAR, HEADS_BLOCK):
             # same error class/wording as reference model.py:225-229
             raise ValueError(
@@ -184,6 +192,20 @@ class MedusaConfig:
             if tb["n_nodes"] > MAX_TREE_NODES or tb["n_paths"] > MAX_TREE_PATHS or max(tb["topk"]) > MAX_TREE_TOPK:
                 raise ValueError(f"candidate tree {ch}: {tb['n_nodes']} nodes / {tb['n_paths']} paths / top-{max(tb['topk'])}; the engine "
                                  f"supports <= {MAX_TREE_NODES} nodes, <= {MAX_TREE_PATHS} paths, top-k <= {MAX_TREE_TOPK}")
+
+    def check_alignment_heads(self, heads) -> List[List[int]]:
+        """[[layer, head], ..] with every layer below decoder_layers and every head below decoder_attention_heads (1 .. 64 pairs)."""
+        try:
+            out = [[int(l), int(h)] for l, h in heads]
+        except (TypeError, ValueError):
+            raise ValueError("alignment_heads must be a list of [decoder layer, head] pairs")
+        if not 1 <= len(out) <= 64:
+            raise ValueError("alignment_heads must hold 1 .. 64 [decoder layer, head] pairs")
+        for l, h in out:
+            if not (0 <= l < self.decoder_layers and 0 <= h < self.decoder_attention_heads):
+                raise ValueError(f"alignment head [{l}, {h}] is out of range: the decoder has {self.decoder_layers} layers of "
+                                 f"{self.decoder_attention_heads} heads")
+        return out
 
     @property
     def is_tree(self) -> bool:
@@ -239,7 +261,8 @@ class MedusaConfig:
                 g = json.load(f)
             for k in ("eos_token_id", "pad_token_id", "decoder_start_token_id", "is_multilingual",
                       "lang_to_id", "task_to_id", "no_timestamps_token_id", "suppress_tokens",
-                      "begin_suppress_tokens", "max_length", "max_initial_timestamp_index", "posterior_threshold", "posterior_alpha"):
+                      "begin_suppress_tokens", "max_length", "max_initial_timestamp_index", "posterior_threshold", "posterior_alpha",
+                      "alignment_heads", "median_filter_width"):
                 if k in g and g[k] is not None:
                     d[k] = g[k]
         if "medusa_choices" not in d and "medusa_num_heads" in d:

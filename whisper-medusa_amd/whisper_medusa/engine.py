@@ -49,6 +49,10 @@ class WmTimestampParams(C.Structure):
                 ("begin_index", C.c_int32)]
 
 
+class WmAlignParams(C.Structure):
+    _fields_ = [("heads", C.POINTER(C.c_int32)), ("n_heads", C.c_int32), ("median_filter_width", C.c_int32), ("time_precision", C.c_float)]
+
+
 class WmStats(C.Structure):
     _fields_ = [("iterations", C.c_int64), ("iterations_launched", C.c_int64), ("tokens_emitted", C.c_int64),
                 ("accept_hist", C.c_int64 * 16),
@@ -59,7 +63,8 @@ class WmStats(C.Structure):
 EXPORTS = ["wm_create", "wm_destroy", "wm_last_error", "wm_abi_version", "wm_build_act_fp16", "wm_resample_len", "wm_resample", "wm_logmel", "wm_encode", "wm_set_encoder_output",
            "wm_decode_begin", "wm_decode_run", "wm_get_tokens", "wm_get_stats", "wm_sync",
            "wm_get_encoder_output", "wm_forward_logits", "wm_get_cross_kv", "wm_profile_kernel",
-           "wm_decode_begin_ts", "wm_select_rows"]
+           "wm_decode_begin_ts", "wm_select_rows",
+           "wm_token_timestamps", "wm_get_align_probs", "wm_get_align_matrix", "wm_dtw"]
 
 _lib = {}
 
@@ -111,6 +116,10 @@ def load_library(path: Optional[str] = None, act_fp16: bool = False) -> C.CDLL:
     lib.wm_forward_logits.argtypes = [vp, i32, i32p, i32, i32, i32, f32p]
     lib.wm_get_cross_kv.argtypes = [vp, i32, i32, i32, f32p, f32p]
     lib.wm_profile_kernel.argtypes = [vp, i32, i32, i32, f32p, C.POINTER(C.c_double)]
+    lib.wm_token_timestamps.argtypes = [vp, C.POINTER(WmAlignParams), i32, i32p, i32, i32p, i32p, i32p, f32p, f32p]
+    lib.wm_get_align_probs.argtypes = [vp, i32, i32, f32p]
+    lib.wm_get_align_matrix.argtypes = [vp, i32, f32p]
+    lib.wm_dtw.argtypes = [vp, f32p, i32, i32, i32p, i32p, i32p, i32p]
     for name in EXPORTS:
         if name not in ("wm_destroy", "wm_last_error", "wm_resample_len"):      # wm_resample_len returns int64 (set above)
             getattr(lib, name).restype = i32
@@ -304,6 +313,63 @@ class Engine:
                                             lens.ctypes.data_as(i32p), probe.ctypes.data_as(i32p), am.ctypes.data_as(i32p),
                                             pp.ctypes.data_as(f32p), H.ctypes.data_as(f32p), fo.ctypes.data_as(i32p)), "wm_select_rows")
         return dict(argmax=am, p_probe=pp, entropy=H, ts_forced=fo)
+
+    # ---- token-level timestamps (include/wm.h wm_token_timestamps) ---------------------------------
+    def token_timestamps(self, seqs: Sequence[Sequence[int]], n_prompt, alignment_heads: Sequence[Sequence[int]], median_filter_width: int = 7,
+                         time_precision: float = 0.02, num_frames=None):
+        """Teacher-forced replay of ``seqs`` (one id list per stream of the resident encoder pass: prompt + generated, the stream's own end)
+        that taps the alignment heads, then normalisation, median filter and DTW on the GPU (HF _extract_token_timestamps).  ``n_prompt``:
+        int or one per stream; ``num_frames``: None, int or one per stream (mel frames of the clip: the attention is cropped to half of it).
+        Returns (numpy float32 [B, max len] seconds, ms).  Overwrites the decode state."""
+        B = len(seqs)
+        heads = np.ascontiguousarray(alignment_heads, dtype=np.int32).reshape(-1, 2)
+        Tmax = max(max(len(s) for s in seqs), 1)
+        tok = np.zeros((B, Tmax), dtype=np.int32)
+        for b, s in enumerate(seqs):
+            tok[b, : len(s)] = s
+        lens = np.array([len(s) for s in seqs], dtype=np.int32)
+        npr = np.ascontiguousarray(np.broadcast_to(np.asarray(n_prompt, dtype=np.int32), (B,)))
+        nf = None if num_frames is None else np.ascontiguousarray(np.broadcast_to(np.asarray(num_frames, dtype=np.int32), (B,)))
+        out = np.zeros((B, Tmax), dtype=np.float32)
+        ms = C.c_float(0)
+        ap = WmAlignParams(heads.ctypes.data_as(C.POINTER(C.c_int32)), heads.shape[0], int(median_filter_width), float(time_precision))
+        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        self._kv_stamp = object()
+        self._align_shape = (lens - npr - 1, None if nf is None else nf // 2)
+        self._check(self.lib.wm_token_timestamps(self.h, C.byref(ap), B, tok.ctypes.data_as(i32p), Tmax, lens.ctypes.data_as(i32p),
+                                                 npr.ctypes.data_as(i32p), None if nf is None else nf.ctypes.data_as(i32p),
+                                                 out.ctypes.data_as(f32p), C.byref(ms)), "wm_token_timestamps")
+        return out, ms.value
+
+    def _align_nf(self, stream: int):
+        N, F = self._align_shape
+        S = self.cfg.max_source_positions
+        return int(N[stream]), S if F is None else min(int(F[stream]), S)
+
+    def align_probs(self, stream: int, a: int) -> np.ndarray:
+        """Parity tap: softmax weights [N, n_ctx] of alignment head ``a`` of the last token_timestamps call."""
+        N, _ = self._align_nf(stream)
+        out = np.zeros((max(N, 0), self.cfg.max_source_positions), dtype=np.float32)
+        self._check(self.lib.wm_get_align_probs(self.h, stream, a, out.ctypes.data_as(C.POINTER(C.c_float))), "wm_get_align_probs")
+        return out
+
+    def align_matrix(self, stream: int) -> np.ndarray:
+        """Parity tap: the matrix [N, F] the DTW of the last token_timestamps call ran on."""
+        N, F = self._align_nf(stream)
+        out = np.zeros((max(N, 0), F), dtype=np.float32)
+        self._check(self.lib.wm_get_align_matrix(self.h, stream, out.ctypes.data_as(C.POINTER(C.c_float))), "wm_get_align_matrix")
+        return out
+
+    def dtw(self, matrix: np.ndarray):
+        """Parity tap: HF _dynamic_time_warping(-matrix) by the engine's kernel -> (text_indices, time_indices, first_frame)."""
+        m = np.ascontiguousarray(matrix, dtype=np.float32)
+        N, F = m.shape
+        first = np.zeros(N, np.int32); pt = np.zeros(N + F, np.int32); pm = np.zeros(N + F, np.int32)
+        n = C.c_int32(0)
+        i32p = C.POINTER(C.c_int32)
+        self._check(self.lib.wm_dtw(self.h, m.ctypes.data_as(C.POINTER(C.c_float)), N, F, first.ctypes.data_as(i32p), pt.ctypes.data_as(i32p),
+                                    pm.ctypes.data_as(i32p), C.byref(n)), "wm_dtw")
+        return pt[: n.value].copy(), pm[: n.value].copy(), first
 
     def tokens(self, stream: int) -> List[int]:
         cap = self.cfg.max_target_positions + 16

@@ -79,24 +79,34 @@ class ContextPool:
             e.close()
         self.engines = []
 
-    def _one(self, eng: Engine, x: torch.Tensor, gp: GenParams, from_wav: bool):
+    def _one(self, eng: Engine, x: torch.Tensor, gp: GenParams, from_wav: bool, token_ts=None):
         with torch.cuda.device(eng.device):
             feats = eng.logmel(x) if from_wav else x
             eng.encode(feats)
             seqs = eng.decode(gp, x.shape[0])
-            return seqs, eng.stats()
+            st = eng.stats()
+            tt = None
+            if token_ts is not None:        # every context replays its own streams (api.token_timestamps_of)
+                tt, st["ms_token_timestamps"] = token_ts(eng, seqs)
+            return seqs, st, tt
 
-    def run(self, x: torch.Tensor, gp: GenParams, from_wav: bool = False) -> List[List[int]]:
-        """x: input features [B, n_mels, frames] (or waveforms [B, samples] with ``from_wav``) on the pool's GPU."""
+    def run(self, x: torch.Tensor, gp: GenParams, from_wav: bool = False, token_ts=None) -> List[List[int]]:
+        """x: input features [B, n_mels, frames] (or waveforms [B, samples] with ``from_wav``) on the pool's GPU.
+        ``token_ts(engine, seqs, lo)`` -> (list of per-stream float32 arrays, ms): token-level timestamps of a context's streams (whose first
+        is stream ``lo`` of the batch), computed right behind its decode; the per-stream arrays are left in ``last_token_timestamps``."""
         B = x.shape[0]
         if B > self.per_ctx * len(self.engines):
             raise ValueError(f"batch of {B} exceeds the pool capacity {self.per_ctx * len(self.engines)}")
         bounds = shard_bounds(B, len(self.engines))
         if len(bounds) == 1:
-            res = [self._one(self.engines[0], x, gp, from_wav)]
+            res = [self._one(self.engines[0], x, gp, from_wav, None if token_ts is None else (lambda e, s: token_ts(e, s, 0)))]
         else:
-            futs = [self._ex.submit(self._one, self.engines[i], x[lo:hi].contiguous(), gp, from_wav)
+            futs = [self._ex.submit(self._one, self.engines[i], x[lo:hi].contiguous(), gp, from_wav,
+                                    None if token_ts is None else (lambda e, s, lo=lo: token_ts(e, s, lo)))
                     for i, (lo, hi) in enumerate(bounds)]
             res = [f.result() for f in futs]
-        self.last_stats = merge_stats([st for _, st in res])
-        return [s for seqs, _ in res for s in seqs]
+        self.last_stats = merge_stats([st for _, st, _ in res])
+        if token_ts is not None:
+            self.last_stats["ms_token_timestamps"] = max(st["ms_token_timestamps"] for _, st, _ in res)
+            self.last_token_timestamps = [r for _, _, tt in res for r in tt]
+        return [s for seqs, _, _ in res for s in seqs]

@@ -126,6 +126,23 @@ def synth_state_dict(cfg: MedusaConfig, seed: int = 0, device: str = "cpu",
     return sd
 
 
+def synth_alignment_heads(cfg: MedusaConfig, n: int = 4) -> List[List[int]]:
+    """``n`` deterministic [decoder layer, head] pairs in the upper half of the decoder (where Whisper's alignment heads sit), walking the
+    layers from the middle up and the heads with a stride: what a synthetic checkpoint's ``alignment_heads`` is set to in tests and
+    microbenchmarks.  The same pair is never returned twice (at most layers_in_upper_half * heads pairs)."""
+    L, H = cfg.decoder_layers, cfg.decoder_attention_heads
+    lo = L // 2
+    n = max(1, min(int(n), (L - lo) * H))
+    out = []
+    for i in range(n):
+        l = lo + i % (L - lo)
+        h = (3 * (i // (L - lo)) + l) % H if H % 3 else (i // (L - lo) + l) % H
+        while [l, h] in out:
+            h = (h + 1) % H
+        out.append([l, h])
+    return out
+
+
 def default_prompt(cfg: MedusaConfig, language: Optional[str] = "en", task: str = "transcribe", timestamps: bool = False) -> List[int]:
     """Decoder prompt ids (G1; reference model.py:1519-1537 via HF ``_retrieve_init_tokens``).  ``timestamps=True``: without
     <|notimestamps|> (HF drops it when return_timestamps is set)."""
