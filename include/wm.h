@@ -231,6 +231,29 @@ int wm_token_timestamps(wm_ctx* ctx, const wm_align_params* ap, int B, const int
                         const int32_t* lens /* HOST [B] */, const int32_t* n_prompt /* HOST [B] */, const int32_t* num_frames /* HOST [B] or NULL */,
                         float* out /* HOST [B][Tmax] seconds */, float* ms /* hipEvent time of replay + alignment, may be NULL */);
 
+/* ---- token log-probabilities and the no-speech probability (additive to ABI v9; csrc/wm_score.hip) ----
+ * Stands in for what HF's greedy decode returns with output_scores (GenerationMixin: `scores[i]`, the processed logits of step i) as consumed by
+ * WhisperGenerationMixin._retrieve_avg_logprobs (log_softmax at temperature 1, gathered at the emitted ids), and for WhisperNoSpeechDetection
+ * (transformers generation/logits_process.py: softmax of the UNPROCESSED logits of the <|startoftranscript|> row at no_speech_token_id).  The
+ * reference refuses no_speech_threshold (model.py:1201-1205) and ignores logprob_threshold.  A Medusa loop processes the rows of an iteration
+ * under one shared length (model.py:689-694), so "the scores of step i" do not exist inside it: the engine replays the FINAL ids teacher-forced
+ * through all decoder layers in 16-row tiles (the context's own decode contract) and scores every row under its OWN length. */
+typedef struct wm_score_params {
+    int32_t no_speech_token_id;  /* < 0: no_speech_prob is not computed.  HF: generation_config.no_speech_token_id, default no_timestamps_token_id - 1 */
+    int32_t sot_index;           /* index of <|startoftranscript|> in the prompt; < 0: 0.  With prompt_ids it is len(prompt_ids) (HF reads index 0 there) */
+} wm_score_params;
+/* Per stream b: ids tokens[b][0 .. lens[b]) (the stream's own end: EOS included, padding excluded), scored from position n_prompt[b] on.  For
+ * n_prompt <= t < lens: z = base-head logits of input position t - 1; the processors of gp with cur_len = t (exponential decay, begin-suppress at
+ * t == begin_index, suppress list; prompt_len / begin_index as wm_decode_begin_ts reads them), then — ts != NULL — HF
+ * WhisperTimeStampLogitsProcessor with prefix tokens[b][0 .. t); logprobs[b][t] = log_softmax(processed row)[tokens[b][t]] in fp32, -inf where that
+ * id is masked; 0 for t < n_prompt and t >= lens.  no_speech_prob[b] (may be NULL) = softmax(raw row of input position sot_index)[no_speech_token_id].
+ * Needs wm_encode (else WM_ERR_STATE); WM_ERR_ARG (wm_last_error says which) for lens[b] > n_tgt, n_prompt[b] > lens[b] or < 1, an id outside the
+ * vocabulary, sot_index outside the prompt.  Overwrites the decode state like wm_forward_logits (begin again afterwards).  *ms: hipEvent time of
+ * replay + vocabulary projection + scoring. */
+int wm_score_tokens(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* ts /* NULL: rules off */, const wm_score_params* sp /* may be NULL */,
+                    int B, const int32_t* tokens /* HOST [B][Tmax] */, int Tmax, const int32_t* lens /* HOST [B] */, const int32_t* n_prompt /* HOST [B] */,
+                    float* logprobs /* HOST [B][Tmax] */, float* no_speech_prob /* HOST [B] or NULL */, float* ms /* may be NULL */);
+
 /* ---- parity taps (test-only views of intermediate state; no reference equivalent except
  * forward(), model.py:1223-1347) ---- */
 /* encoder output [B][n_ctx][d_model] as float32 to HOST */
@@ -251,6 +274,13 @@ int wm_forward_logits(wm_ctx* ctx, int B, const int32_t* tokens /* HOST [B][T] *
 int wm_select_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* ts, int R, const float* logits, const int32_t* prefixes,
                    int Tmax, const int32_t* lens, const int32_t* probe_tokens, int32_t* out_argmax, float* out_p_probe, float* out_entropy,
                    int32_t* out_ts_forced);
+/* Scoring parity tap, the counterpart of wm_select_rows: R caller-given logits rows (HOST float32 [R][vocab]) through the scoring kernels of
+ * wm_score_tokens only, row r under prefix prefixes[r][0 .. lens[r]) (HOST int32 [R][Tmax]) with cur_len = lens[r] — its own length, exponential
+ * decay included — and target targets[r]; ts NULL: rules off.  out_logprob HOST [R]: what HF's log_softmax(processors(row))[target] gives, -inf for
+ * a masked target.  WM_ERR_ARG for lens outside [1, min(Tmax, n_tgt)] or a target outside the vocabulary.  Overwrites the processors' tables of the
+ * decode state (begin again afterwards).  Any R >= 1. */
+int wm_score_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* ts, int R, const float* logits, const int32_t* prefixes,
+                  int Tmax, const int32_t* lens, const int32_t* targets, float* out_logprob);
 /* Alignment parity taps: views of the last wm_token_timestamps call.  WM_ERR_STATE for a stream whose workspace group is no longer
  * resident (only the last group is) or that had fewer than 2 rows.  Probabilities of alignment head a (the softmax of HF WhisperAttention's
  * cross branch, modeling_whisper.py, before any crop): HOST float32 [N][n_ctx]. */

@@ -40,6 +40,7 @@ extern "C" void wm_destroy(wm_ctx* ctx)
                     ctx->ts.st, ctx->ts.ver, ctx->ts.part1t, ctx->ts.forced};
     for (void* b : bufs) if (b) hipFree(b);
     wm_align_free(ctx);
+    wm_score_free(ctx);
     if (ctx->ev0) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) hipEventDestroy(ctx->ev1);
     if (ctx->own_stream && ctx->stream) hipStreamDestroy(ctx->stream);
@@ -305,7 +306,7 @@ extern "C" int wm_set_encoder_output(wm_ctx* ctx, const float* hidden, int B)
 }
 
 // the timestamp scalars of a decode / tap: ts == NULL -> off.  Validation errors go to ctx->err.
-static int ts_setup(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* ts, TsDev* out)
+int wm_ts_setup(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* ts, TsDev* out)
 {
     TsDev t = ctx->ts;
     t.on = 0; t.tb = 0; t.nots = -1; t.mit = -1; t.L = ctx->L;
@@ -349,7 +350,7 @@ extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm
     g.force_accept = gp->force_accept;
     g.begin = gp->begin_index >= 0 ? gp->begin_index : P;
     TsDev ts{};
-    if (int rc = ts_setup(ctx, gp, tsp, &ts)) return rc;
+    if (int rc = wm_ts_setup(ctx, gp, tsp, &ts)) return rc;
     if (ts.on && tsp->begin_index >= 0) g.begin = tsp->begin_index;
     g.accept_mode = gp->accept_mode; g.vanilla = gp->vanilla; g.K = K; g.V = ctx->V; g.Vpad = ctx->Vpad; g.Tids = Tids;
     ctx->fuse = std::getenv("WM_NO_CARRY") == nullptr;
@@ -608,7 +609,7 @@ extern "C" int wm_select_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_tim
     WM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     TsDev ts{};
-    if (int rc = ts_setup(ctx, gp, tsp, &ts)) return rc;
+    if (int rc = wm_ts_setup(ctx, gp, tsp, &ts)) return rc;
     GenDev g{};
     g.P = gp->prompt_len; g.eos = gp->eos_token_id; g.pad = gp->pad_token_id;
     g.max_length = g.hard_max_length = ctx->Tmax; g.exp_start = -1;

@@ -195,6 +195,7 @@ struct wm_ctx {
 
     // ---- token timestamps (wm_align.hip): workspace of the last wm_token_timestamps call, allocated on first use ----
     struct wm_align_state* align = nullptr;
+    struct wm_score_state* score = nullptr;     // token log-probabilities (wm_score.hip): row descriptors, slice partials and outputs, allocated on first use
     bool replay = false;            // a teacher-forced replay pass is being enqueued: the cross-q launch must leave its fp32 rows in qbuf (no WM_FUSE_CQ)
 };
 
@@ -223,6 +224,10 @@ int wm_dec_fold_init(wm_ctx* ctx);   // c = W gamma, b' = b + W beta of every La
 int wm_dec_replay_layers(wm_ctx* ctx, int b0, int nb, int Mper, int n_layers, int (*after)(wm_ctx*, int, void*), void* arg);
 // implemented in wm_align.hip
 void wm_align_free(wm_ctx* ctx);
+// implemented in wm_score.hip
+void wm_score_free(wm_ctx* ctx);
+// implemented in wm_engine.hip: the timestamp scalars of a decode / tap / scoring call (ts == NULL: off); validation errors go to ctx->err
+int wm_ts_setup(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* ts, TsDev* out);
 // timestamp parity tap (wm_select_rows): R <= 15 rows already in ctx->logits, probe tokens in cand[1 .. R], cur_len in L[0];
 // prefixes DEV [R][Tmax], lengths DEV [R]
 int wm_dec_select_rows(wm_ctx* ctx, const int* pre_dev, const int* len_dev, int R, int Tmax);

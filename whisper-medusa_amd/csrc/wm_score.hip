@@ -1,0 +1,365 @@
+// wm_score.hip — token log-probabilities and the no-speech probability (include/wm.h wm_score_tokens / wm_score_rows): what
+// HF's greedy decode hands out as `scores[i]` (GenerationMixin with output_scores: the processed logits of step i, log-softmaxed by
+// WhisperGenerationMixin._retrieve_avg_logprobs) and what WhisperNoSpeechDetection reads off the raw <|startoftranscript|> row, for an
+// engine whose Medusa loop emits several tokens per iteration under one shared length and never keeps a logits row.
+//
+//   replay         the final ids of every stream go through ALL decoder layers once more, teacher-forced, in 16-row tiles (the launches of a
+//                  base pass: wm_decoder.hip wm_dec_replay_layers), then the final LayerNorm and the packed vocabulary projection of the base
+//                  head for the tile's rows (no Medusa heads, no Medusa-Block extra layer)
+//   k_score_build  one thread per stream: the tile's row descriptors — row of input position t - 1 scores s[t] under cur_len = t, its OWN
+//                  length — and, with the timestamp rules on, the row's record from the fold of its own prefix (carried from tile to tile)
+//   k_score1       SEL_SP slice blocks per row: running (max, sum of exp) at temperature 1 of the processed row, text region [0, tb) and
+//                  timestamp region [tb, V) apart (the partials ts_finish takes); 16-byte loads, wave64 shuffles, one LDS round
+//   k_score2       one thread per row: merges the slices (ts_finish: the log-softmax decision of the timestamp rules), gathers the processed
+//                  logit of the target and writes logit - max - log Z, or -inf where the target is masked
+// The raw <|startoftranscript|> row rides in the launches of the tile that holds it as one extra row per stream: no mask, target = the
+// no-speech token.  Only [B][Tmax] + [B] floats go back to the host.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+#include "wm_select.h"
+
+struct wm_score_state {
+    int4 *desc = nullptr, *rec = nullptr, *sst = nullptr;   // [rows] {logits row, cur_len (< 0: raw row), target (< 0: skip), out index}, records; [maxB] fold state
+    float *p1 = nullptr, *p1t = nullptr, *out = nullptr;    // [rows][SEL_SP][4] text / timestamp partials; outputs
+    int *lens = nullptr, *npr = nullptr, *ibuf = nullptr;   // [maxB] each; tap: prefixes + lengths + targets
+    size_t cap_rows = 0, cap_out = 0, cap_b = 0, cap_ibuf = 0;
+};
+
+void wm_score_free(wm_ctx* ctx)
+{
+    wm_score_state* sc = ctx->score;
+    if (!sc) return;
+    void* bufs[] = {sc->desc, sc->rec, sc->sst, sc->p1, sc->p1t, sc->out, sc->lens, sc->npr, sc->ibuf};
+    for (void* b : bufs) if (b) hipFree(b);
+    delete sc;
+    ctx->score = nullptr;
+}
+
+template <class T>
+static hipError_t regrow(T** p, size_t n)
+{
+    if (*p) { (void)hipFree(*p); *p = nullptr; }
+    return hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(n, 1) * sizeof(T));
+}
+
+static int score_reserve(wm_ctx* ctx, size_t rows, size_t nout, size_t nb, size_t nibuf)
+{
+    if (!ctx->score) ctx->score = new wm_score_state();
+    wm_score_state* sc = ctx->score;
+    if (rows > sc->cap_rows) {
+        sc->cap_rows = 0;
+        WM_HIP(regrow(&sc->desc, rows)); WM_HIP(regrow(&sc->rec, rows));
+        WM_HIP(regrow(&sc->p1, rows * SEL_SP * 4)); WM_HIP(regrow(&sc->p1t, rows * SEL_SP * 4));
+        sc->cap_rows = rows;
+    }
+    if (nout > sc->cap_out) { sc->cap_out = 0; WM_HIP(regrow(&sc->out, nout)); sc->cap_out = nout; }
+    if (nb > sc->cap_b) { sc->cap_b = 0; WM_HIP(regrow(&sc->lens, nb)); WM_HIP(regrow(&sc->npr, nb)); WM_HIP(regrow(&sc->sst, nb)); sc->cap_b = nb; }
+    if (nibuf > sc->cap_ibuf) { sc->cap_ibuf = 0; WM_HIP(regrow(&sc->ibuf, nibuf)); sc->cap_ibuf = nibuf; }
+    return WM_OK;
+}
+
+__global__ void k_score_fill(int* __restrict__ p, int n, int v)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_score_build: thread b = stream b of the call.  Tile rows i = 0 .. Mper - 1 are input positions pos0 + i; row i scores s[t], t = pos0 + i + 1,
+// when n_prompt <= t < len.  The timestamp state of ids[begin : t) is carried across the tiles in sst (reset by the first tile).
+// Row nb * Mper + b is the stream's raw <|startoftranscript|> row when position `sot` lies in this tile.
+// ---------------------------------------------------------------------------------------------
+__global__ void k_score_build(const int* __restrict__ ids, int Tids, const int* __restrict__ lens, const int* __restrict__ npr, int nb, int pos0,
+                              int Mper, GenDev gp, TsDev ts, int sot, int ns_id, int Tout, int ns_out0, int4* __restrict__ sst,
+                              int4* __restrict__ desc, int4* __restrict__ rec)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= nb) return;
+    int4 st = pos0 == 0 ? make_int4(0, 0, -1, 0) : sst[b];
+    const int* id = ids + (size_t)b * Tids;
+    const int T = lens[b], P = npr[b];
+    for (int i = 0; i < Mper; ++i) {
+        const int pos = pos0 + i, t = pos + 1;
+        if (ts.on && pos >= gp.begin && pos < T) st = ts_fold(st, id[pos], ts.tb);          // st: ids[begin : t)
+        const bool scored = t >= P && t < T;
+        desc[b * Mper + i] = make_int4(b * Mper + i, t, scored ? id[t] : -1, b * Tout + t);
+        rec[b * Mper + i] = ts.on ? ts_record(st, t, gp.begin, ts.tb, gp.V, ts.mit) : make_int4(0, 0, 0, 0);
+    }
+    sst[b] = st;
+    const bool here = ns_id >= 0 && sot >= pos0 && sot < pos0 + Mper && sot < T;
+    desc[nb * Mper + b] = make_int4(here ? b * Mper + (sot - pos0) : 0, -1, here ? ns_id : -1, ns_out0 + b);
+    rec[nb * Mper + b] = make_int4(0, 0, 0, 0);
+}
+
+// parity tap: row r = caller-given logits row r under prefix pre[r][0 .. len[r]) (the fold k_ts_tap_build does for wm_select_rows), its own length
+__global__ void k_score_tap_build(const int* __restrict__ pre, const int* __restrict__ len, const int* __restrict__ tgt, int R, int Tmax, GenDev gp,
+                                  TsDev ts, int4* __restrict__ desc, int4* __restrict__ rec)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R) return;
+    int4 st = make_int4(0, 0, -1, 0);
+    const int n = len[r];
+    if (ts.on) for (int t = max(gp.begin, 0); t < n; ++t) st = ts_fold(st, pre[(size_t)r * Tmax + t], ts.tb);
+    desc[r] = make_int4(r, n, tgt[r], r);
+    rec[r] = ts.on ? ts_record(st, n, gp.begin, ts.tb, gp.V, ts.mit) : make_int4(0, 0, 0, 0);
+}
+
+// running (max, sum of exp(v - max)) of one more value / of two partial results; -inf never enters
+__device__ __forceinline__ void lse_push(float& m, float& z, float v)
+{
+    if (v > m) { z = z * expf(m - v) + 1.0f; m = v; }
+    else z += expf(v - m);
+}
+__device__ __forceinline__ void lse_merge(float& m, float& z, float om, float oz)
+{
+    const float M = fmaxf(m, om);
+    z = (M == -INFINITY) ? 0.f : z * expf(m - M) + oz * expf(om - M);
+    m = M;
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_score1: grid (SEL_SP, rows), 256 threads.  Slice sp of a row is float4s [sp * per4, (sp + 1) * per4) of its Vpad-strided logits row (16-byte
+// aligned: Vpad is a multiple of 16).  Sibling of k_select1_ts<true> with the row's own cur_len and record, one sweep, temperature 1.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_score1(const float* __restrict__ logits, GenDev gp, const unsigned char* __restrict__ mask, const float* __restrict__ exppen, TsDev ts,
+         const int4* __restrict__ desc, const int4* __restrict__ recs, float* __restrict__ p1, float* __restrict__ p1t)
+{
+    __shared__ float sm[4][4];
+    const int row = blockIdx.y, sp = blockIdx.x;
+    const int4 dsc = desc[row];
+    if (dsc.z < 0) return;
+    const bool raw = dsc.y < 0;
+    const int cur_len = dsc.y;
+    const int4 rec = recs[row];
+    const bool tson = ts.on && !raw;
+    const int tb = tson ? ts.tb : gp.V;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const float4* x4 = reinterpret_cast<const float4*>(logits + (size_t)dsc.x * gp.Vpad);
+    const int n4 = (gp.V + 3) / 4, per4 = (n4 + SEL_SP - 1) / SEL_SP, q0 = sp * per4, q1 = min(n4, q0 + per4);
+    float mt = -INFINITY, zt = 0.f, ms = -INFINITY, zs = 0.f;
+    for (int q = q0 + tid; q < q1; q += 256) {
+        const float4 v4 = x4[q];
+        const float vals[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int n = 4 * q + j;
+            if (n >= gp.V) continue;
+            float v = vals[j];
+            if (!raw) {
+                v = proc_logit(v, n, cur_len, gp, mask, exppen);
+                if (tson) v = ts_mask(v, n, rec, gp, ts);
+            }
+            if (v == -INFINITY) continue;
+            if (n < tb) lse_push(mt, zt, v); else lse_push(ms, zs, v);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        lse_merge(mt, zt, __shfl_xor(mt, o, 64), __shfl_xor(zt, o, 64));
+        lse_merge(ms, zs, __shfl_xor(ms, o, 64), __shfl_xor(zs, o, 64));
+    }
+    if (lane == 0) { sm[w][0] = mt; sm[w][1] = zt; sm[w][2] = ms; sm[w][3] = zs; }
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int k = 1; k < 4; ++k) { lse_merge(mt, zt, sm[k][0], sm[k][1]); lse_merge(ms, zs, sm[k][2], sm[k][3]); }
+        float* o = p1 + ((size_t)row * SEL_SP + sp) * 4;
+        o[0] = mt; o[1] = __int_as_float(0); o[2] = zt; o[3] = 0.f;
+        float* q = p1t + ((size_t)row * SEL_SP + sp) * 4;
+        q[0] = ms; q[1] = __int_as_float(0); q[2] = zs; q[3] = zs;      // temperature 1: both sums of the timestamp region are the same
+    }
+}
+
+// k_score2: one thread per row (the shape of k_select_argmax_ts): the decision and the row's (max, Z) from the slices, then the target's score
+__global__ void k_score2(const float* __restrict__ logits, GenDev gp, const unsigned char* __restrict__ mask, const float* __restrict__ exppen,
+                         TsDev ts, const int4* __restrict__ desc, const int4* __restrict__ recs, const float* __restrict__ p1,
+                         const float* __restrict__ p1t, int nrows, float* __restrict__ out)
+{
+    const int row = blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= nrows) return;
+    const int4 dsc = desc[row];
+    if (dsc.z < 0) return;
+    const TsSel f = ts_finish(p1 + (size_t)row * SEL_SP * 4, p1t + (size_t)row * SEL_SP * 4, 1.0f);
+    const int n = dsc.z;
+    float v = logits[(size_t)dsc.x * gp.Vpad + n];
+    if (dsc.y >= 0) {
+        v = proc_logit(v, n, dsc.y, gp, mask, exppen);
+        if (ts.on) {
+            v = ts_mask(v, n, recs[row], gp, ts);
+            if (f.forced && n < ts.tb) v = -INFINITY;
+        }
+    }
+    out[dsc.w] = (v == -INFINITY) ? -INFINITY : (v - f.mx) - logf(f.z);
+}
+
+// ---------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------
+// the processors' scalars and tables of a scoring call: what wm_decode_begin_ts derives from the same structs
+static int score_setup(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* tsp, const char* who, GenDev* g_out, TsDev* ts_out)
+{
+    if (gp->eos_token_id < 0 || gp->eos_token_id >= ctx->V) { ctx->err = std::string(who) + ": eos out of range"; return WM_ERR_ARG; }
+    if (gp->prompt_len < 0 || (gp->prompt_len > 0 && !gp->prompt)) { ctx->err = std::string(who) + ": bad prompt"; return WM_ERR_ARG; }
+    hipStream_t st = ctx->stream;
+    TsDev ts{};
+    if (int rc = wm_ts_setup(ctx, gp, tsp, &ts)) return rc;
+    const int P = gp->prompt_len, Tids = ctx->Tal;
+    GenDev g{};
+    g.P = P; g.eos = gp->eos_token_id; g.pad = gp->pad_token_id;
+    g.max_length = g.hard_max_length = ctx->Tmax;
+    g.exp_start = gp->exp_decay_start >= 0 ? gp->exp_decay_start + P : -1;
+    g.thr = gp->posterior_threshold; g.alpha = gp->posterior_alpha; g.inv_temp = 1.0f;
+    g.force_accept = -1;
+    g.begin = gp->begin_index >= 0 ? gp->begin_index : P;
+    if (ts.on && tsp->begin_index >= 0) g.begin = tsp->begin_index;
+    g.accept_mode = WM_ACCEPT_TYPICAL; g.vanilla = 1;       // vanilla: the final stage stops at the LayerNorm (no Medusa-Block extra layer)
+    g.K = ctx->K; g.V = ctx->V; g.Vpad = ctx->Vpad; g.Tids = Tids;
+    std::vector<unsigned char> mask(ctx->Vpad, 0);
+    for (int i = 0; i < gp->n_suppress; ++i) if (gp->suppress[i] >= 0 && gp->suppress[i] < ctx->V) mask[gp->suppress[i]] |= 1;
+    for (int i = 0; i < gp->n_begin_suppress; ++i)
+        if (gp->begin_suppress[i] >= 0 && gp->begin_suppress[i] < ctx->V) mask[gp->begin_suppress[i]] |= 2;
+    std::vector<float> pen(Tids + 1, 0.f);
+    if (g.exp_start >= 0)
+        for (int t = 0; t <= Tids; ++t)     // (factor^(cur_len - start) - 1) evaluated in double like the Python scalar (wm_decode_begin_ts)
+            pen[t] = t > g.exp_start ? (float)(std::pow((double)gp->exp_decay_factor, (double)(t - g.exp_start)) - 1.0) : 0.f;
+    WM_HIP(hipMemcpyAsync(ctx->supmask, mask.data(), mask.size(), hipMemcpyHostToDevice, st));
+    WM_HIP(hipMemcpyAsync(ctx->exppen, pen.data(), pen.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    WM_HIP(hipStreamSynchronize(st));      // host vectors go out of scope
+    *g_out = g; *ts_out = ts;
+    return WM_OK;
+}
+
+static int score_launch(wm_ctx* ctx, const GenDev& g, const TsDev& ts, int nrows)
+{
+    wm_score_state* sc = ctx->score;
+    hipLaunchKernelGGL(k_score1, dim3(SEL_SP, nrows), dim3(256), 0, ctx->stream, ctx->logits, g, ctx->supmask, ctx->exppen, ts, sc->desc, sc->rec,
+                       sc->p1, sc->p1t);
+    WM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_score2, dim3((nrows + 63) / 64), dim3(64), 0, ctx->stream, ctx->logits, g, ctx->supmask, ctx->exppen, ts, sc->desc, sc->rec,
+                       sc->p1, sc->p1t, nrows, sc->out);
+    WM_HIP(hipGetLastError());
+    return WM_OK;
+}
+
+static int score_tokens_run(wm_ctx* ctx, const GenDev& g, const TsDev& ts, int ns_id, int sot, int B, const int32_t* tokens, int Tmax,
+                            const int32_t* lens, const int32_t* n_prompt, float* logprobs, float* no_speech_prob)
+{
+    hipStream_t st = ctx->stream;
+    const int Tids = ctx->Tal;
+    if (int rc = score_reserve(ctx, (size_t)B * 17, (size_t)B * Tmax + B, (size_t)B, 0)) return rc;
+    wm_score_state* sc = ctx->score;
+    std::vector<int> ids((size_t)B * Tids, 0);      // rows past a stream's length: token 0, computed and ignored
+    int npos = 0;
+    for (int b = 0; b < B; ++b) {
+        for (int t = 0; t < lens[b]; ++t) ids[(size_t)b * Tids + t] = tokens[(size_t)b * Tmax + t];
+        npos = std::max(npos, std::max(lens[b] - 1, ns_id >= 0 ? sot + 1 : 0));
+    }
+    WM_HIP(hipMemcpyAsync(ctx->ids, ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    WM_HIP(hipMemcpyAsync(sc->lens, lens, B * sizeof(int), hipMemcpyHostToDevice, st));
+    WM_HIP(hipMemcpyAsync(sc->npr, n_prompt, B * sizeof(int), hipMemcpyHostToDevice, st));
+    WM_HIP(hipMemsetAsync(sc->out, 0, ((size_t)B * Tmax + B) * sizeof(float), st));
+    WM_HIP(hipStreamSynchronize(st));
+    for (int pos0 = 0; pos0 < npos; pos0 += 16) {
+        const int Mper = std::min(16, npos - pos0);
+        hipLaunchKernelGGL(k_score_fill, dim3((B + 63) / 64), dim3(64), 0, st, ctx->kvlen, B, pos0);
+        WM_HIP(hipGetLastError());
+        if (int rc = wm_dec_replay_layers(ctx, 0, B, Mper, ctx->cfg.dec_layers, nullptr, nullptr)) return rc;
+        // EVERY tile folds its tokens into the streams' timestamp state (k_score_build resets it at pos0 == 0 and carries it in sst): a long
+        // prompt's tokens — prompt_ids may hold timestamps of previous text — reach the records of the later tiles as they reach the decode's
+        hipLaunchKernelGGL(k_score_build, dim3((B + 63) / 64), dim3(64), 0, st, ctx->ids, Tids, sc->lens, sc->npr, B, pos0, Mper, g, ts, sot, ns_id,
+                           Tmax, B * Tmax, sc->sst, sc->desc, sc->rec);
+        WM_HIP(hipGetLastError());
+        // logits only for a tile that holds a scored row (a long prompt's leading tiles are wanted for their K/V and their fold alone)
+        bool need = ns_id >= 0 && sot >= pos0 && sot < pos0 + Mper;
+        for (int b = 0; b < B && !need; ++b) need = std::max(n_prompt[b], pos0 + 1) < std::min(lens[b], pos0 + Mper + 1);
+        if (!need) continue;
+        if (int rc = wm_dec_stage_final(ctx, 0, B, Mper, 0, 0)) return rc;
+        if (int rc = wm_dec_stage_heads(ctx, B * Mper, 1, 0, 0)) return rc;
+        if (int rc = score_launch(ctx, g, ts, B * Mper + B)) return rc;
+    }
+    std::vector<float> ns(B, 0.f);
+    WM_HIP(hipMemcpyAsync(logprobs, sc->out, (size_t)B * Tmax * sizeof(float), hipMemcpyDeviceToHost, st));
+    WM_HIP(hipMemcpyAsync(ns.data(), sc->out + (size_t)B * Tmax, B * sizeof(float), hipMemcpyDeviceToHost, st));
+    WM_HIP(hipStreamSynchronize(st));
+    if (no_speech_prob) for (int b = 0; b < B; ++b) no_speech_prob[b] = ns_id >= 0 ? (float)std::exp((double)ns[b]) : 0.f;
+    return WM_OK;
+}
+
+extern "C" int wm_score_tokens(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* tsp, const wm_score_params* sp, int B,
+                               const int32_t* tokens, int Tmax, const int32_t* lens, const int32_t* n_prompt, float* logprobs,
+                               float* no_speech_prob, float* ms)
+{
+    if (!ctx) return WM_ERR_ARG;
+    if (!gp || !tokens || !lens || !n_prompt || !logprobs || B < 1 || Tmax < 1) { ctx->err = "wm_score_tokens: bad arguments"; return WM_ERR_ARG; }
+    if (ctx->Benc < 1) { ctx->err = "wm_score_tokens: call wm_encode first"; return WM_ERR_STATE; }
+    if (B > ctx->Benc || B * 16 > ctx->Rcap) { ctx->err = "wm_score_tokens: more streams than the last wm_encode"; return WM_ERR_ARG; }
+    const int ns_id = (sp && no_speech_prob) ? sp->no_speech_token_id : -1;
+    const int sot = (sp && sp->sot_index >= 0) ? sp->sot_index : 0;
+    if (ns_id >= ctx->V) { ctx->err = "wm_score_tokens: no_speech_token_id outside the vocabulary"; return WM_ERR_ARG; }
+    for (int b = 0; b < B; ++b) {
+        if (lens[b] < 1 || lens[b] > ctx->Tmax || lens[b] > Tmax) { ctx->err = "wm_score_tokens: lens must be in [1, min(Tmax, n_tgt)]"; return WM_ERR_ARG; }
+        if (n_prompt[b] < 1 || n_prompt[b] > lens[b]) { ctx->err = "wm_score_tokens: n_prompt must be in [1, lens]"; return WM_ERR_ARG; }
+        if (ns_id >= 0 && sot >= n_prompt[b]) { ctx->err = "wm_score_tokens: sot_index must lie inside the prompt"; return WM_ERR_ARG; }
+        for (int t = 0; t < lens[b]; ++t)
+            if (tokens[(size_t)b * Tmax + t] < 0 || tokens[(size_t)b * Tmax + t] >= ctx->V) {
+                ctx->err = "wm_score_tokens: target outside the vocabulary (stream " + std::to_string(b) + ", position " + std::to_string(t) + ")";
+                return WM_ERR_ARG;
+            }
+    }
+    WM_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    GenDev g{}; TsDev ts{};
+    if (int rc = score_setup(ctx, gp, tsp, "wm_score_tokens", &g, &ts)) return rc;
+    // the replay overwrites the decode state (ids, kvlen, self K/V, the processors' tables): begin again afterwards.  The decode's scalars
+    // come back, so that a following wm_decode_begin with the same parameters still finds its captured graph.
+    const GenDev g_keep = ctx->gp; const TsDev ts_keep = ctx->ts;
+    ctx->gp = g; ctx->ts = ts;
+    ctx->began = false; ctx->use_done = false; ctx->host_carry = false; ctx->dev_carry = false; ctx->step_flow = false;
+    for (size_t i = 0; i < (size_t)B * Tmax; ++i) logprobs[i] = 0.f;
+    hipError_t e = hipEventRecord(ctx->ev0, st);
+    int rc = e == hipSuccess ? score_tokens_run(ctx, g, ts, ns_id, sot, B, tokens, Tmax, lens, n_prompt, logprobs, no_speech_prob) : WM_ERR_HIP;
+    if (e != hipSuccess) ctx->err = std::string("wm_score_tokens: ") + hipGetErrorString(e);
+    ctx->gp = g_keep; ctx->ts = ts_keep;
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    WM_HIP(hipEventRecord(ctx->ev1, st));
+    WM_HIP(hipEventSynchronize(ctx->ev1));
+    if (ms) WM_HIP(hipEventElapsedTime(ms, ctx->ev0, ctx->ev1));
+    return WM_OK;
+}
+
+extern "C" int wm_score_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* tsp, int R, const float* logits,
+                             const int32_t* prefixes, int Tmax, const int32_t* lens, const int32_t* targets, float* out_logprob)
+{
+    if (!ctx) return WM_ERR_ARG;
+    if (!gp || R < 1 || !logits || !prefixes || Tmax < 1 || !lens || !targets || !out_logprob) { ctx->err = "wm_score_rows: bad arguments"; return WM_ERR_ARG; }
+    for (int r = 0; r < R; ++r) {
+        if (lens[r] < 1 || lens[r] > Tmax || lens[r] > ctx->Tmax) { ctx->err = "wm_score_rows: lens must be in [1, min(Tmax, n_tgt)]"; return WM_ERR_ARG; }
+        if (targets[r] < 0 || targets[r] >= ctx->V) { ctx->err = "wm_score_rows: target outside the vocabulary (row " + std::to_string(r) + ")"; return WM_ERR_ARG; }
+    }
+    WM_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    GenDev g{}; TsDev ts{};
+    if (int rc = score_setup(ctx, gp, tsp, "wm_score_rows", &g, &ts)) return rc;
+    ctx->began = false;
+    const int G = ctx->Rcap;                   // rows per group: what the logits scratch holds
+    if (int rc = score_reserve(ctx, (size_t)G, (size_t)G, 0, (size_t)G * Tmax + 2 * G)) return rc;
+    wm_score_state* sc = ctx->score;
+    for (int r0 = 0; r0 < R; r0 += G) {
+        const int n = std::min(G, R - r0);
+        int* pre = sc->ibuf; int* len = pre + (size_t)G * Tmax; int* tgt = len + G;
+        WM_HIP(hipMemcpyAsync(pre, prefixes + (size_t)r0 * Tmax, (size_t)n * Tmax * sizeof(int), hipMemcpyHostToDevice, st));
+        WM_HIP(hipMemcpyAsync(len, lens + r0, n * sizeof(int), hipMemcpyHostToDevice, st));
+        WM_HIP(hipMemcpyAsync(tgt, targets + r0, n * sizeof(int), hipMemcpyHostToDevice, st));
+        WM_HIP(hipMemcpy2DAsync(ctx->logits, (size_t)ctx->Vpad * sizeof(float), logits + (size_t)r0 * ctx->V, (size_t)ctx->V * sizeof(float),
+                                (size_t)ctx->V * sizeof(float), n, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_score_tap_build, dim3((n + 63) / 64), dim3(64), 0, st, pre, len, tgt, n, Tmax, g, ts, sc->desc, sc->rec);
+        WM_HIP(hipGetLastError());
+        if (int rc = score_launch(ctx, g, ts, n)) return rc;
+        WM_HIP(hipMemcpyAsync(out_logprob + r0, sc->out, n * sizeof(float), hipMemcpyDeviceToHost, st));
+        WM_HIP(hipStreamSynchronize(st));
+    }
+    return WM_OK;
+}

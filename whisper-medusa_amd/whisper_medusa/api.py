@@ -26,6 +26,7 @@ from .engine import Engine
 from . import weights as _weights
 from . import synth as _synth
 from . import timestamps as _timestamps
+from . import scores as _scores
 
 
 class EngineKVCache:
@@ -486,9 +487,13 @@ class WhisperMedusaModel:
                  attention_mask: Optional[torch.Tensor] = None, time_precision: float = 0.02,
                  time_precision_features: float = 0.01, return_token_timestamps: Optional[bool] = None,
                  return_segments: bool = False, return_dict_in_generate: Optional[bool] = None,
-                 force_unique_generate_call: Optional[bool] = None, **kwargs):
+                 force_unique_generate_call: Optional[bool] = None, return_token_logprobs: Optional[bool] = None, **kwargs):
         """Same signature as the reference (model.py:1419-1449).  Returns ``LongTensor [B, T]`` holding the
-        prompt + generated ids, right-padded with ``pad_token_id`` (model.py:1747-1762)."""
+        prompt + generated ids, right-padded with ``pad_token_id`` (model.py:1747-1762).
+
+        ``return_token_logprobs=True`` returns a GenerateEncoderDecoderOutput with ``token_logprobs [B, T]``, ``avg_logprob``,
+        ``compression_ratio`` and ``no_speech_prob``; ``no_speech_threshold`` / ``logprob_threshold`` / ``compression_ratio_threshold`` run the
+        same scoring pass and gate on it (``skipped``, ``needs_fallback`` in the dict outputs and in ``self.last_scores``)."""
         if generation_config is not None:
             # HF semantics (model.py:936-943 -> GenerationMixin._prepare_generation_config): a copy of the passed config, updated by every
             # explicit argument of this call — an explicit argument wins, the config fills what the call leaves open.  Only the fields this
@@ -500,6 +505,8 @@ class WhisperMedusaModel:
             return_timestamps = pick("return_timestamps", return_timestamps)
             task, language = pick("task", task), pick("language", language)
             no_speech_threshold = pick("no_speech_threshold", no_speech_threshold)
+            logprob_threshold = pick("logprob_threshold", logprob_threshold)
+            compression_ratio_threshold = pick("compression_ratio_threshold", compression_ratio_threshold)
             return_token_timestamps = pick("return_token_timestamps", return_token_timestamps)
             return_dict_in_generate = pick("return_dict_in_generate", return_dict_in_generate)
             for name in ("max_new_tokens", "max_length", "num_beams", "suppress_tokens", "begin_suppress_tokens",
@@ -538,8 +545,24 @@ class WhisperMedusaModel:
                 raise NotImplementedError("return_timestamps is not supported together with logits_processor= / stopping_criteria= "
                                           "(the host processor path)")
             return_timestamps = True
-        if no_speech_threshold is not None:
-            raise NotImplementedError("no_speech_detection is not supported with medusa for now")  # model.py:1201-1205
+        # model.py:1201-1205 raises for no_speech_threshold and ignores the other two; the engine scores the final ids in a teacher-forced
+        # replay whenever one of these arguments is given — none of them: no new launch
+        sc_req = None
+        if return_token_logprobs or no_speech_threshold is not None or logprob_threshold is not None or compression_ratio_threshold is not None:
+            if no_speech_threshold is not None and self.config.no_speech_token_id is None:
+                raise NotImplementedError("no_speech_threshold needs a <|nospeech|> token (no_timestamps_token_id - 1) inside the vocabulary")
+            if no_speech_threshold is not None and self._engine is None:
+                # the reference's refusal (model.py:1201-1205) stays where nothing can score the clip: the detection is the engine's scoring pass
+                raise NotImplementedError("no_speech_detection is not supported with medusa without the HIP engine's scoring pass: "
+                                          "call model.to('cuda') first (no_speech_threshold)")
+            if logits_processor and any(type(p_).__name__ not in _LOWERABLE_PROCESSORS for p_ in logits_processor):
+                raise NotImplementedError("token log-probabilities / quality gating are not supported on the host processor path (logits_processor=)")
+            sc_req = dict(want=bool(return_token_logprobs), no_speech_threshold=no_speech_threshold, logprob_threshold=logprob_threshold,
+                          compression_ratio_threshold=compression_ratio_threshold)
+        sc_side = kwargs.pop("_sc_req", None)       # called by the language / long-form wrappers: plain tensor back, scores in self._last_sc
+        if sc_side is not None:
+            sc_req = sc_side
+        sc_side = sc_side is not None
         if kwargs.get("num_beams", 1) not in (None, 1):
             raise Exception("Beam search is not supported with medusa for now")                     # model.py:1153-1156
         if prefix_allowed_tokens_fn:
@@ -564,7 +587,8 @@ class WhisperMedusaModel:
             return self._generate_longform(input_features, dict(kwargs, language=language, task=task, temperature=temperature,
                                                                 prompt_ids=prompt_ids, logits_processor=logits_processor,
                                                                 stopping_criteria=stopping_criteria,
-                                                                return_timestamps=bool(return_timestamps), _tt_req=tt_req,
+                                                                return_timestamps=bool(return_timestamps), _tt_req=tt_req, _sc_req=sc_req,
+                                                                return_dict_in_generate=return_dict_in_generate,
                                                                 return_segments=return_segments, time_precision=time_precision))
         if language is None and self.config.is_multilingual and kwargs.get("detect_language", True) and input_features.shape[0] >= 1 \
                 and not kwargs.get("_language_resolved"):
@@ -572,6 +596,7 @@ class WhisperMedusaModel:
                                                                           return_dict_in_generate=return_dict_in_generate,
                                                                           return_segments=return_segments, logits_processor=logits_processor,
                                                                           stopping_criteria=stopping_criteria, _tt_req=tt_req, _tt_outer=tt_side,
+                                                                          _sc_req=sc_req, _sc_outer=sc_side,
                                                                           return_timestamps=bool(return_timestamps), time_precision=time_precision))
         B = input_features.shape[0]
         if B > self._max_batch:
@@ -598,10 +623,14 @@ class WhisperMedusaModel:
             tsf = None
             if tt_req is not None:
                 tsf = lambda e, sq, lo: self._token_ts_run(e, sq, gp, tt_req, lo)       # noqa: E731
-            seqs = pool.run(feats, gp, **({"token_ts": tsf} if tsf is not None else {}))      # F1..F14 per micro-batch, concurrently
+            extra = {"token_ts": tsf} if tsf is not None else {}
+            if sc_req is not None:
+                extra["score"] = lambda e, sq, lo: self._score_run(e, sq, gp, sc_req)    # noqa: E731
+            seqs = pool.run(feats, gp, **extra)      # F1..F14 per micro-batch, concurrently
             self.last_stats = pool.last_stats
             tt = self._token_ts_tensor(pool.last_token_timestamps, seqs, gp) if tt_req is not None else None
-            return self._outputs(seqs, gp, return_dict_in_generate, return_segments, tt, tt_side)
+            sc = self._score_pack(pool.last_scores, seqs, gp, sc_req) if sc_req is not None else None
+            return self._outputs(seqs, gp, return_dict_in_generate, return_segments, tt, tt_side, sc, sc_side)
         eng = self.engine
         streamer = kwargs.get("streamer")
         host_crit = getattr(gp, "_host_criteria", None)
@@ -610,6 +639,8 @@ class WhisperMedusaModel:
         if getattr(gp, "_host_processors", None):
             if tt_req is not None:
                 raise NotImplementedError("return_token_timestamps is not supported on the host processor path (logits_processor=)")
+            if sc_req is not None:
+                raise NotImplementedError("token log-probabilities / quality gating are not supported on the host processor path (logits_processor=)")
             seqs = self._decode_host_processors(feats, gp, streamer, host_crit)
             return self._outputs(seqs, gp, return_dict_in_generate, return_segments)
         # language detection just encoded exactly these clips on this engine (one language group, same order): its encoder output and
@@ -654,12 +685,64 @@ class WhisperMedusaModel:
         else:
             seqs = eng.decode(gp, B)                                        # F3..F14
         self.last_stats = eng.stats()
+        sc = None
+        if sc_req is not None:
+            # scoring first: a skipped clip's row becomes prompt + EOS before anything else looks at it (two replays when token timestamps
+            # are asked for in the same call)
+            seqs, infos, ms = self._score_run(eng, seqs, gp, sc_req)
+            self.last_stats["ms_token_logprobs"] = ms
+            sc = self._score_pack(infos, seqs, gp, sc_req)
         tt = None
         if tt_req is not None:
             rows, ms = self._token_ts_run(eng, seqs, gp, tt_req, 0)
             self.last_stats["ms_token_timestamps"] = ms
             tt = self._token_ts_tensor(rows, seqs, gp)
-        return self._outputs(seqs, gp, return_dict_in_generate, return_segments, tt, tt_side)
+        return self._outputs(seqs, gp, return_dict_in_generate, return_segments, tt, tt_side, sc, sc_side)
+
+    # ---- token log-probabilities, no-speech probability, quality gating (engine: csrc/wm_score.hip) --------------------------
+    def _score_run(self, eng, seqs, gp: GenParams, req: dict):
+        """Scores of the streams ``seqs`` an engine context has just decoded -> (seqs with every skipped stream replaced by prompt + EOS,
+        one info dict per stream, ms)."""
+        cfg = self.config
+        own = [self._own_end(s, gp) for s in seqs]
+        P = len(gp.prompt)
+        ns_id = cfg.no_speech_token_id
+        # <|startoftranscript|> sits behind the prompt_ids: index len(prompt_ids) (HF's WhisperNoSpeechDetection reads index 0 there)
+        lp, nsp, ms = eng.score_tokens(own, P, gp, ns_id, P - gp.begin_index if gp.begin_suppress_index is not None else 0)
+        infos, out = [], []
+        for b, s in enumerate(own):
+            row = lp[b, : len(s)].copy()
+            avg = _scores.avg_logprob(row, P, len(s))
+            cr = _scores.compression_ratio(s[P:], cfg.vocab_size)
+            ns = None if nsp is None else float(nsp[b])
+            fb, skip = _scores.gate(ns, avg, cr, req["no_speech_threshold"], req["logprob_threshold"], req["compression_ratio_threshold"])
+            if skip:
+                s = list(gp.prompt) + [gp.eos_token_id]
+                row = np.zeros(len(s), dtype=np.float32)
+            infos.append(dict(token_logprobs=row, avg_logprob=avg, compression_ratio=cr, no_speech_prob=ns, skipped=skip, needs_fallback=fb))
+            out.append(s if skip else seqs[b])
+        return out, infos, ms
+
+    def _score_pack(self, infos, seqs, gp: GenParams, req: dict) -> dict:
+        """Per-stream infos -> the tensors of the dict output, next to _pad's ids (token_logprobs is 0 after a stream's end)."""
+        T = max(len(self._own_end(s, gp)) for s in seqs)
+        t = torch.zeros(len(infos), T, dtype=torch.float32)
+        for i, f in enumerate(infos):
+            r = np.asarray(f["token_logprobs"], dtype=np.float32)
+            t[i, : len(r)] = torch.from_numpy(r)
+        sc = dict(token_logprobs=t.to(self.device),
+                  avg_logprob=torch.tensor([f["avg_logprob"] for f in infos], dtype=torch.float32, device=self.device),
+                  compression_ratio=torch.tensor([f["compression_ratio"] for f in infos], dtype=torch.float32, device=self.device),
+                  # the streams' own ends (EOS included): with pad == eos a padded row alone cannot tell a stream's EOS from its padding
+                  lengths=torch.tensor([len(self._own_end(s, gp)) for s in seqs], dtype=torch.long, device=self.device))
+        if all(f["no_speech_prob"] is not None for f in infos):
+            sc["no_speech_prob"] = torch.tensor([f["no_speech_prob"] for f in infos], dtype=torch.float32, device=self.device)
+        if req["no_speech_threshold"] is not None:
+            sc["skipped"] = torch.tensor([f["skipped"] for f in infos], dtype=torch.bool, device=self.device)
+        if req["logprob_threshold"] is not None or req["compression_ratio_threshold"] is not None:
+            sc["needs_fallback"] = torch.tensor([f["needs_fallback"] for f in infos], dtype=torch.bool, device=self.device)
+        sc["_want"] = req["want"]
+        return sc
 
     # ---- token-level timestamps (HF _extract_token_timestamps; engine: csrc/wm_align.hip) ----------------------------------------------
     def _token_ts_request(self, alignment_heads, generation_config, num_frames, logits_processor, time_precision) -> dict:
@@ -805,20 +888,44 @@ class WhisperMedusaModel:
         self.last_stats = dict(iterations=n_iter, iterations_launched=n_iter, tokens_emitted=n_tok, accept_hist=hist, host_processors=len(procs))
         return seqs
 
-    def _outputs(self, seqs, gp, return_dict_in_generate, return_segments, token_timestamps=None, tt_side=False):
+    def _outputs(self, seqs, gp, return_dict_in_generate, return_segments, token_timestamps=None, tt_side=False, scores=None, sc_side=False):
         """Default: the padded LongTensor.  ``return_dict_in_generate`` / ``return_segments``: the reference's dict form
         ``{"sequences": ..., ["segments": ...]}`` (model.py:1747-1779; one segment per clip, short-form only)."""
         if tt_side:          # an inner call of the language / long-form wrappers: they wrap the outputs themselves
             self._last_tt = token_timestamps
             token_timestamps = None
+        if sc_side:
+            self._last_sc = scores
+            scores = None
         return self._wrap_outputs(self._pad(seqs, gp), [len(gp.prompt)] * len(seqs), gp.pad_token_id, gp.eos_token_id,
                                   return_dict_in_generate, return_segments, timestamps=gp.timestamps,
-                                  time_precision=getattr(gp, "_time_precision", 0.02), token_timestamps=token_timestamps)
+                                  time_precision=getattr(gp, "_time_precision", 0.02), token_timestamps=token_timestamps, scores=scores)
 
     def _wrap_outputs(self, t, prompt_lens, pad, eos, return_dict_in_generate, return_segments, timestamps=False, time_precision=0.02,
-                      token_timestamps=None):
+                      token_timestamps=None, scores=None):
         """``return_dict_in_generate``: a GenerateEncoderDecoderOutput (model.py:812-823, :1715-1742); ``return_segments`` alone:
         the dict {"sequences", "segments"} of model.py:1764-1779 (one segment per clip, short-form only)."""
+        if scores is not None:
+            # the scoring pass ran: its fields go into every dict form of the output and stay in self.last_scores; return_token_logprobs forces
+            # the dict form (as HF does for return_token_timestamps), thresholds alone keep the shape the caller asked for
+            want = scores.get("_want", False)
+            fields = {k: v for k, v in scores.items() if not k.startswith("_")}
+            self.last_scores = fields
+            out = self._wrap_outputs(t, prompt_lens, pad, eos, return_dict_in_generate or (want and not return_segments) or token_timestamps is not None,
+                                     return_segments, timestamps, time_precision, token_timestamps)
+            if not isinstance(out, dict):
+                return out
+            if "segments" not in out and return_segments:
+                out["segments"] = self._wrap_outputs(t, prompt_lens, pad, eos, False, True, timestamps, time_precision)["segments"]
+            if "segments" in out:
+                for i, P in enumerate(prompt_lens):
+                    o = P
+                    for sg in out["segments"][i]:
+                        n = int(sg["tokens"].numel())
+                        sg["token_logprobs"] = fields["token_logprobs"][i, o: o + n]
+                        o += n
+            out.update(fields)
+            return out
         if token_timestamps is not None:
             # HF forces return_dict_in_generate with return_token_timestamps: sequences + token_timestamps [B, T]; with return_segments every
             # segment also carries the slice of its own tokens (HF's long-form output shape)
@@ -897,22 +1004,30 @@ class WhisperMedusaModel:
         rows: List[Optional[torch.Tensor]] = [None] * len(langs)
         plens = [0] * len(langs)
         req, outer = kw.pop("_tt_req", None), kw.pop("_tt_outer", False)
+        sreq, souter = kw.pop("_sc_req", None), kw.pop("_sc_outer", False)
         tts: List[Optional[torch.Tensor]] = [None] * len(langs)
-        ms_tt = 0.0
+        scs: List[Optional[dict]] = [None] * len(langs)
+        ms_tt = ms_sc = 0.0
         for l, idx in groups.items():
             # one group = every clip in its original order: the engine still holds the encoder pass detect_language() ran
             reuse = {"_encoded_batch": len(langs)} if len(groups) == 1 else {}
             if req is not None:         # per-stream num_frames follow their clips into the group
                 nf = req["num_frames"]
                 reuse["_tt_req"] = dict(req, num_frames=[nf[i] for i in idx] if isinstance(nf, list) else nf)
+            if sreq is not None:
+                reuse["_sc_req"] = sreq
             out = self.generate(input_features[idx], language=l, _language_resolved=True, **reuse, **kw)
             if req is not None:
                 ms_tt += self.last_stats.get("ms_token_timestamps", 0.0)
+            if sreq is not None:
+                ms_sc += self.last_stats.get("ms_token_logprobs", 0.0)
             for j, i in enumerate(idx):
                 rows[i] = out[j]
                 plens[i] = len(self._last_prompt)
                 if req is not None:
                     tts[i] = self._last_tt[j]
+                if sreq is not None:
+                    scs[i] = {k: v[j] for k, v in self._last_sc.items() if not k.startswith("_")}
         T = max(r.numel() for r in rows)
         t = torch.full((len(rows), T), self.config.pad_token_id, dtype=torch.long, device=self.device)
         for i, r in enumerate(rows):
@@ -928,8 +1043,23 @@ class WhisperMedusaModel:
             if outer:
                 self._last_tt = tt
                 tt = None
+        sc = None
+        if sreq is not None:
+            # per-clip fields of the groups back in the clips' order; token_logprobs rows are 0 after a stream's end
+            sc = {"_want": sreq["want"]}
+            for k in scs[0]:
+                if k == "token_logprobs":
+                    sc[k] = torch.zeros(len(rows), T, dtype=torch.float32, device=self.device)
+                    for i, f in enumerate(scs):
+                        sc[k][i, : f[k].numel()] = f[k]
+                else:
+                    sc[k] = torch.stack([f[k] for f in scs])
+            self.last_stats["ms_token_logprobs"] = ms_sc
+            if souter:
+                self._last_sc = sc
+                sc = None
         return self._wrap_outputs(t, plens, self.config.pad_token_id, self.config.eos_token_id, rdg, rseg, timestamps=rts,
-                                  time_precision=tprec, token_timestamps=tt)
+                                  time_precision=tprec, token_timestamps=tt, scores=sc)
 
     def _generate_longform(self, input_features, kw):
         """`chunk_longform=True`: clips longer than 30 s (the reference raises, model.py:1213-1214) are cut into 30 s windows,
@@ -937,9 +1067,12 @@ class WhisperMedusaModel:
         each clip's windows are concatenated: prompt once, then the generated ids of every window without its EOS / padding.
         No conditioning on the previous window (unsupported with Medusa in the reference as well).  `return_timestamps=True`: every
         window keeps its timestamp tokens (relative to the window); `return_segments=True` then gives each window's segments offset by
-        the window's start, j * n_mel_frames * 10 ms (the windows stay fixed: HF's sequential seek to the last timestamp is not done)."""
+        the window's start, j * n_mel_frames * 10 ms (the windows stay fixed: HF's sequential seek to the last timestamp is not done).
+        With the scoring arguments every window is scored and gated on its own: a skipped window (no_speech_threshold) contributes no ids, no
+        segments and no token timestamps to its clip and leaves the offsets of the following windows where they are."""
         cfg = self.config
         kw.pop("chunk_longform", None)
+        rdg, sreq = kw.pop("return_dict_in_generate", None), kw.pop("_sc_req", None)
         rseg, tprec = kw.pop("return_segments", False), kw.get("time_precision", 0.02)
         rts = bool(kw.get("return_timestamps"))
         F = cfg.n_mel_frames
@@ -966,54 +1099,94 @@ class WhisperMedusaModel:
         if req is not None and req["num_frames"] is not None:
             raise NotImplementedError("num_frames= is not supported together with chunk_longform=True (the windows are fixed)")
         wtt = [None] * (B * n)
-        ms_tt = 0.0
+        wsc: List[Optional[dict]] = [None] * (B * n)
+        ms_tt = ms_sc = 0.0
         for l in sorted(set(langs), key=lambda v: (v is None, v or "")):
             clips = [b for b in range(B) if langs[b] == l]
             widx = [b * n + j for b in clips for j in range(n)]
-            o = self.generate(win[widx], language=l, **kw, **({"_tt_req": req} if req is not None else {}))
+            o = self.generate(win[widx], language=l, **kw, **({"_tt_req": req} if req is not None else {}),
+                              **({"_sc_req": sreq} if sreq is not None else {}))
             if req is not None:
                 ms_tt += self.last_stats.get("ms_token_timestamps", 0.0)
+            if sreq is not None:
+                ms_sc += self.last_stats.get("ms_token_logprobs", 0.0)
             for q, wi in enumerate(widx):
                 rows[wi] = o[q]
                 if req is not None:
                     wtt[wi] = self._last_tt[q].cpu()
+                if sreq is not None:
+                    wsc[wi] = {k: v[q].cpu() for k, v in self._last_sc.items() if not k.startswith("_")}
             for b in clips:
                 prompts[b] = list(self._last_prompt)
         eos, pad = cfg.eos_token_id, cfg.pad_token_id
-        seqs, all_tt = [], []
+        seqs, all_tt, all_lp = [], [], []
         segs = [[] for _ in range(B)]
+        skipped = [[bool(wsc[b * n + j]["skipped"]) if sreq is not None and "skipped" in wsc[b * n + j] else False for j in range(n)] for b in range(B)]
         for b in range(B):
             if rts and rseg:
                 for j in range(n):
+                    if skipped[b][j]:
+                        continue
                     segs[b] += _timestamps.row_segments(rows[b * n + j].tolist(), len(prompts[b]), eos, cfg.timestamp_begin, F, tprec,
                                                         time_offset=j * F * 0.01, result=rows[b * n + j])
             ids = list(prompts[b])
             P = len(ids)
             tts = [0.0] * P
+            lps, last_eos_lp = [0.0] * P, 0.0
             for j in range(n):
+                if skipped[b][j]:
+                    continue
                 row = rows[b * n + j][P:].tolist()
                 for q, t in enumerate(row):
                     if t == eos or t == pad:
+                        if sreq is not None:      # the clip's one EOS takes the score of the last kept window's
+                            last_eos_lp = float(wsc[b * n + j]["token_logprobs"][P + q])
                         break
                     ids.append(t)
+                    if sreq is not None:
+                        lps.append(float(wsc[b * n + j]["token_logprobs"][P + q]))
                     if req is not None:       # the window's own value, offset by the window's start (float32 sum, as the tensor holds it)
                         tts.append(float(wtt[b * n + j][P + q] + torch.tensor(j * F * 0.01, dtype=torch.float32)))
             seqs.append(ids + [eos])
             all_tt.append(tts + [tts[-1]])
-            if req is not None and rts and rseg:      # each segment's slice of its own window's values, offset like its start / end
+            all_lp.append(lps + [last_eos_lp])
+            if (req is not None or sreq is not None) and rts and rseg:      # each segment's slice of its own window's values (times offset like its start / end)
                 k = 0
                 for j in range(n):
+                    if skipped[b][j]:
+                        continue
                     o = P
                     nseg = len(_timestamps.row_segments(rows[b * n + j].tolist(), P, eos, cfg.timestamp_begin, F, tprec))
                     for sg in segs[b][k: k + nseg]:
                         m = int(sg["tokens"].numel())
-                        sg["token_timestamps"] = wtt[b * n + j][o: o + m] + torch.tensor(j * F * 0.01, dtype=torch.float32)
+                        if req is not None:
+                            sg["token_timestamps"] = wtt[b * n + j][o: o + m] + torch.tensor(j * F * 0.01, dtype=torch.float32)
+                        if sreq is not None:
+                            sg["token_logprobs"] = wsc[b * n + j]["token_logprobs"][o: o + m]
                         o += m
                     k += nseg
         Tm = max(len(s_) for s_ in seqs)
         t = torch.full((B, Tm), pad, dtype=torch.long, device=self.device)
         for i, s_ in enumerate(seqs):
             t[i, : len(s_)] = torch.tensor(s_, dtype=torch.long)
+        fields = None
+        if sreq is not None:
+            # per clip: the kept tokens' scores, their average and the compression ratio of the assembled ids; per window [B, n]: the gate's inputs and verdicts
+            lp = torch.zeros(B, Tm, dtype=torch.float32)
+            for i, r in enumerate(all_lp):
+                lp[i, : len(r)] = torch.tensor(r, dtype=torch.float32)
+            Pb = [len(p_) for p_ in prompts]
+            fields = dict(token_logprobs=lp.to(self.device),
+                          avg_logprob=torch.tensor([_scores.avg_logprob(all_lp[i], Pb[i], len(seqs[i])) for i in range(B)], dtype=torch.float32, device=self.device),
+                          compression_ratio=torch.tensor([_scores.compression_ratio(seqs[i][Pb[i]:], cfg.vocab_size) for i in range(B)],
+                                                         dtype=torch.float32, device=self.device),
+                          lengths=torch.tensor([len(s_) for s_ in seqs], dtype=torch.long, device=self.device))
+            for k in ("no_speech_prob", "skipped", "needs_fallback"):
+                if k in wsc[0]:
+                    fields[k] = torch.stack([wsc[i][k] for i in range(B * n)]).view(B, n).to(self.device)
+            fields["window_avg_logprob"] = torch.stack([wsc[i]["avg_logprob"] for i in range(B * n)]).view(B, n).to(self.device)
+            self.last_scores = fields
+            self.last_stats["ms_token_logprobs"] = ms_sc
         if req is not None:
             tt = torch.zeros(B, Tm, dtype=torch.float32)
             for i, r in enumerate(all_tt):
@@ -1023,9 +1196,16 @@ class WhisperMedusaModel:
             out = GenerateEncoderDecoderOutput(t, token_timestamps=tt.to(self.device))
             if rts and rseg:
                 out["segments"] = segs
+            if fields is not None:
+                out.update(fields)
+            return out
+        if fields is not None and (sreq["want"] or rdg):
+            out = GenerateEncoderDecoderOutput(t, **fields)
+            if rts and rseg:
+                out["segments"] = segs
             return out
         if rts and rseg:
-            return {"sequences": t, "segments": segs}
+            return dict({"sequences": t, "segments": segs}, **(fields or {}))
         return t
 
     @torch.no_grad()
@@ -1041,16 +1221,36 @@ class WhisperMedusaModel:
             return self.generate(input_features, **kw)
         rank, world = td.get_rank(), td.get_world_size()
         mine = _dist.shard_streams(B, rank, world)
-        local = []
+        local, local_sc = [], []
+        gc = kw.get("generation_config")        # (the thresholds may come through a passed generation_config, as in generate())
+        scoring = any(kw.get(k) is not None or getattr(gc, k, None) is not None
+                      for k in ("no_speech_threshold", "logprob_threshold", "compression_ratio_threshold")) or bool(kw.get("return_token_logprobs"))
         if mine:
             out = self.generate(input_features[mine], **kw)
-            local = [(s_, out[j].tolist()) for j, s_ in enumerate(mine)]
+            rows = out["sequences"] if isinstance(out, dict) else out
+            local = [(s_, rows[j].tolist()) for j, s_ in enumerate(mine)]
+            if scoring:     # every rank's per-stream score fields travel like its ids (ragged Python lists)
+                local_sc = [(s_, {k: v[j].tolist() for k, v in self.last_scores.items()}) for j, s_ in enumerate(mine)]
         seqs = _dist.gather_token_lists(local)
         pad = self.config.pad_token_id
         T = max(len(s_) for s_ in seqs)
         t = torch.full((B, T), pad, dtype=torch.long, device=self.device)
         for i, s_ in enumerate(seqs):
             t[i, : len(s_)] = torch.tensor(s_, dtype=torch.long)
+        if not scoring:
+            return t
+        infos = _dist.gather_token_lists(local_sc)
+        fields = {}
+        for k in infos[0]:
+            if k == "token_logprobs":
+                fields[k] = torch.zeros(B, T, dtype=torch.float32, device=self.device)
+                for i, f in enumerate(infos):
+                    fields[k][i, : len(f[k])] = torch.tensor(f[k], dtype=torch.float32)
+            else:
+                fields[k] = torch.tensor([f[k] for f in infos], device=self.device)
+        self.last_scores = fields
+        if kw.get("return_token_logprobs") or kw.get("return_dict_in_generate") or getattr(gc, "return_dict_in_generate", None):
+            return GenerateEncoderDecoderOutput(t, **fields)
         return t
 
     def generate_from_wav(self, wav, **kw) -> torch.Tensor:

@@ -225,6 +225,13 @@ class MedusaConfig:
                 and 0 <= self.decoder_start_token_id < tb)
 
     @property
+    def no_speech_token_id(self) -> Optional[int]:
+        """<|nospeech|> by HF's default rule (WhisperGenerationMixin: no_timestamps_token_id - 1 when the generation config names none);
+        None when that is no id of the vocabulary."""
+        t = int(self.no_timestamps_token_id) - 1
+        return t if 0 <= t < self.vocab_size else None
+
+    @property
     def is_block(self) -> bool:
         return self.medusa_heads_type == HEADS_BLOCK
 

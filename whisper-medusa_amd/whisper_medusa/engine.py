@@ -53,6 +53,10 @@ class WmAlignParams(C.Structure):
     _fields_ = [("heads", C.POINTER(C.c_int32)), ("n_heads", C.c_int32), ("median_filter_width", C.c_int32), ("time_precision", C.c_float)]
 
 
+class WmScoreParams(C.Structure):
+    _fields_ = [("no_speech_token_id", C.c_int32), ("sot_index", C.c_int32)]
+
+
 class WmStats(C.Structure):
     _fields_ = [("iterations", C.c_int64), ("iterations_launched", C.c_int64), ("tokens_emitted", C.c_int64),
                 ("accept_hist", C.c_int64 * 16),
@@ -64,7 +68,8 @@ EXPORTS = ["wm_create", "wm_destroy", "wm_last_error", "wm_abi_version", "wm_bui
            "wm_decode_begin", "wm_decode_run", "wm_get_tokens", "wm_get_stats", "wm_sync",
            "wm_get_encoder_output", "wm_forward_logits", "wm_get_cross_kv", "wm_profile_kernel",
            "wm_decode_begin_ts", "wm_select_rows",
-           "wm_token_timestamps", "wm_get_align_probs", "wm_get_align_matrix", "wm_dtw"]
+           "wm_token_timestamps", "wm_get_align_probs", "wm_get_align_matrix", "wm_dtw",
+           "wm_score_tokens", "wm_score_rows"]
 
 _lib = {}
 
@@ -120,6 +125,9 @@ def load_library(path: Optional[str] = None, act_fp16: bool = False) -> C.CDLL:
     lib.wm_get_align_probs.argtypes = [vp, i32, i32, f32p]
     lib.wm_get_align_matrix.argtypes = [vp, i32, f32p]
     lib.wm_dtw.argtypes = [vp, f32p, i32, i32, i32p, i32p, i32p, i32p]
+    lib.wm_score_tokens.argtypes = [vp, C.POINTER(WmGenParams), C.POINTER(WmTimestampParams), C.POINTER(WmScoreParams), i32, i32p, i32, i32p, i32p,
+                                    f32p, f32p, f32p]
+    lib.wm_score_rows.argtypes = [vp, C.POINTER(WmGenParams), C.POINTER(WmTimestampParams), i32, f32p, i32p, i32, i32p, i32p, f32p]
     for name in EXPORTS:
         if name not in ("wm_destroy", "wm_last_error", "wm_resample_len"):      # wm_resample_len returns int64 (set above)
             getattr(lib, name).restype = i32
@@ -370,6 +378,57 @@ class Engine:
         self._check(self.lib.wm_dtw(self.h, m.ctypes.data_as(C.POINTER(C.c_float)), N, F, first.ctypes.data_as(i32p), pt.ctypes.data_as(i32p),
                                     pm.ctypes.data_as(i32p), C.byref(n)), "wm_dtw")
         return pt[: n.value].copy(), pm[: n.value].copy(), first
+
+    # ---- token log-probabilities (include/wm.h wm_score_tokens) -----------------------------------
+    def score_tokens(self, seqs: Sequence[Sequence[int]], n_prompt, gp: GenParams, no_speech_token_id: Optional[int] = None, sot_index: int = 0):
+        """Teacher-forced replay of ``seqs`` (one id list per stream of the resident encoder pass: prompt + generated, the stream's own end)
+        through all decoder layers and the base head, then HF's per-step scores on the GPU: ``log_softmax(processors(z_t), cur_len = t)[s[t]]``
+        for every generated position, the timestamp rules included when ``gp.timestamps``.  ``n_prompt``: int or one per stream.
+        Returns (numpy float32 [B, max len] log-probabilities — 0 inside the prompt and after a stream's end —, numpy float32 [B]
+        no-speech probabilities or None, ms).  Overwrites the decode state."""
+        B = len(seqs)
+        Tmax = max(max(len(s) for s in seqs), 1)
+        tok = np.zeros((B, Tmax), dtype=np.int32)
+        for b, s in enumerate(seqs):
+            tok[b, : len(s)] = s
+        lens = np.array([len(s) for s in seqs], dtype=np.int32)
+        npr = np.ascontiguousarray(np.broadcast_to(np.asarray(n_prompt, dtype=np.int32), (B,)))
+        out = np.zeros((B, Tmax), dtype=np.float32)
+        want_ns = no_speech_token_id is not None and int(no_speech_token_id) >= 0
+        nsp = np.zeros(B, dtype=np.float32)
+        ms = C.c_float(0)
+        g, _keep = self._gen_struct(gp)
+        ts = self._ts_struct(gp) if gp.timestamps else None
+        sp = WmScoreParams(int(no_speech_token_id) if want_ns else -1, int(sot_index))
+        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        self._kv_stamp = object()
+        self._check(self.lib.wm_score_tokens(self.h, C.byref(g), C.byref(ts) if ts is not None else None, C.byref(sp), B, tok.ctypes.data_as(i32p), Tmax,
+                                             lens.ctypes.data_as(i32p), npr.ctypes.data_as(i32p), out.ctypes.data_as(f32p),
+                                             nsp.ctypes.data_as(f32p) if want_ns else None, C.byref(ms)), "wm_score_tokens")
+        return out, (nsp if want_ns else None), ms.value
+
+    def score_rows(self, gp: GenParams, logits: np.ndarray, prefixes: Sequence[Sequence[int]], targets: Sequence[int]) -> np.ndarray:
+        """Scoring parity tap (wm_score_rows): rows ``logits [R, V]``, each under its own prefix and length, through the scoring kernels only.
+        Returns numpy float32 [R]: log_softmax(processed row)[target], -inf for a masked target."""
+        x = np.ascontiguousarray(logits, dtype=np.float32)
+        R, V = x.shape
+        if V != self.cfg.vocab_size or len(prefixes) != R or len(targets) != R:
+            raise ValueError("score_rows: logits must be [R, vocab] with one prefix and one target per row")
+        Tmax = max(len(p) for p in prefixes)
+        pre = np.zeros((R, Tmax), dtype=np.int32)
+        for r, p in enumerate(prefixes):
+            pre[r, : len(p)] = p
+        lens = np.array([len(p) for p in prefixes], dtype=np.int32)
+        tgt = np.ascontiguousarray(targets, dtype=np.int32)
+        out = np.zeros(R, np.float32)
+        g, _keep = self._gen_struct(gp)
+        ts = self._ts_struct(gp) if gp.timestamps else None
+        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        self._kv_stamp = object()
+        self._check(self.lib.wm_score_rows(self.h, C.byref(g), C.byref(ts) if ts is not None else None, R, x.ctypes.data_as(f32p),
+                                           pre.ctypes.data_as(i32p), Tmax, lens.ctypes.data_as(i32p), tgt.ctypes.data_as(i32p),
+                                           out.ctypes.data_as(f32p)), "wm_score_rows")
+        return out
 
     def tokens(self, stream: int) -> List[int]:
         cap = self.cfg.max_target_positions + 16

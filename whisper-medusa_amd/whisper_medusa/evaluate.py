@@ -17,14 +17,20 @@ from .metrics import compute_cer, compute_wer
 
 
 def evaluate_model(model, tokenizer, data: pd.DataFrame, language: str = "en", regulation_start: float = 140,
-                   regulation_factor: float = 1.0, out_file_path: Optional[str] = None) -> pd.DataFrame:
+                   regulation_factor: float = 1.0, out_file_path: Optional[str] = None, with_scores: bool = False) -> pd.DataFrame:
+    """``with_scores`` adds the columns ``avg_logprob`` and ``no_speech_prob`` per utterance (generate(return_token_logprobs=True): one
+    teacher-forced scoring pass per file); without it the output is the reference's."""
     data = data.fillna("")
-    preds, gts, langs, audios = [], [], [], []
+    preds, gts, langs, audios, avgs, nsps = [], [], [], [], [], []
     for _, row in data.iterrows():
         lang = row.get("language", language) or language
         feats = model.features_from_file(row.audio)                       # decode + downmix + resample + log-mel on the GPU
         decay = (regulation_start, regulation_factor) if regulation_factor != 1 else None      # eval_whisper_medusa.py:52-58
-        out = model.generate(feats, language=lang, exponential_decay_length_penalty=decay)
+        out = model.generate(feats, language=lang, exponential_decay_length_penalty=decay, **({"return_token_logprobs": True} if with_scores else {}))
+        if with_scores:
+            avgs.append(float(out["avg_logprob"][0]))
+            nsps.append(float(out["no_speech_prob"][0]) if "no_speech_prob" in out else float("nan"))
+            out = out["sequences"]
         preds.append(tokenizer.decode(out[0].tolist(), skip_special_tokens=True))
         gts.append(row.sentence)
         langs.append(language)                                            # the reference logs args.language here (:72)
@@ -34,6 +40,8 @@ def evaluate_model(model, tokenizer, data: pd.DataFrame, language: str = "en", r
     logging.info("WER: %s", wer)
     logging.info("CER: %s", cer)
     results = pd.DataFrame({"audio": audios, "label": gts, "prediction": preds, "wer": wers, "cer": cers, "language": langs})
+    if with_scores:
+        results["avg_logprob"], results["no_speech_prob"] = avgs, nsps
     results.attrs["wer"], results.attrs["cer"] = wer, cer
     if out_file_path:
         p = Path(out_file_path)
@@ -50,6 +58,7 @@ def main(argv=None):
     ap.add_argument("--language", default="en")
     ap.add_argument("--regulation-start", type=float, default=140)
     ap.add_argument("--regulation-factor", type=float, default=1)
+    ap.add_argument("--with-scores", action="store_true", help="add avg_logprob / no_speech_prob columns (one scoring pass per file)")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     from transformers import WhisperTokenizer
@@ -57,7 +66,7 @@ def main(argv=None):
     model = WhisperMedusaModel.from_pretrained(args.model_name).to("cuda")
     tok = WhisperTokenizer.from_pretrained(args.model_name)
     res = evaluate_model(model, tok, pd.read_csv(args.data_path), args.language, args.regulation_start, args.regulation_factor,
-                         args.out_file_path)
+                         args.out_file_path, with_scores=args.with_scores)
     logging.info("Results saved to %s (WER %.4f, CER %.4f)", args.out_file_path, res.attrs["wer"], res.attrs["cer"])
 
 

@@ -79,34 +79,43 @@ class ContextPool:
             e.close()
         self.engines = []
 
-    def _one(self, eng: Engine, x: torch.Tensor, gp: GenParams, from_wav: bool, token_ts=None):
+    def _one(self, eng: Engine, x: torch.Tensor, gp: GenParams, from_wav: bool, token_ts=None, score=None):
         with torch.cuda.device(eng.device):
             feats = eng.logmel(x) if from_wav else x
             eng.encode(feats)
             seqs = eng.decode(gp, x.shape[0])
             st = eng.stats()
-            tt = None
+            tt = sc = None
+            if score is not None:           # token log-probabilities / gating of the context's own streams; a skipped stream's row is replaced
+                seqs, sc, st["ms_token_logprobs"] = score(eng, seqs)
             if token_ts is not None:        # every context replays its own streams (api.token_timestamps_of)
                 tt, st["ms_token_timestamps"] = token_ts(eng, seqs)
-            return seqs, st, tt
+            return seqs, st, tt, sc
 
-    def run(self, x: torch.Tensor, gp: GenParams, from_wav: bool = False, token_ts=None) -> List[List[int]]:
+    def run(self, x: torch.Tensor, gp: GenParams, from_wav: bool = False, token_ts=None, score=None) -> List[List[int]]:
         """x: input features [B, n_mels, frames] (or waveforms [B, samples] with ``from_wav``) on the pool's GPU.
         ``token_ts(engine, seqs, lo)`` -> (list of per-stream float32 arrays, ms): token-level timestamps of a context's streams (whose first
-        is stream ``lo`` of the batch), computed right behind its decode; the per-stream arrays are left in ``last_token_timestamps``."""
+        is stream ``lo`` of the batch), computed right behind its decode; the per-stream arrays are left in ``last_token_timestamps``.
+        ``score(engine, seqs, lo)`` -> (seqs, list of per-stream score dicts, ms): token log-probabilities and gating of a context's streams
+        (api._score_run), run before ``token_ts``; the per-stream dicts are left in ``last_scores``."""
         B = x.shape[0]
         if B > self.per_ctx * len(self.engines):
             raise ValueError(f"batch of {B} exceeds the pool capacity {self.per_ctx * len(self.engines)}")
         bounds = shard_bounds(B, len(self.engines))
         if len(bounds) == 1:
-            res = [self._one(self.engines[0], x, gp, from_wav, None if token_ts is None else (lambda e, s: token_ts(e, s, 0)))]
+            res = [self._one(self.engines[0], x, gp, from_wav, None if token_ts is None else (lambda e, s: token_ts(e, s, 0)),
+                             None if score is None else (lambda e, s: score(e, s, 0)))]
         else:
             futs = [self._ex.submit(self._one, self.engines[i], x[lo:hi].contiguous(), gp, from_wav,
-                                    None if token_ts is None else (lambda e, s, lo=lo: token_ts(e, s, lo)))
+                                    None if token_ts is None else (lambda e, s, lo=lo: token_ts(e, s, lo)),
+                                    None if score is None else (lambda e, s, lo=lo: score(e, s, lo)))
                     for i, (lo, hi) in enumerate(bounds)]
             res = [f.result() for f in futs]
-        self.last_stats = merge_stats([st for _, st, _ in res])
+        self.last_stats = merge_stats([r[1] for r in res])
         if token_ts is not None:
-            self.last_stats["ms_token_timestamps"] = max(st["ms_token_timestamps"] for _, st, _ in res)
-            self.last_token_timestamps = [r for _, _, tt in res for r in tt]
-        return [s for seqs, _, _ in res for s in seqs]
+            self.last_stats["ms_token_timestamps"] = max(r[1]["ms_token_timestamps"] for r in res)
+            self.last_token_timestamps = [row for r in res for row in r[2]]
+        if score is not None:
+            self.last_stats["ms_token_logprobs"] = max(r[1]["ms_token_logprobs"] for r in res)
+            self.last_scores = [f for r in res for f in r[3]]
+        return [s for r in res for s in r[0]]
