@@ -294,7 +294,105 @@ def test_pool_longform_segments_match_single_engine(gpu):
     assert torch.equal(lf["token_timestamps"][0].cpu(), torch.tensor(want_tt, dtype=torch.float32))
 
 
-# ---- 7. error paths -------------------------------------------------------------------------------------------------------------------------
+# ---- 7. the replays and taps share one driver and leave the decode alone ------------------------------------------------------------------
+def _tap_params(cfg):
+    """Parameters of the two row taps: ids of their own with a timestamp block at the vocabulary's end (the taps never touch the weights)."""
+    from helpers import GenParams, ACCEPT_TYPICAL
+    tb = cfg.vocab_size - 30
+    return GenParams(prompt=[5, 6], eos_token_id=900, pad_token_id=900, suppress_tokens=[3, 40], begin_suppress_tokens=[7], max_length=cfg.max_target_positions,
+                     hard_max_length=cfg.max_length, accept_mode=ACCEPT_TYPICAL, temperature=1.0, exp_decay=(1, 1.3), timestamps=True,
+                     no_timestamps_token_id=tb - 1, max_initial_timestamp_index=5), tb
+
+
+def test_replays_and_taps_leave_the_decode_alone(gpu):
+    """Both replays in both orders, then both row taps, between two identical decodes: the orders agree bit for bit and the second decode
+    finds ids, statistics and the captured graph of the first.  Hand-made streams of 16, 17 and 33 tokens (prompt + generated): their last
+    replayed input positions (len - 2 = 14, 15, 31) sit below the first 16-row tile edge, on it, and on the edge of the second tile."""
+    model, cfg, _ = model_for(gpu, "micro")
+    eng, heads, P = model.engine, cfg.alignment_heads, len(synth.default_prompt(cfg))
+    f3 = feats_for(model, cfg, [0, 1, 2])
+    kw = dict(max_new_tokens=30, exponential_decay_length_penalty=(4, 1.5))
+
+    def run():
+        ids = model.generate(f3, **kw)
+        return ids, {k: model.last_stats[k] for k in ("iterations", "tokens_emitted", "accept_hist", "schedule_steps", "graph_replays")}
+    model.generate(f3, **kw)                    # (captures the graph of these parameters)
+    ids0, st0 = run()
+    seqs = [random_ids(cfg, n - P, seed) for n, seed in ((16, 1), (17, 2), (33, 3))]
+    assert [len(s) for s in seqs] == [16, 17, 33]
+    gp = model._gen_params(None, None, (4, 1.5), 30, None, None, False, None, None, None, None, None)
+    ns = cfg.no_timestamps_token_id - 1
+    lp_a, ns_a, _ = eng.score_tokens(seqs, P, gp, no_speech_token_id=ns)
+    tt_a, _ = eng.token_timestamps(seqs, P, heads, cfg.median_filter_width)
+    tt_b, _ = eng.token_timestamps(seqs, P, heads, cfg.median_filter_width)
+    lp_b, ns_b, _ = eng.score_tokens(seqs, P, gp, no_speech_token_id=ns)
+    assert np.array_equal(lp_a, lp_b) and np.array_equal(ns_a, ns_b) and np.array_equal(tt_a, tt_b)
+    assert np.isfinite(lp_a[2, P:33]).all() and bool((lp_a[2, P:33] < 0).all()) and float(tt_a.max()) > 0
+    tgp, tb = _tap_params(cfg)
+    rows = np.random.default_rng(3).standard_normal((2, cfg.vocab_size)).astype(np.float32) * 2.0
+    pre = [list(tgp.prompt) + [tb + 3, 41], list(tgp.prompt) + [tb + 3, 41, tb + 9, tb + 9, 12]]
+    sr = eng.score_rows(tgp, rows, pre, [44, tb + 12])
+    sel = eng.select_rows(tgp, rows, pre, [44, tb + 12])
+    assert sr.shape == (2,) and not np.isnan(sr).any() and sel["argmax"].shape == (2,)
+    ids1, st1 = run()
+    assert torch.equal(ids0, ids1) and st0 == st1, (st0, st1)
+    assert st0["graph_replays"] > 0
+    # the replays after the taps: what they gave before them
+    assert np.array_equal(eng.score_tokens(seqs, P, gp, no_speech_token_id=ns)[0], lp_a)
+    assert np.array_equal(eng.token_timestamps(seqs, P, heads, cfg.median_filter_width)[0], tt_a)
+
+
+_GROUPS_CHILD = r"""
+import sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+import torch
+import test_gpu_token_timestamps as T
+model, eng, seqs, P, heads, width = T.groups_rig(torch.device("cuda", 0))
+out, _ = eng.token_timestamps(seqs, P, heads, width)
+try:
+    eng.align_matrix(0)
+    split = False
+except RuntimeError as e:
+    split = "no longer resident" in str(e)
+np.savez(sys.argv[2], out=out, split=split, m2=eng.align_matrix(2))
+eng.close()
+"""
+
+
+def groups_rig(gpu):
+    """Three streams whose alignment workspaces are 480 KB each (2 heads x 40 rows x 1536 frames x 4 bytes) on a micro checkpoint with a long
+    encoder: under a 1 MB cap (the smallest WM_ALIGN_WS_MB) they form the groups [0, 1] and [2], so the replay driver runs at b0 = 2."""
+    cfg = MedusaConfig.micro(K=4, n_ctx=1536)
+    cfg = dataclasses.replace(cfg, alignment_heads=synth.synth_alignment_heads(cfg, 2))
+    model = WhisperMedusaModel(cfg, synth.synth_state_dict(cfg, seed=31), device=gpu, max_batch=3)
+    P = len(synth.default_prompt(cfg))
+    model.engine.encode(feats_for(model, cfg, [0, 1, 2]))
+    return model, model.engine, [random_ids(cfg, 42 - P, s) for s in (1, 2, 3)], P, cfg.alignment_heads, cfg.median_filter_width
+
+
+def test_workspace_groups_equal_one_group(gpu, tmp_path):
+    """WM_ALIGN_WS_MB is read once per process: a fresh child runs the call split into two workspace groups; the timestamps and the last
+    group's matrix must be those of this process, where all three streams share one group."""
+    import os
+    import subprocess
+    import sys
+    model, eng, seqs, P, heads, width = groups_rig(gpu)
+    want, _ = eng.token_timestamps(seqs, P, heads, width)
+    m2 = eng.align_matrix(2)
+    eng.align_matrix(0)                         # one group: every stream is resident
+    eng.close()
+    path = str(tmp_path / "child.npz")
+    env = dict(os.environ, WM_ALIGN_WS_MB="1")
+    here = os.path.dirname(os.path.abspath(__file__))
+    r = subprocess.run([sys.executable, "-c", _GROUPS_CHILD, here, path], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = np.load(path)
+    assert bool(got["split"]), "the child did not split the streams into more than one workspace group"
+    assert float(want.max()) > 0 and np.array_equal(got["out"], want) and np.array_equal(got["m2"], m2, equal_nan=True)
+
+
+# ---- 8. error paths -------------------------------------------------------------------------------------------------------------------------
 def test_error_paths(gpu):
     model, cfg, sd = model_for(gpu, "micro")
     f1 = feats_for(model, cfg, [0])

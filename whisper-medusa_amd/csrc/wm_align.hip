@@ -2,8 +2,8 @@
 // computes from the cross-attentions of an autoregressive decode (transformers generation_whisper.py: _extract_token_timestamps,
 // _median_filter, _dynamic_time_warping), for an engine whose Medusa loop never materialises attention weights.
 //
-//   replay        the final ids of every stream go through the decoder once more, teacher-forced, in 16-row tiles (the launches of a base
-//                 pass: wm_decoder.hip wm_dec_replay_layers), up to the highest alignment layer; no heads, no vocabulary projection
+//   replay        the final ids of every stream go through the decoder once more, teacher-forced, in 16-row tiles (the shared driver
+//                 wm_dec_replay: wm_internal.h / wm_decoder.hip), up to the highest alignment layer; no heads, no vocabulary projection
 //   k_align_probs behind every layer that owns alignment heads: softmax(q K^T) of those heads over the n_ctx encoder frames, from the
 //                 layer's fp32 cross-attention query rows (ctx->qbuf) and the bf16 cross-K -> workspace [stream][A][N][n_ctx] fp32
 //   k_align_stats mean / population std over the N rows per (head, frame)
@@ -28,13 +28,12 @@ struct AlignStream {            // one stream of the resident group (device copy
 };
 
 struct wm_align_state {
-    float *probs = nullptr, *stats = nullptr, *M = nullptr;
-    unsigned char* trace = nullptr;
-    int* first = nullptr;
-    AlignStream* si = nullptr;
-    int2* heads = nullptr;          // [A] (layer, head)
-    int* lay_list = nullptr;        // [A] head indices a grouped by layer
-    size_t cap_probs = 0, cap_stats = 0, cap_M = 0, cap_trace = 0, cap_first = 0, cap_si = 0, cap_heads = 0;
+    DevBuf<float> probs, stats, M;
+    DevBuf<unsigned char> trace;
+    DevBuf<int> first;
+    DevBuf<AlignStream> si;
+    DevBuf<int2> heads;             // [A] (layer, head)
+    DevBuf<int> lay_list;           // [A] head indices a grouped by layer
     // the group of the last call that is still resident (parity taps)
     int g0 = 0, g1 = 0, A = 0, B = 0;
     std::vector<AlignStream> host;  // [B] of the last call (offsets valid for streams in [g0, g1))
@@ -42,28 +41,8 @@ struct wm_align_state {
 
 void wm_align_free(wm_ctx* ctx)
 {
-    wm_align_state* al = ctx->align;
-    if (!al) return;
-    void* bufs[] = {al->probs, al->stats, al->M, al->trace, al->first, al->si, al->heads, al->lay_list};
-    for (void* b : bufs) if (b) hipFree(b);
-    delete al;
+    delete ctx->align;
     ctx->align = nullptr;
-}
-
-template <class T>
-static hipError_t grow(T** p, size_t* cap, size_t n)
-{
-    if (n <= *cap && *p) return hipSuccess;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(n, 1) * sizeof(T));
-    if (e == hipSuccess) *cap = n;
-    return e;
-}
-
-__global__ void k_fill_int(int* __restrict__ p, int n, int v)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = v;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -305,18 +284,18 @@ k_dtw(const float* __restrict__ M, const AlignStream* __restrict__ si, unsigned 
 struct ReplayHook {
     wm_align_state* al;
     const std::vector<int>* lay_off;    // [dec_layers + 1] into lay_list
-    int g0, nb, pos0, Mper;
+    int g0, nb;
     size_t lds;
 };
 
-static int after_layer(wm_ctx* ctx, int l, void* arg)
+static int after_layer(wm_ctx* ctx, int l, int pos0, int Mper, void* arg)
 {
     const ReplayHook* hk = static_cast<const ReplayHook*>(arg);
     const int o0 = (*hk->lay_off)[l], cnt = (*hk->lay_off)[l + 1] - o0;
     if (cnt == 0) return WM_OK;
     const bf16_t* kx = ctx->kx + ((size_t)l * ctx->Benc + hk->g0) * ctx->H * ctx->Spad * 64;       // the bf16 projection (also on a cross_kv_fp8 context)
     hipLaunchKernelGGL(k_align_probs, dim3(cnt, hk->nb), dim3(256), hk->lds, ctx->stream, ctx->qbuf, kx, hk->al->lay_list + o0, hk->al->heads,
-                       hk->al->si, hk->al->probs, hk->pos0, hk->Mper, ctx->d, ctx->H, ctx->S, ctx->Spad);
+                       hk->al->si, hk->al->probs, pos0, Mper, ctx->d, ctx->H, ctx->S, ctx->Spad);
     WM_HIP(hipGetLastError());
     return WM_OK;
 }
@@ -350,8 +329,7 @@ extern "C" int wm_token_timestamps(wm_ctx* ctx, const wm_align_params* ap, int B
 {
     if (!ctx) return WM_ERR_ARG;
     if (!ap || !ap->heads || !tokens || !lens || !n_prompt || !out || B < 1 || Tmax < 1) { ctx->err = "wm_token_timestamps: bad arguments"; return WM_ERR_ARG; }
-    if (ctx->Benc < 1) { ctx->err = "wm_token_timestamps: call wm_encode first"; return WM_ERR_STATE; }
-    if (B > ctx->Benc) { ctx->err = "wm_token_timestamps: more streams than the last wm_encode"; return WM_ERR_ARG; }
+    if (int rc = wm_replay_check(ctx, "wm_token_timestamps", B, Tmax, lens, n_prompt, 0)) return rc;
     const int A = ap->n_heads, W = ap->median_filter_width, S = ctx->S;
     if (A < 1 || A > 64) { ctx->err = "wm_token_timestamps: n_heads must be in 1..64"; return WM_ERR_ARG; }
     if (W < 1 || W > 15 || W % 2 == 0) { ctx->err = "wm_token_timestamps: median_filter_width must be odd, 1..15"; return WM_ERR_ARG; }
@@ -363,20 +341,19 @@ extern "C" int wm_token_timestamps(wm_ctx* ctx, const wm_align_params* ap, int B
             ctx->err = "wm_token_timestamps: alignment head (" + std::to_string(l) + ", " + std::to_string(h) + ") out of range"; return WM_ERR_ARG; }
         lmax = std::max(lmax, l);
     }
-    for (int b = 0; b < B; ++b) {
-        if (lens[b] < 1 || lens[b] > ctx->Tmax || lens[b] > Tmax) { ctx->err = "wm_token_timestamps: lens must be in [1, min(Tmax, n_tgt)]"; return WM_ERR_ARG; }
-        if (n_prompt[b] < 0 || n_prompt[b] > lens[b]) { ctx->err = "wm_token_timestamps: n_prompt must be in [0, lens]"; return WM_ERR_ARG; }
-        if (num_frames && num_frames[b] / 2 < 1) { ctx->err = "wm_token_timestamps: num_frames must be at least 2"; return WM_ERR_ARG; }
-    }
+    for (int b = 0; num_frames && b < B; ++b)
+        if (num_frames[b] / 2 < 1) { ctx->err = "wm_token_timestamps: num_frames must be at least 2"; return WM_ERR_ARG; }
     WM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     wm_align_state* al = align_state(ctx);
     const double tp = precision_decimal(ap->time_precision);
 
-    // the replay overwrites the decode state (ids, kvlen, self K/V): begin again afterwards
-    ctx->gp.K = ctx->K; ctx->gp.V = ctx->V; ctx->gp.Vpad = ctx->Vpad; ctx->gp.Tids = ctx->Tal;
-    ctx->began = false; ctx->use_done = false; ctx->host_carry = false; ctx->dev_carry = false; ctx->step_flow = false;
-    const int Tids = ctx->Tal;
+    // the replay overwrites the decode state (ids, kvlen, self K/V): begin again afterwards.  Its launches read only the shape fields of
+    // the scalars; the rest stays what the last decode left.
+    wm_decode_invalidate(ctx);
+    GenDev g = ctx->gp;
+    g.K = ctx->K; g.V = ctx->V; g.Vpad = ctx->Vpad; g.Tids = ctx->Tal;
+    wm_scalars_swap swap(ctx, g, ctx->ts);
 
     std::vector<AlignStream>& hs = al->host;
     hs.assign(B, AlignStream{});
@@ -393,18 +370,17 @@ extern "C" int wm_token_timestamps(wm_ctx* ctx, const wm_align_params* ap, int B
     for (int a = 0; a < A; ++a) { heads[a] = make_int2(ap->heads[2 * a], ap->heads[2 * a + 1]); lay_off[heads[a].x + 1]++; }
     for (int l = 0; l < ctx->cfg.dec_layers; ++l) lay_off[l + 1] += lay_off[l];
     { std::vector<int> fill(lay_off.begin(), lay_off.end() - 1); for (int a = 0; a < A; ++a) lay_list[fill[heads[a].x]++] = a; }
-    WM_HIP(grow(&al->heads, &al->cap_heads, (size_t)A));
-    if (!al->lay_list) WM_HIP(hipMalloc(reinterpret_cast<void**>(&al->lay_list), 64 * sizeof(int)));
+    WM_HIP(al->heads.reserve(A)); WM_HIP(al->lay_list.reserve(A));
     WM_HIP(hipMemcpyAsync(al->heads, heads.data(), A * sizeof(int2), hipMemcpyHostToDevice, st));
     WM_HIP(hipMemcpyAsync(al->lay_list, lay_list.data(), A * sizeof(int), hipMemcpyHostToDevice, st));
-    WM_HIP(grow(&al->si, &al->cap_si, (size_t)ctx->maxB));
+    WM_HIP(al->si.reserve(ctx->maxB));
 
     const size_t lds = (size_t)(16 * 64 + 16 * ctx->Spad) * sizeof(float);
     WM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_align_probs), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     static const size_t cap_bytes = [] { const char* v = std::getenv("WM_ALIGN_WS_MB"); return (size_t)(v ? std::max(1, std::atoi(v)) : 512) << 20; }();
 
     WM_HIP(hipEventRecord(ctx->ev0, st));
-    std::vector<int> ids, fr;
+    std::vector<int> fr;
     for (int g0 = 0; g0 < B;) {
         // streams [g0, g1) whose probabilities fit the workspace cap (at least one)
         int g1 = g0;
@@ -421,22 +397,13 @@ extern "C" int wm_token_timestamps(wm_ctx* ctx, const wm_align_params* ap, int B
         }
         const int nb = g1 - g0;
         if (Nmax >= 2) {
-            WM_HIP(grow(&al->probs, &al->cap_probs, np)); WM_HIP(grow(&al->stats, &al->cap_stats, ns)); WM_HIP(grow(&al->M, &al->cap_M, nm));
-            WM_HIP(grow(&al->trace, &al->cap_trace, nt)); WM_HIP(grow(&al->first, &al->cap_first, nf));
+            WM_HIP(al->probs.reserve(np)); WM_HIP(al->stats.reserve(ns)); WM_HIP(al->M.reserve(nm));
+            WM_HIP(al->trace.reserve(nt)); WM_HIP(al->first.reserve(nf));
             WM_HIP(hipMemcpyAsync(al->si, hs.data() + g0, nb * sizeof(AlignStream), hipMemcpyHostToDevice, st));
-            // ids of the group (rows past a stream's length: token 0, computed and ignored)
-            ids.assign((size_t)nb * Tids, 0);
-            for (int b = g0; b < g1; ++b) for (int t = 0; t < lens[b]; ++t) ids[(size_t)(b - g0) * Tids + t] = tokens[(size_t)b * Tmax + t];
-            WM_HIP(hipMemcpyAsync(ctx->ids + (size_t)g0 * Tids, ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice, st));
-            WM_HIP(hipStreamSynchronize(st));
-            // teacher-forced replay of input positions 0 .. maxlen - 2 in 16-row tiles
-            ReplayHook hk{al, &lay_off, g0, nb, 0, 0, lds};
-            for (int pos0 = 0; pos0 < maxlen - 1; pos0 += 16) {
-                hk.pos0 = pos0; hk.Mper = std::min(16, maxlen - 1 - pos0);
-                hipLaunchKernelGGL(k_fill_int, dim3((nb + 63) / 64), dim3(64), 0, st, ctx->kvlen + g0, nb, pos0);
-                WM_HIP(hipGetLastError());
-                if (int rc = wm_dec_replay_layers(ctx, g0, nb, hk.Mper, lmax + 1, after_layer, &hk)) return rc;
-            }
+            // teacher-forced replay of the group's input positions 0 .. maxlen - 2
+            ReplayHook hk{al, &lay_off, g0, nb, lds};
+            wm_replay_hooks hooks; hooks.layer = after_layer; hooks.arg = &hk;
+            if (int rc = wm_dec_replay(ctx, g0, nb, tokens, Tmax, lens, maxlen - 1, lmax + 1, hooks)) return rc;
             hipLaunchKernelGGL(k_align_stats, dim3((Fmax + 255) / 256, A, nb), dim3(256), 0, st, al->probs, al->si, al->stats, S);
             WM_HIP(hipGetLastError());
             if (int rc = launch_norm(ctx, al, W, Fmax, Nmax, nb, A)) return rc;

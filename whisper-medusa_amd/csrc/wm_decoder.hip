@@ -1621,9 +1621,16 @@ int wm_dec_stage_layers(wm_ctx* ctx, int b0, int nb, int Mper, int mode)
     return WM_OK;
 }
 
-// Teacher-forced replay (token timestamps, wm_align.hip): the embed + layer launches of a base pass (mode 0 above) for the first n_layers
-// layers, with a hook behind every layer.  No carry, no early exit on the decode's done flag: the caller has cleared both.
-int wm_dec_replay_layers(wm_ctx* ctx, int b0, int nb, int Mper, int n_layers, int (*after)(wm_ctx*, int, void*), void* arg)
+// ---- teacher-forced replay (wm_internal.h wm_dec_replay: token timestamps and token log-probabilities) ------------------------------
+__global__ void k_fill_int(int* __restrict__ p, int n, int v)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
+// One tile: the embed + layer launches of a base pass (mode 0 above) for the first n_layers layers, with the hook behind every layer.
+// No carry, no early exit on the decode's done flag: the caller has cleared both (wm_decode_invalidate).
+static int replay_tile(wm_ctx* ctx, int b0, int nb, int pos0, int Mper, int n_layers, const wm_replay_hooks& hk)
 {
     hipStream_t st = ctx->stream;
     g_skinny_done = nullptr;
@@ -1640,10 +1647,42 @@ int wm_dec_replay_layers(wm_ctx* ctx, int b0, int nb, int Mper, int n_layers, in
     int rc = WM_OK;
     for (int l = 0; l < n_layers && rc == WM_OK; ++l) {
         rc = dec_layer(ctx, ctx->dec[l], l, ctx->h, b0, nb, Mper, base, false, nullptr, l + 1 < ctx->cfg.dec_layers ? &ctx->dec[l + 1] : nullptr);
-        if (rc == WM_OK && after) rc = after(ctx, l, arg);
+        if (rc == WM_OK && hk.layer) rc = hk.layer(ctx, l, pos0, Mper, hk.arg);
     }
     ctx->replay = false;
     return rc;
+}
+
+int wm_dec_replay(wm_ctx* ctx, int b0, int nb, const int32_t* tokens, int Tmax, const int32_t* lens, int npos, int n_layers,
+                  const wm_replay_hooks& hk)
+{
+    hipStream_t st = ctx->stream;
+    const int Tids = ctx->Tal;
+    std::vector<int> ids((size_t)nb * Tids, 0);
+    for (int b = b0; b < b0 + nb; ++b) for (int t = 0; t < lens[b]; ++t) ids[(size_t)(b - b0) * Tids + t] = tokens[(size_t)b * Tmax + t];
+    WM_HIP(hipMemcpyAsync(ctx->ids + (size_t)b0 * Tids, ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    WM_HIP(hipStreamSynchronize(st));      // the host vector goes out of scope
+    for (int pos0 = 0; pos0 < npos; pos0 += 16) {
+        const int Mper = std::min(16, npos - pos0);
+        hipLaunchKernelGGL(k_fill_int, dim3((nb + 63) / 64), dim3(64), 0, st, ctx->kvlen + b0, nb, pos0);
+        WM_HIP(hipGetLastError());
+        if (int rc = replay_tile(ctx, b0, nb, pos0, Mper, n_layers, hk)) return rc;
+        if (hk.tile) if (int rc = hk.tile(ctx, pos0, Mper, hk.arg)) return rc;
+    }
+    return WM_OK;
+}
+
+int wm_replay_check(wm_ctx* ctx, const char* who, int B, int Tmax, const int32_t* lens, const int32_t* n_prompt, int min_prompt)
+{
+    const std::string w(who);
+    if (ctx->Benc < 1) { ctx->err = w + ": call wm_encode first"; return WM_ERR_STATE; }
+    if (B > ctx->Benc || B * 16 > ctx->Rcap) { ctx->err = w + ": more streams than the last wm_encode"; return WM_ERR_ARG; }
+    for (int b = 0; b < B; ++b) {
+        if (lens[b] < 1 || lens[b] > ctx->Tmax || lens[b] > Tmax) { ctx->err = w + ": lens must be in [1, min(Tmax, n_tgt)]"; return WM_ERR_ARG; }
+        if (n_prompt[b] < min_prompt || n_prompt[b] > lens[b]) {
+            ctx->err = w + ": n_prompt must be in [" + std::to_string(min_prompt) + ", lens]"; return WM_ERR_ARG; }
+    }
+    return WM_OK;
 }
 
 // ---- stage 2: final LayerNorm for all rows (-> hf); Medusa-Block: the extra decoder layer on the

@@ -4,7 +4,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include "wm_internal.h"
+#include "wm_select.h"
 
 static thread_local std::string g_create_err;
 
@@ -220,7 +220,7 @@ extern "C" int wm_create(const wm_config* cfg, const wm_weights* w, int device, 
             for (int n = 0; n <= K; ++n) { sib.depth[n] = n; sib.parent[n] = n - 1; sib.anc[n] = (2ull << n) - 1ull; }
             for (int j = 0; j < S; ++j) { const int n = K + 1 + j; sib.depth[n] = 1; sib.parent[n] = 0; sib.anc[n] = 1ull | (1ull << n); }
             CREATE_HIP(dev_alloc(&ctx->sibtree, 1, st));
-            CREATE_HIP(dev_alloc(&ctx->sibpart, (size_t)cfg->max_batch * 16 * 6, st));      // SEL_SP = 16 slices
+            CREATE_HIP(dev_alloc(&ctx->sibpart, (size_t)cfg->max_batch * SEL_SP * 6, st));
             CREATE_HIP(hipMemcpyAsync(ctx->sibtree, &sib, sizeof(TreeDev), hipMemcpyHostToDevice, st));
             CREATE_HIP(hipStreamSynchronize(st));
             ctx->sib_cfg = S;
@@ -306,7 +306,7 @@ extern "C" int wm_set_encoder_output(wm_ctx* ctx, const float* hidden, int B)
 }
 
 // the timestamp scalars of a decode / tap: ts == NULL -> off.  Validation errors go to ctx->err.
-int wm_ts_setup(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* ts, TsDev* out)
+static int wm_ts_setup(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* ts, TsDev* out)
 {
     TsDev t = ctx->ts;
     t.on = 0; t.tb = 0; t.nots = -1; t.mit = -1; t.L = ctx->L;
@@ -325,6 +325,42 @@ int wm_ts_setup(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params*
     return WM_OK;
 }
 
+int wm_proc_setup(wm_ctx* ctx, const char* who, const wm_gen_params* gp, const wm_timestamp_params* tsp, GenDev* g_out, TsDev* ts_out)
+{
+    if (gp->eos_token_id < 0 || gp->eos_token_id >= ctx->V) { ctx->err = std::string(who) + ": eos out of range"; return WM_ERR_ARG; }
+    if (gp->prompt_len < 0 || (gp->prompt_len > 0 && !gp->prompt)) { ctx->err = std::string(who) + ": bad prompt"; return WM_ERR_ARG; }
+    TsDev ts{};
+    if (int rc = wm_ts_setup(ctx, gp, tsp, &ts)) return rc;
+    const int P = gp->prompt_len, Tids = ctx->Tal;
+    GenDev g{};
+    g.P = P; g.eos = gp->eos_token_id; g.pad = gp->pad_token_id;
+    g.exp_start = gp->exp_decay_start >= 0 ? gp->exp_decay_start + P : -1;
+    g.thr = gp->posterior_threshold; g.alpha = gp->posterior_alpha;
+    // the begin-suppress list applies at: the timestamp rules' begin_index, else the generation parameters', else the prompt length
+    g.begin = (tsp && tsp->begin_index >= 0) ? tsp->begin_index : (gp->begin_index >= 0 ? gp->begin_index : P);
+    g.K = ctx->K; g.V = ctx->V; g.Vpad = ctx->Vpad; g.Tids = Tids;
+    std::vector<unsigned char> mask(ctx->Vpad, 0);
+    for (int i = 0; i < gp->n_suppress; ++i) if (gp->suppress[i] >= 0 && gp->suppress[i] < ctx->V) mask[gp->suppress[i]] |= 1;
+    for (int i = 0; i < gp->n_begin_suppress; ++i)
+        if (gp->begin_suppress[i] >= 0 && gp->begin_suppress[i] < ctx->V) mask[gp->begin_suppress[i]] |= 2;
+    std::vector<float> pen(Tids + 1, 0.f);
+    if (g.exp_start >= 0)
+        for (int t = 0; t <= Tids; ++t)     // (factor^(cur_len - start) - 1) evaluated in double like the Python scalar
+            pen[t] = t > g.exp_start ? (float)(std::pow((double)gp->exp_decay_factor, (double)(t - g.exp_start)) - 1.0) : 0.f;
+    WM_HIP(hipMemcpyAsync(ctx->supmask, mask.data(), mask.size(), hipMemcpyHostToDevice, ctx->stream));
+    WM_HIP(hipMemcpyAsync(ctx->exppen, pen.data(), pen.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    WM_HIP(hipStreamSynchronize(ctx->stream));      // host vectors go out of scope
+    *g_out = g; *ts_out = ts;
+    return WM_OK;
+}
+
+void wm_decode_invalidate(wm_ctx* ctx, bool drop_graphs)
+{
+    ctx->began = false; ctx->use_done = false; ctx->host_carry = false; ctx->dev_carry = false; ctx->step_flow = false;
+    if (drop_graphs && ctx->graph) { (void)hipGraphExecDestroy(ctx->graph); ctx->graph = nullptr; }
+    if (drop_graphs && ctx->graph_base) { (void)hipGraphExecDestroy(ctx->graph_base); ctx->graph_base = nullptr; }
+}
+
 extern "C" int wm_decode_begin(wm_ctx* ctx, const wm_gen_params* gp, int B) { return wm_decode_begin_ts(ctx, gp, nullptr, B); }
 
 extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* tsp, int B)
@@ -332,27 +368,20 @@ extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm
     if (!ctx || !gp) return WM_ERR_ARG;
     WM_HIP(hipSetDevice(ctx->device));
     if (ctx->Benc < 1 || B != ctx->Benc) { ctx->err = "wm_decode_begin: call wm_encode with the same B first"; return WM_ERR_STATE; }
-    const int P = gp->prompt_len, K = ctx->K, Tids = ctx->Tal;
-    if (P < 1 || P >= ctx->Tmax - K - 1) {
+    const int P = gp->prompt_len, Tids = ctx->Tal;
+    if (P < 1 || P >= ctx->Tmax - ctx->K - 1) {
         // same condition class as the reference's over-long prompt ValueError (model.py:1526-1529)
         ctx->err = "wm_decode_begin: prompt length must be in [1, n_tgt - K - 2]"; return WM_ERR_ARG; }
-    if (gp->eos_token_id < 0 || gp->eos_token_id >= ctx->V) { ctx->err = "wm_decode_begin: eos out of range"; return WM_ERR_ARG; }
     if (!gp->vanilla && gp->accept_mode == WM_ACCEPT_TYPICAL && !(gp->temperature > 0.f)) {
         ctx->err = "wm_decode_begin: typical acceptance needs temperature > 0"; return WM_ERR_ARG; }
     hipStream_t st = ctx->stream;
-    GenDev g{};
-    g.P = P; g.eos = gp->eos_token_id; g.pad = gp->pad_token_id;
+    GenDev g{}; TsDev ts{};
+    if (int rc = wm_proc_setup(ctx, "wm_decode_begin", gp, tsp, &g, &ts)) return rc;
     g.max_length = std::min(gp->max_length, ctx->Tmax);
     g.hard_max_length = std::min(gp->hard_max_length, ctx->Tmax);
-    g.exp_start = gp->exp_decay_start >= 0 ? gp->exp_decay_start + P : -1;
-    g.thr = gp->posterior_threshold; g.alpha = gp->posterior_alpha;
     g.inv_temp = (gp->accept_mode == WM_ACCEPT_TYPICAL && gp->temperature > 0.f) ? 1.0f / gp->temperature : 1.0f;
     g.force_accept = gp->force_accept;
-    g.begin = gp->begin_index >= 0 ? gp->begin_index : P;
-    TsDev ts{};
-    if (int rc = wm_ts_setup(ctx, gp, tsp, &ts)) return rc;
-    if (ts.on && tsp->begin_index >= 0) g.begin = tsp->begin_index;
-    g.accept_mode = gp->accept_mode; g.vanilla = gp->vanilla; g.K = K; g.V = ctx->V; g.Vpad = ctx->Vpad; g.Tids = Tids;
+    g.accept_mode = gp->accept_mode; g.vanilla = gp->vanilla;
     ctx->fuse = std::getenv("WM_NO_CARRY") == nullptr;
     ctx->host_carry = ctx->fuse && B == 1 && !gp->vanilla;
     ctx->dev_carry = ctx->fuse && B > 1 && !gp->vanilla;
@@ -369,14 +398,6 @@ extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm
 
     std::vector<int> ids((size_t)B * Tids, gp->pad_token_id), L(B, P), zero(B, 0);
     for (int b = 0; b < B; ++b) for (int i = 0; i < P; ++i) ids[(size_t)b * Tids + i] = gp->prompt[i];
-    std::vector<unsigned char> mask(ctx->Vpad, 0);
-    for (int i = 0; i < gp->n_suppress; ++i) if (gp->suppress[i] >= 0 && gp->suppress[i] < ctx->V) mask[gp->suppress[i]] |= 1;
-    for (int i = 0; i < gp->n_begin_suppress; ++i)
-        if (gp->begin_suppress[i] >= 0 && gp->begin_suppress[i] < ctx->V) mask[gp->begin_suppress[i]] |= 2;
-    std::vector<float> pen(Tids + 1, 0.f);
-    if (g.exp_start >= 0)
-        for (int t = 0; t <= Tids; ++t)     // (factor^(cur_len - start) - 1) evaluated in double like the Python scalar
-            pen[t] = t > g.exp_start ? (float)(std::pow((double)gp->exp_decay_factor, (double)(t - g.exp_start)) - 1.0) : 0.f;
     WM_HIP(hipMemcpyAsync(ctx->ids, ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice, st));
     WM_HIP(hipMemcpyAsync(ctx->L, L.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
     WM_HIP(hipMemcpyAsync(ctx->kvlen, zero.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
@@ -387,8 +408,6 @@ extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm
     WM_HIP(hipMemsetAsync(ctx->carry, 0, ctx->maxB * sizeof(int), st));
     WM_HIP(hipMemsetAsync(ctx->steprows, 0, 4 * sizeof(int), st));
     ctx->use_done = true;
-    WM_HIP(hipMemcpyAsync(ctx->supmask, mask.data(), mask.size(), hipMemcpyHostToDevice, st));
-    WM_HIP(hipMemcpyAsync(ctx->exppen, pen.data(), pen.size() * sizeof(float), hipMemcpyHostToDevice, st));
     std::vector<int4> tst(B, make_int4(0, 0, -1, 0));
     if (ts.on) {                           // the committed timestamp state of the prompt's sampled part, ids[begin:P] (HF slices input_ids[begin_index:])
         int4 s0 = make_int4(0, 0, -1, 0);
@@ -591,9 +610,6 @@ extern "C" int wm_get_cross_kv(wm_ctx* ctx, int kv_layer, int stream, int head, 
     return WM_OK;
 }
 
-// forward(): one decoder pass over T tokens per stream at positions pos0.., K/V appended at row pos0.
-static constexpr int SEL_SP_HOST = 16;         // select slices per logits row (wm_decoder.hip SEL_SP)
-
 // Timestamp parity tap: caller-given rows through the decode loop's timestamp state fold and select kernels (include/wm.h).
 extern "C" int wm_select_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* tsp, int R, const float* logits,
                               const int32_t* prefixes, int Tmax, const int32_t* lens, const int32_t* probe_tokens, int32_t* out_argmax,
@@ -605,31 +621,22 @@ extern "C" int wm_select_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_tim
     for (int r = 0; r < R; ++r)
         if (lens[r] < 1 || lens[r] > Tmax || probe_tokens[r] < 0 || probe_tokens[r] >= ctx->V) {
             ctx->err = "wm_select_rows: lens must be in [1, Tmax] and probe tokens inside the vocabulary"; return WM_ERR_ARG; }
-    if (gp->eos_token_id < 0 || gp->eos_token_id >= ctx->V) { ctx->err = "wm_select_rows: eos out of range"; return WM_ERR_ARG; }
     WM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    TsDev ts{};
-    if (int rc = wm_ts_setup(ctx, gp, tsp, &ts)) return rc;
-    GenDev g{};
-    g.P = gp->prompt_len; g.eos = gp->eos_token_id; g.pad = gp->pad_token_id;
-    g.max_length = g.hard_max_length = ctx->Tmax; g.exp_start = -1;
-    g.thr = gp->posterior_threshold; g.alpha = gp->posterior_alpha;
+    GenDev g{}; TsDev ts{};
+    if (int rc = wm_proc_setup(ctx, "wm_select_rows", gp, tsp, &g, &ts)) return rc;
+    g.max_length = g.hard_max_length = ctx->Tmax; g.exp_start = -1;         // no length penalty
     g.inv_temp = gp->temperature > 0.f ? 1.0f / gp->temperature : 1.0f;
     g.force_accept = -1;
-    g.begin = tsp->begin_index >= 0 ? tsp->begin_index : (gp->begin_index >= 0 ? gp->begin_index : gp->prompt_len);
-    g.accept_mode = WM_ACCEPT_TYPICAL; g.vanilla = 0; g.K = ctx->K; g.V = ctx->V; g.Vpad = ctx->Vpad; g.Tids = ctx->Tal;
-    ctx->gp = g; ctx->ts = ts; ctx->began = false;
-    std::vector<unsigned char> mask(ctx->Vpad, 0);
-    for (int i = 0; i < gp->n_suppress; ++i) if (gp->suppress[i] >= 0 && gp->suppress[i] < ctx->V) mask[gp->suppress[i]] |= 1;
-    for (int i = 0; i < gp->n_begin_suppress; ++i)
-        if (gp->begin_suppress[i] >= 0 && gp->begin_suppress[i] < ctx->V) mask[gp->begin_suppress[i]] |= 2;
-    WM_HIP(hipMemcpyAsync(ctx->supmask, mask.data(), mask.size(), hipMemcpyHostToDevice, st));
+    g.accept_mode = WM_ACCEPT_TYPICAL; g.vanilla = 0;
+    wm_decode_invalidate(ctx);
+    wm_scalars_swap swap(ctx, g, ts);
     const int L0 = lens[0];
     WM_HIP(hipMemcpyAsync(ctx->L, &L0, sizeof(int), hipMemcpyHostToDevice, st));
     int* buf = nullptr;
     WM_HIP(hipMalloc(reinterpret_cast<void**>(&buf), ((size_t)R * Tmax + R) * sizeof(int)));
     int rc = WM_OK;
-    std::vector<float> h2(16 * SEL_SP_HOST);
+    std::vector<float> h2(16 * SEL_SP);
     for (int r0 = 0; r0 < R && rc == WM_OK; r0 += 15) {
         const int n = std::min(15, R - r0);
         hipError_t e = hipMemcpyAsync(buf, prefixes + (size_t)r0 * Tmax, (size_t)n * Tmax * sizeof(int), hipMemcpyHostToDevice, st);
@@ -643,12 +650,12 @@ extern "C" int wm_select_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_tim
         e = hipMemcpyAsync(out_argmax + r0, ctx->amax, n * sizeof(int), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipMemcpyAsync(out_p_probe + r0, ctx->pc, n * sizeof(float), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipMemcpyAsync(out_ts_forced + r0, ctx->ts.forced, n * sizeof(int), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(h2.data(), ctx->part2, (size_t)n * SEL_SP_HOST * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(h2.data(), ctx->part2, (size_t)n * SEL_SP * sizeof(float), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) { ctx->err = std::string("wm_select_rows: ") + hipGetErrorString(e); rc = WM_ERR_HIP; break; }
         for (int r = 0; r < n; ++r) {
             float hs = 0.f;
-            for (int k = 0; k < SEL_SP_HOST; ++k) hs += h2[(size_t)r * SEL_SP_HOST + k];     // (k_accept's order)
+            for (int k = 0; k < SEL_SP; ++k) hs += h2[(size_t)r * SEL_SP + k];     // (k_accept's order)
             out_entropy[r0 + r] = -hs;
         }
     }
@@ -657,7 +664,7 @@ extern "C" int wm_select_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_tim
     return rc;
 }
 
-
+// forward(): one decoder pass over T tokens per stream at positions pos0.., K/V appended at row pos0.
 // Uses (and overwrites) the decode-loop state: call it before wm_decode_begin, or begin again afterwards.
 extern "C" int wm_forward_logits(wm_ctx* ctx, int B, const int32_t* tokens, int T, int pos0, int disable_medusa, float* logits_out)
 {
@@ -667,10 +674,8 @@ extern "C" int wm_forward_logits(wm_ctx* ctx, int B, const int32_t* tokens, int 
     const int Tids = ctx->Tal, K = ctx->K, V = ctx->V, nout = disable_medusa ? 1 : K + 1;
     GenDev g = ctx->gp;
     g.K = K; g.V = V; g.Vpad = ctx->Vpad; g.Tids = Tids; g.vanilla = 0;
-    ctx->gp = g; ctx->began = false; ctx->use_done = false; ctx->host_carry = false; ctx->dev_carry = false;
-    ctx->step_flow = false;                 // (wm_get_stats must not report the previous decode's schedule_steps for this pass)
-    if (ctx->graph) { hipGraphExecDestroy(ctx->graph); ctx->graph = nullptr; }
-    if (ctx->graph_base) { hipGraphExecDestroy(ctx->graph_base); ctx->graph_base = nullptr; }
+    ctx->gp = g;
+    wm_decode_invalidate(ctx, true);
     std::vector<float> rowbuf((size_t)nout * ctx->Vpad);
     for (int b = 0; b < B; ++b) {
         std::vector<int> v(T);

@@ -1,4 +1,4 @@
-// wm_internal.h — engine context shared by the three translation units of libwm.so.
+// wm_internal.h — engine context and internal interfaces shared by the translation units of libwm.so.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -72,6 +72,27 @@ __host__ __device__ __forceinline__ int4 ts_record(int4 st, int len, int begin, 
     if (len == begin) { fl |= 2; if (mit >= 0) hi = std::min(hi, tb + mit); }  // first sampled token: a timestamp <= max_initial
     return make_int4(lo, hi, fl, 0);
 }
+// A device buffer that only grows: reserve(n) keeps the allocation while it holds n elements, else frees it and allocates anew (the contents
+// are not carried over).  Converts to its pointer; freed with its owner.
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    operator T*() const { return p; }
+    hipError_t reserve(size_t n)
+    {
+        if (p && n <= cap) return hipSuccess;
+        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 1) * sizeof(T));
+        if (e == hipSuccess) cap = n;
+        return e;
+    }
+};
+
 // Static tables of the candidate tree (device memory; medusa_utils.py:305-421).  Nodes are numbered depth by depth.
 struct TreeDev {
     int n_nodes, n_paths, K, pad_;
@@ -218,16 +239,44 @@ int wm_dec_iter_rest(wm_ctx* ctx, int Mper_base);
 int wm_dec_step(wm_ctx* ctx, int);   // heads, candidates, verify pass, accept
 int wm_dec_profile(wm_ctx* ctx, int kernel, int rows, int reps, float* ms, double* bytes);
 int wm_dec_fold_init(wm_ctx* ctx);   // c = W gamma, b' = b + W beta of every LayerNorm-fed decoder GEMM (needs ctx->foldv)
-// Teacher-forced replay pass of the token-timestamp path (wm_align.hip): embed + decoder layers [0, n_layers) over Mper (<= 16) tokens of
-// streams [b0, b0 + nb) at positions kvlen[s].. (tokens ids[s][kvlen[s] ..]), exactly the launches of a base pass; after(ctx, l, arg) runs
-// behind layer l, while ctx->qbuf still holds that layer's cross-attention query rows (fp32 [nb * Mper][d], scaled by 0.125).
-int wm_dec_replay_layers(wm_ctx* ctx, int b0, int nb, int Mper, int n_layers, int (*after)(wm_ctx*, int, void*), void* arg);
+// Teacher-forced replay (token timestamps: wm_align.hip; token log-probabilities: wm_score.hip).  Input positions [0, npos) of streams
+// [b0, b0 + nb) go through embed + decoder layers [0, n_layers) in 16-row tiles, exactly the launches of a base pass.  The ids (tokens HOST
+// [.][Tmax], lens HOST, indexed by stream; zero past a stream's length: computed and ignored) are uploaded at the context's stride; a tile
+// sets kvlen to its first position pos0 and runs Mper = min(16, npos - pos0) rows.  Hooks (may be null): layer(ctx, l, pos0, Mper, arg)
+// behind layer l, while ctx->qbuf still holds its cross-attention query rows (fp32 [nb * Mper][d], scaled by 0.125); tile(ctx, pos0, Mper,
+// arg) behind the tile's last layer.  The caller has called wm_decode_invalidate and holds a wm_scalars_swap (below).
+struct wm_replay_hooks {
+    int (*layer)(wm_ctx*, int, int, int, void*) = nullptr;
+    int (*tile)(wm_ctx*, int, int, void*) = nullptr;
+    void* arg = nullptr;
+};
+int wm_dec_replay(wm_ctx* ctx, int b0, int nb, const int32_t* tokens, int Tmax, const int32_t* lens, int npos, int n_layers, const wm_replay_hooks& hooks);
+// a replay call's streams against the last encode: B <= Benc, lens in [1, min(Tmax, n_tgt)], n_prompt in [min_prompt, lens]; errors under `who`
+int wm_replay_check(wm_ctx* ctx, const char* who, int B, int Tmax, const int32_t* lens, const int32_t* n_prompt, int min_prompt);
 // implemented in wm_align.hip
 void wm_align_free(wm_ctx* ctx);
 // implemented in wm_score.hip
 void wm_score_free(wm_ctx* ctx);
-// implemented in wm_engine.hip: the timestamp scalars of a decode / tap / scoring call (ts == NULL: off); validation errors go to ctx->err
-int wm_ts_setup(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* ts, TsDev* out);
+// implemented in wm_engine.hip
+// The logits processors of a decode / tap / scoring call, derived in ONE place so that scoring applies exactly what the decode applied:
+// checks eos and the prompt pointer (errors under `who`), derives the timestamp scalars (tsp == NULL: off), fills the GenDev fields that depend on the parameter structs and
+// the context alone (P, eos, pad, exp_start, thr, alpha, begin, K, V, Vpad, Tids; the rest zero: the caller's) and uploads the suppress /
+// begin-suppress mask (ctx->supmask) and the length-penalty table (ctx->exppen).  Returns with the stream idle.
+int wm_proc_setup(wm_ctx* ctx, const char* who, const wm_gen_params* gp, const wm_timestamp_params* tsp, GenDev* g, TsDev* ts);
+// A call outside the decode loop (replay, parity tap, forward pass) overwrites what a decode in flight lives on (ids, L, kvlen, self K/V,
+// the processors' tables).  Clears `began` (wm_decode_run refuses until the next wm_decode_begin) and the modes the launches read off the
+// context: use_done (no early exit on the done flag), host_carry / dev_carry (no carried hidden rows), step_flow (no merged-step schedule;
+// wm_get_stats reports no schedule_steps).  The captured graphs depend only on GenDev / TsDev and buffer addresses: they are kept for a
+// following wm_decode_begin with the same parameters, unless drop_graphs (wm_forward_logits changes ctx->gp for good).
+void wm_decode_invalidate(wm_ctx* ctx, bool drop_graphs = false);
+// A call's own scalars in ctx->gp / ctx->ts for the lifetime of the object; the decode's come back on every exit path, so that
+// wm_decode_begin_ts still finds its captured graph.
+struct wm_scalars_swap {
+    wm_ctx* ctx; GenDev gp; TsDev ts;
+    wm_scalars_swap(wm_ctx* c, const GenDev& g, const TsDev& t) : ctx(c), gp(c->gp), ts(c->ts) { c->gp = g; c->ts = t; }
+    wm_scalars_swap(const wm_scalars_swap&) = delete;
+    ~wm_scalars_swap() { ctx->gp = gp; ctx->ts = ts; }
+};
 // timestamp parity tap (wm_select_rows): R <= 15 rows already in ctx->logits, probe tokens in cand[1 .. R], cur_len in L[0];
 // prefixes DEV [R][Tmax], lengths DEV [R]
 int wm_dec_select_rows(wm_ctx* ctx, const int* pre_dev, const int* len_dev, int R, int Tmax);

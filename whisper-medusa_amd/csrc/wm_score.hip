@@ -3,9 +3,9 @@
 // WhisperGenerationMixin._retrieve_avg_logprobs) and what WhisperNoSpeechDetection reads off the raw <|startoftranscript|> row, for an
 // engine whose Medusa loop emits several tokens per iteration under one shared length and never keeps a logits row.
 //
-//   replay         the final ids of every stream go through ALL decoder layers once more, teacher-forced, in 16-row tiles (the launches of a
-//                  base pass: wm_decoder.hip wm_dec_replay_layers), then the final LayerNorm and the packed vocabulary projection of the base
-//                  head for the tile's rows (no Medusa heads, no Medusa-Block extra layer)
+//   replay         the final ids of every stream go through ALL decoder layers once more, teacher-forced, in 16-row tiles (the shared driver
+//                  wm_dec_replay: wm_internal.h / wm_decoder.hip); behind every tile (score_tile) the final LayerNorm and the packed
+//                  vocabulary projection of the base head for the tile's rows (no Medusa heads, no Medusa-Block extra layer)
 //   k_score_build  one thread per stream: the tile's row descriptors — row of input position t - 1 scores s[t] under cur_len = t, its OWN
 //                  length — and, with the timestamp rules on, the row's record from the fold of its own prefix (carried from tile to tile)
 //   k_score1       SEL_SP slice blocks per row: running (max, sum of exp) at temperature 1 of the processed row, text region [0, tb) and
@@ -21,49 +21,27 @@
 #include "wm_select.h"
 
 struct wm_score_state {
-    int4 *desc = nullptr, *rec = nullptr, *sst = nullptr;   // [rows] {logits row, cur_len (< 0: raw row), target (< 0: skip), out index}, records; [maxB] fold state
-    float *p1 = nullptr, *p1t = nullptr, *out = nullptr;    // [rows][SEL_SP][4] text / timestamp partials; outputs
-    int *lens = nullptr, *npr = nullptr, *ibuf = nullptr;   // [maxB] each; tap: prefixes + lengths + targets
-    size_t cap_rows = 0, cap_out = 0, cap_b = 0, cap_ibuf = 0;
+    DevBuf<int4> desc, rec, sst;    // [rows] {logits row, cur_len (< 0: raw row), target (< 0: skip), out index}, records; [maxB] fold state
+    DevBuf<float> p1, p1t, out;     // [rows][SEL_SP][4] text / timestamp partials; outputs
+    DevBuf<int> lens, npr, ibuf;    // [maxB] each; tap: prefixes + lengths + targets
 };
 
 void wm_score_free(wm_ctx* ctx)
 {
-    wm_score_state* sc = ctx->score;
-    if (!sc) return;
-    void* bufs[] = {sc->desc, sc->rec, sc->sst, sc->p1, sc->p1t, sc->out, sc->lens, sc->npr, sc->ibuf};
-    for (void* b : bufs) if (b) hipFree(b);
-    delete sc;
+    delete ctx->score;
     ctx->score = nullptr;
-}
-
-template <class T>
-static hipError_t regrow(T** p, size_t n)
-{
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-    return hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(n, 1) * sizeof(T));
 }
 
 static int score_reserve(wm_ctx* ctx, size_t rows, size_t nout, size_t nb, size_t nibuf)
 {
     if (!ctx->score) ctx->score = new wm_score_state();
     wm_score_state* sc = ctx->score;
-    if (rows > sc->cap_rows) {
-        sc->cap_rows = 0;
-        WM_HIP(regrow(&sc->desc, rows)); WM_HIP(regrow(&sc->rec, rows));
-        WM_HIP(regrow(&sc->p1, rows * SEL_SP * 4)); WM_HIP(regrow(&sc->p1t, rows * SEL_SP * 4));
-        sc->cap_rows = rows;
-    }
-    if (nout > sc->cap_out) { sc->cap_out = 0; WM_HIP(regrow(&sc->out, nout)); sc->cap_out = nout; }
-    if (nb > sc->cap_b) { sc->cap_b = 0; WM_HIP(regrow(&sc->lens, nb)); WM_HIP(regrow(&sc->npr, nb)); WM_HIP(regrow(&sc->sst, nb)); sc->cap_b = nb; }
-    if (nibuf > sc->cap_ibuf) { sc->cap_ibuf = 0; WM_HIP(regrow(&sc->ibuf, nibuf)); sc->cap_ibuf = nibuf; }
+    WM_HIP(sc->desc.reserve(rows)); WM_HIP(sc->rec.reserve(rows));
+    WM_HIP(sc->p1.reserve(rows * SEL_SP * 4)); WM_HIP(sc->p1t.reserve(rows * SEL_SP * 4));
+    WM_HIP(sc->out.reserve(nout));
+    WM_HIP(sc->lens.reserve(nb)); WM_HIP(sc->npr.reserve(nb)); WM_HIP(sc->sst.reserve(nb));
+    WM_HIP(sc->ibuf.reserve(nibuf));
     return WM_OK;
-}
-
-__global__ void k_score_fill(int* __restrict__ p, int n, int v)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = v;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -198,37 +176,14 @@ __global__ void k_score2(const float* __restrict__ logits, GenDev gp, const unsi
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-// the processors' scalars and tables of a scoring call: what wm_decode_begin_ts derives from the same structs
-static int score_setup(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* tsp, const char* who, GenDev* g_out, TsDev* ts_out)
+// the processors of a scoring call: the decode's own (wm_proc_setup) as a plain greedy step sees them — temperature 1, typical mode, no
+// length limit below n_tgt; vanilla: the final stage stops at the LayerNorm (no Medusa-Block extra layer)
+static int score_setup(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* tsp, const char* who, GenDev* g, TsDev* ts)
 {
-    if (gp->eos_token_id < 0 || gp->eos_token_id >= ctx->V) { ctx->err = std::string(who) + ": eos out of range"; return WM_ERR_ARG; }
-    if (gp->prompt_len < 0 || (gp->prompt_len > 0 && !gp->prompt)) { ctx->err = std::string(who) + ": bad prompt"; return WM_ERR_ARG; }
-    hipStream_t st = ctx->stream;
-    TsDev ts{};
-    if (int rc = wm_ts_setup(ctx, gp, tsp, &ts)) return rc;
-    const int P = gp->prompt_len, Tids = ctx->Tal;
-    GenDev g{};
-    g.P = P; g.eos = gp->eos_token_id; g.pad = gp->pad_token_id;
-    g.max_length = g.hard_max_length = ctx->Tmax;
-    g.exp_start = gp->exp_decay_start >= 0 ? gp->exp_decay_start + P : -1;
-    g.thr = gp->posterior_threshold; g.alpha = gp->posterior_alpha; g.inv_temp = 1.0f;
-    g.force_accept = -1;
-    g.begin = gp->begin_index >= 0 ? gp->begin_index : P;
-    if (ts.on && tsp->begin_index >= 0) g.begin = tsp->begin_index;
-    g.accept_mode = WM_ACCEPT_TYPICAL; g.vanilla = 1;       // vanilla: the final stage stops at the LayerNorm (no Medusa-Block extra layer)
-    g.K = ctx->K; g.V = ctx->V; g.Vpad = ctx->Vpad; g.Tids = Tids;
-    std::vector<unsigned char> mask(ctx->Vpad, 0);
-    for (int i = 0; i < gp->n_suppress; ++i) if (gp->suppress[i] >= 0 && gp->suppress[i] < ctx->V) mask[gp->suppress[i]] |= 1;
-    for (int i = 0; i < gp->n_begin_suppress; ++i)
-        if (gp->begin_suppress[i] >= 0 && gp->begin_suppress[i] < ctx->V) mask[gp->begin_suppress[i]] |= 2;
-    std::vector<float> pen(Tids + 1, 0.f);
-    if (g.exp_start >= 0)
-        for (int t = 0; t <= Tids; ++t)     // (factor^(cur_len - start) - 1) evaluated in double like the Python scalar (wm_decode_begin_ts)
-            pen[t] = t > g.exp_start ? (float)(std::pow((double)gp->exp_decay_factor, (double)(t - g.exp_start)) - 1.0) : 0.f;
-    WM_HIP(hipMemcpyAsync(ctx->supmask, mask.data(), mask.size(), hipMemcpyHostToDevice, st));
-    WM_HIP(hipMemcpyAsync(ctx->exppen, pen.data(), pen.size() * sizeof(float), hipMemcpyHostToDevice, st));
-    WM_HIP(hipStreamSynchronize(st));      // host vectors go out of scope
-    *g_out = g; *ts_out = ts;
+    if (int rc = wm_proc_setup(ctx, who, gp, tsp, g, ts)) return rc;
+    g->max_length = g->hard_max_length = ctx->Tmax;
+    g->inv_temp = 1.0f; g->force_accept = -1;
+    g->accept_mode = WM_ACCEPT_TYPICAL; g->vanilla = 1;
     return WM_OK;
 }
 
@@ -244,48 +199,30 @@ static int score_launch(wm_ctx* ctx, const GenDev& g, const TsDev& ts, int nrows
     return WM_OK;
 }
 
-static int score_tokens_run(wm_ctx* ctx, const GenDev& g, const TsDev& ts, int ns_id, int sot, int B, const int32_t* tokens, int Tmax,
-                            const int32_t* lens, const int32_t* n_prompt, float* logprobs, float* no_speech_prob)
+struct ScoreCall {
+    GenDev g; TsDev ts;
+    int ns_id, sot, B, Tmax;
+    const int32_t *lens, *n_prompt;
+};
+
+// behind the layers of a tile: its row descriptors, then — for a tile that holds a scored row — final LayerNorm, base head, scores
+static int score_tile(wm_ctx* ctx, int pos0, int Mper, void* arg)
 {
-    hipStream_t st = ctx->stream;
-    const int Tids = ctx->Tal;
-    if (int rc = score_reserve(ctx, (size_t)B * 17, (size_t)B * Tmax + B, (size_t)B, 0)) return rc;
+    const ScoreCall& c = *static_cast<const ScoreCall*>(arg);
     wm_score_state* sc = ctx->score;
-    std::vector<int> ids((size_t)B * Tids, 0);      // rows past a stream's length: token 0, computed and ignored
-    int npos = 0;
-    for (int b = 0; b < B; ++b) {
-        for (int t = 0; t < lens[b]; ++t) ids[(size_t)b * Tids + t] = tokens[(size_t)b * Tmax + t];
-        npos = std::max(npos, std::max(lens[b] - 1, ns_id >= 0 ? sot + 1 : 0));
-    }
-    WM_HIP(hipMemcpyAsync(ctx->ids, ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    WM_HIP(hipMemcpyAsync(sc->lens, lens, B * sizeof(int), hipMemcpyHostToDevice, st));
-    WM_HIP(hipMemcpyAsync(sc->npr, n_prompt, B * sizeof(int), hipMemcpyHostToDevice, st));
-    WM_HIP(hipMemsetAsync(sc->out, 0, ((size_t)B * Tmax + B) * sizeof(float), st));
-    WM_HIP(hipStreamSynchronize(st));
-    for (int pos0 = 0; pos0 < npos; pos0 += 16) {
-        const int Mper = std::min(16, npos - pos0);
-        hipLaunchKernelGGL(k_score_fill, dim3((B + 63) / 64), dim3(64), 0, st, ctx->kvlen, B, pos0);
-        WM_HIP(hipGetLastError());
-        if (int rc = wm_dec_replay_layers(ctx, 0, B, Mper, ctx->cfg.dec_layers, nullptr, nullptr)) return rc;
-        // EVERY tile folds its tokens into the streams' timestamp state (k_score_build resets it at pos0 == 0 and carries it in sst): a long
-        // prompt's tokens — prompt_ids may hold timestamps of previous text — reach the records of the later tiles as they reach the decode's
-        hipLaunchKernelGGL(k_score_build, dim3((B + 63) / 64), dim3(64), 0, st, ctx->ids, Tids, sc->lens, sc->npr, B, pos0, Mper, g, ts, sot, ns_id,
-                           Tmax, B * Tmax, sc->sst, sc->desc, sc->rec);
-        WM_HIP(hipGetLastError());
-        // logits only for a tile that holds a scored row (a long prompt's leading tiles are wanted for their K/V and their fold alone)
-        bool need = ns_id >= 0 && sot >= pos0 && sot < pos0 + Mper;
-        for (int b = 0; b < B && !need; ++b) need = std::max(n_prompt[b], pos0 + 1) < std::min(lens[b], pos0 + Mper + 1);
-        if (!need) continue;
-        if (int rc = wm_dec_stage_final(ctx, 0, B, Mper, 0, 0)) return rc;
-        if (int rc = wm_dec_stage_heads(ctx, B * Mper, 1, 0, 0)) return rc;
-        if (int rc = score_launch(ctx, g, ts, B * Mper + B)) return rc;
-    }
-    std::vector<float> ns(B, 0.f);
-    WM_HIP(hipMemcpyAsync(logprobs, sc->out, (size_t)B * Tmax * sizeof(float), hipMemcpyDeviceToHost, st));
-    WM_HIP(hipMemcpyAsync(ns.data(), sc->out + (size_t)B * Tmax, B * sizeof(float), hipMemcpyDeviceToHost, st));
-    WM_HIP(hipStreamSynchronize(st));
-    if (no_speech_prob) for (int b = 0; b < B; ++b) no_speech_prob[b] = ns_id >= 0 ? (float)std::exp((double)ns[b]) : 0.f;
-    return WM_OK;
+    const int B = c.B;
+    // EVERY tile folds its tokens into the streams' timestamp state (k_score_build resets it at pos0 == 0 and carries it in sst): a long
+    // prompt's tokens — prompt_ids may hold timestamps of previous text — reach the records of the later tiles as they reach the decode's
+    hipLaunchKernelGGL(k_score_build, dim3((B + 63) / 64), dim3(64), 0, ctx->stream, ctx->ids, ctx->Tal, sc->lens, sc->npr, B, pos0, Mper, c.g, c.ts,
+                       c.sot, c.ns_id, c.Tmax, B * c.Tmax, sc->sst, sc->desc, sc->rec);
+    WM_HIP(hipGetLastError());
+    // logits only for a tile that holds a scored row (a long prompt's leading tiles are wanted for their K/V and their fold alone)
+    bool need = c.ns_id >= 0 && c.sot >= pos0 && c.sot < pos0 + Mper;
+    for (int b = 0; b < B && !need; ++b) need = std::max(c.n_prompt[b], pos0 + 1) < std::min(c.lens[b], pos0 + Mper + 1);
+    if (!need) return WM_OK;
+    if (int rc = wm_dec_stage_final(ctx, 0, B, Mper, 0, 0)) return rc;
+    if (int rc = wm_dec_stage_heads(ctx, B * Mper, 1, 0, 0)) return rc;
+    return score_launch(ctx, c.g, c.ts, B * Mper + B);
 }
 
 extern "C" int wm_score_tokens(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* tsp, const wm_score_params* sp, int B,
@@ -294,38 +231,44 @@ extern "C" int wm_score_tokens(wm_ctx* ctx, const wm_gen_params* gp, const wm_ti
 {
     if (!ctx) return WM_ERR_ARG;
     if (!gp || !tokens || !lens || !n_prompt || !logprobs || B < 1 || Tmax < 1) { ctx->err = "wm_score_tokens: bad arguments"; return WM_ERR_ARG; }
-    if (ctx->Benc < 1) { ctx->err = "wm_score_tokens: call wm_encode first"; return WM_ERR_STATE; }
-    if (B > ctx->Benc || B * 16 > ctx->Rcap) { ctx->err = "wm_score_tokens: more streams than the last wm_encode"; return WM_ERR_ARG; }
-    const int ns_id = (sp && no_speech_prob) ? sp->no_speech_token_id : -1;
-    const int sot = (sp && sp->sot_index >= 0) ? sp->sot_index : 0;
-    if (ns_id >= ctx->V) { ctx->err = "wm_score_tokens: no_speech_token_id outside the vocabulary"; return WM_ERR_ARG; }
+    if (int rc = wm_replay_check(ctx, "wm_score_tokens", B, Tmax, lens, n_prompt, 1)) return rc;
+    ScoreCall c{};
+    c.ns_id = (sp && no_speech_prob) ? sp->no_speech_token_id : -1;
+    c.sot = (sp && sp->sot_index >= 0) ? sp->sot_index : 0;
+    c.B = B; c.Tmax = Tmax; c.lens = lens; c.n_prompt = n_prompt;
+    if (c.ns_id >= ctx->V) { ctx->err = "wm_score_tokens: no_speech_token_id outside the vocabulary"; return WM_ERR_ARG; }
+    int npos = 0;
     for (int b = 0; b < B; ++b) {
-        if (lens[b] < 1 || lens[b] > ctx->Tmax || lens[b] > Tmax) { ctx->err = "wm_score_tokens: lens must be in [1, min(Tmax, n_tgt)]"; return WM_ERR_ARG; }
-        if (n_prompt[b] < 1 || n_prompt[b] > lens[b]) { ctx->err = "wm_score_tokens: n_prompt must be in [1, lens]"; return WM_ERR_ARG; }
-        if (ns_id >= 0 && sot >= n_prompt[b]) { ctx->err = "wm_score_tokens: sot_index must lie inside the prompt"; return WM_ERR_ARG; }
+        if (c.ns_id >= 0 && c.sot >= n_prompt[b]) { ctx->err = "wm_score_tokens: sot_index must lie inside the prompt"; return WM_ERR_ARG; }
         for (int t = 0; t < lens[b]; ++t)
             if (tokens[(size_t)b * Tmax + t] < 0 || tokens[(size_t)b * Tmax + t] >= ctx->V) {
                 ctx->err = "wm_score_tokens: target outside the vocabulary (stream " + std::to_string(b) + ", position " + std::to_string(t) + ")";
                 return WM_ERR_ARG;
             }
+        npos = std::max(npos, std::max(lens[b] - 1, c.ns_id >= 0 ? c.sot + 1 : 0));
     }
     WM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    GenDev g{}; TsDev ts{};
-    if (int rc = score_setup(ctx, gp, tsp, "wm_score_tokens", &g, &ts)) return rc;
-    // the replay overwrites the decode state (ids, kvlen, self K/V, the processors' tables): begin again afterwards.  The decode's scalars
-    // come back, so that a following wm_decode_begin with the same parameters still finds its captured graph.
-    const GenDev g_keep = ctx->gp; const TsDev ts_keep = ctx->ts;
-    ctx->gp = g; ctx->ts = ts;
-    ctx->began = false; ctx->use_done = false; ctx->host_carry = false; ctx->dev_carry = false; ctx->step_flow = false;
+    if (int rc = score_setup(ctx, gp, tsp, "wm_score_tokens", &c.g, &c.ts)) return rc;
+    if (int rc = score_reserve(ctx, (size_t)B * 17, (size_t)B * Tmax + B, (size_t)B, 0)) return rc;
+    wm_score_state* sc = ctx->score;
+    // the replay overwrites the decode state (ids, kvlen, self K/V, the processors' tables): begin again afterwards
+    wm_decode_invalidate(ctx);
+    wm_scalars_swap swap(ctx, c.g, c.ts);
     for (size_t i = 0; i < (size_t)B * Tmax; ++i) logprobs[i] = 0.f;
-    hipError_t e = hipEventRecord(ctx->ev0, st);
-    int rc = e == hipSuccess ? score_tokens_run(ctx, g, ts, ns_id, sot, B, tokens, Tmax, lens, n_prompt, logprobs, no_speech_prob) : WM_ERR_HIP;
-    if (e != hipSuccess) ctx->err = std::string("wm_score_tokens: ") + hipGetErrorString(e);
-    ctx->gp = g_keep; ctx->ts = ts_keep;
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    WM_HIP(hipEventRecord(ctx->ev0, st));
+    WM_HIP(hipMemcpyAsync(sc->lens, lens, B * sizeof(int), hipMemcpyHostToDevice, st));
+    WM_HIP(hipMemcpyAsync(sc->npr, n_prompt, B * sizeof(int), hipMemcpyHostToDevice, st));
+    WM_HIP(hipMemsetAsync(sc->out, 0, ((size_t)B * Tmax + B) * sizeof(float), st));
+    wm_replay_hooks hk; hk.tile = score_tile; hk.arg = &c;
+    if (int rc = wm_dec_replay(ctx, 0, B, tokens, Tmax, lens, npos, ctx->cfg.dec_layers, hk)) return rc;
+    std::vector<float> ns(B, 0.f);
+    WM_HIP(hipMemcpyAsync(logprobs, sc->out, (size_t)B * Tmax * sizeof(float), hipMemcpyDeviceToHost, st));
+    WM_HIP(hipMemcpyAsync(ns.data(), sc->out + (size_t)B * Tmax, B * sizeof(float), hipMemcpyDeviceToHost, st));
+    WM_HIP(hipStreamSynchronize(st));
     WM_HIP(hipEventRecord(ctx->ev1, st));
     WM_HIP(hipEventSynchronize(ctx->ev1));
+    if (no_speech_prob) for (int b = 0; b < B; ++b) no_speech_prob[b] = c.ns_id >= 0 ? (float)std::exp((double)ns[b]) : 0.f;
     if (ms) WM_HIP(hipEventElapsedTime(ms, ctx->ev0, ctx->ev1));
     return WM_OK;
 }
@@ -343,7 +286,7 @@ extern "C" int wm_score_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_time
     hipStream_t st = ctx->stream;
     GenDev g{}; TsDev ts{};
     if (int rc = score_setup(ctx, gp, tsp, "wm_score_rows", &g, &ts)) return rc;
-    ctx->began = false;
+    wm_decode_invalidate(ctx);       // (the processors' tables are the tap's now)
     const int G = ctx->Rcap;                   // rows per group: what the logits scratch holds
     if (int rc = score_reserve(ctx, (size_t)G, (size_t)G, 0, (size_t)G * Tmax + 2 * G)) return rc;
     wm_score_state* sc = ctx->score;

@@ -299,6 +299,19 @@ class Engine:
                 break
         return [self.tokens(b) for b in range(B)]
 
+    @staticmethod
+    def _pack_ids(lists: Sequence[Sequence[int]], n_prompt=None):
+        """Ragged id lists -> (int32 [B, Tmax] zero-padded, int32 [B] lengths, Tmax >= 1, int32 [B] ``n_prompt`` broadcast from an int or
+        one per list; None when not given)."""
+        B = len(lists)
+        Tmax = max(max(len(s) for s in lists), 1)
+        tok = np.zeros((B, Tmax), dtype=np.int32)
+        for b, s in enumerate(lists):
+            tok[b, : len(s)] = s
+        lens = np.array([len(s) for s in lists], dtype=np.int32)
+        npr = None if n_prompt is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n_prompt, dtype=np.int32), (B,)))
+        return tok, lens, Tmax, npr
+
     def select_rows(self, gp: GenParams, logits: np.ndarray, prefixes: Sequence[Sequence[int]], probe_tokens: Sequence[int]) -> dict:
         """Timestamp parity tap (wm_select_rows): rows ``logits [R, V]`` as verify rows with the given prefixes, through the decode loop's
         state fold and select kernels.  Returns numpy arrays argmax, p_probe, entropy, ts_forced (the log-softmax decision masked all text)."""
@@ -306,11 +319,7 @@ class Engine:
         R, V = x.shape
         if V != self.cfg.vocab_size or len(prefixes) != R or len(probe_tokens) != R:
             raise ValueError("select_rows: logits must be [R, vocab] with one prefix and one probe token per row")
-        Tmax = max(len(p) for p in prefixes)
-        pre = np.zeros((R, Tmax), dtype=np.int32)
-        for r, p in enumerate(prefixes):
-            pre[r, : len(p)] = p
-        lens = np.array([len(p) for p in prefixes], dtype=np.int32)
+        pre, lens, Tmax, _ = self._pack_ids(prefixes)
         probe = np.ascontiguousarray(probe_tokens, dtype=np.int32)
         am = np.zeros(R, np.int32); pp = np.zeros(R, np.float32); H = np.zeros(R, np.float32); fo = np.zeros(R, np.int32)
         g, _keep = self._gen_struct(gp)
@@ -331,12 +340,7 @@ class Engine:
         Returns (numpy float32 [B, max len] seconds, ms).  Overwrites the decode state."""
         B = len(seqs)
         heads = np.ascontiguousarray(alignment_heads, dtype=np.int32).reshape(-1, 2)
-        Tmax = max(max(len(s) for s in seqs), 1)
-        tok = np.zeros((B, Tmax), dtype=np.int32)
-        for b, s in enumerate(seqs):
-            tok[b, : len(s)] = s
-        lens = np.array([len(s) for s in seqs], dtype=np.int32)
-        npr = np.ascontiguousarray(np.broadcast_to(np.asarray(n_prompt, dtype=np.int32), (B,)))
+        tok, lens, Tmax, npr = self._pack_ids(seqs, n_prompt)
         nf = None if num_frames is None else np.ascontiguousarray(np.broadcast_to(np.asarray(num_frames, dtype=np.int32), (B,)))
         out = np.zeros((B, Tmax), dtype=np.float32)
         ms = C.c_float(0)
@@ -387,12 +391,7 @@ class Engine:
         Returns (numpy float32 [B, max len] log-probabilities — 0 inside the prompt and after a stream's end —, numpy float32 [B]
         no-speech probabilities or None, ms).  Overwrites the decode state."""
         B = len(seqs)
-        Tmax = max(max(len(s) for s in seqs), 1)
-        tok = np.zeros((B, Tmax), dtype=np.int32)
-        for b, s in enumerate(seqs):
-            tok[b, : len(s)] = s
-        lens = np.array([len(s) for s in seqs], dtype=np.int32)
-        npr = np.ascontiguousarray(np.broadcast_to(np.asarray(n_prompt, dtype=np.int32), (B,)))
+        tok, lens, Tmax, npr = self._pack_ids(seqs, n_prompt)
         out = np.zeros((B, Tmax), dtype=np.float32)
         want_ns = no_speech_token_id is not None and int(no_speech_token_id) >= 0
         nsp = np.zeros(B, dtype=np.float32)
@@ -414,11 +413,7 @@ class Engine:
         R, V = x.shape
         if V != self.cfg.vocab_size or len(prefixes) != R or len(targets) != R:
             raise ValueError("score_rows: logits must be [R, vocab] with one prefix and one target per row")
-        Tmax = max(len(p) for p in prefixes)
-        pre = np.zeros((R, Tmax), dtype=np.int32)
-        for r, p in enumerate(prefixes):
-            pre[r, : len(p)] = p
-        lens = np.array([len(p) for p in prefixes], dtype=np.int32)
+        pre, lens, Tmax, _ = self._pack_ids(prefixes)
         tgt = np.ascontiguousarray(targets, dtype=np.int32)
         out = np.zeros(R, np.float32)
         g, _keep = self._gen_struct(gp)
