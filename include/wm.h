@@ -190,6 +190,25 @@ typedef struct wm_timestamp_params {
     int32_t begin_index;                 /* the processor's begin_index (ids[begin_index:] are the sampled tokens); < 0: the wm_gen_params one */
 } wm_timestamp_params;
 
+/* Repetition rules (additive to ABI v9).  Stand in for HF RepetitionPenaltyLogitsProcessor and NoRepeatNGramLogitsProcessor
+ * (transformers generation/logits_process.py), which GenerationMixin._get_logits_processor puts FIRST in the chain for
+ * generation_config.repetition_penalty / no_repeat_ngram_size; the reference ignores both fields (its generate() never builds them,
+ * model.py:1168-1207).  For a logits row with prefix `pre` (all ids the row follows, decoder prompt included):
+ *   1. penalty p: every token n of set(pre): x[n] = x[n] < 0 ? x[n] * p : x[n] / p  (on the raw fp32 logit, a true division);
+ *   2. n-gram size g, len(pre) >= g: every token that followed an earlier occurrence of pre[len-g+1:] inside pre becomes -inf
+ *      (g == 1: every token of pre);
+ *   then the processors of wm_gen_params, then the timestamp rules.  A banned token is -inf whatever follows (HF: a banned EOS under
+ *   the exponential decay is -inf + inf * k = NaN; the engine keeps -inf — the one deviation).
+ * Prefixes are each row's OWN (the convention of the timestamp rules): base / Medusa-head rows of a stream the committed ids[:L], verify
+ * row i ids[:L] + c_0 .. c_i, a scored position t ids[:t], a tap row its given prefix.  The select kernels derive both sets from the ids
+ * on the device (no per-stream state): sibling rows (wm_config.sibling_rows) stay on and the hidden-state carry needs nothing new — a
+ * carried row is selected in the next iteration, under the ids committed by then.
+ * Sticky on the context until cleared (NULL, or p == 1 and g == 0); read by wm_decode_begin, wm_decode_begin_ts, wm_score_tokens,
+ * wm_select_rows (whose timestamp argument may then be NULL) and wm_score_rows.  WM_ERR_ARG (wm_last_error says why): p <= 0 or not finite,
+ * g < 0 or g > n_tgt; and from the calls that read them: a candidate tree (medusa_choices with top-k > 1) while rules are on. */
+typedef struct wm_repeat_params { float repetition_penalty; int32_t no_repeat_ngram_size; } wm_repeat_params;
+int wm_set_repeat_rules(wm_ctx* ctx, const wm_repeat_params* rp /* NULL = off */);
+
 /* ---- F3..F14 the Medusa decode loop (replaces _medusa_greedy_search, model.py:404-835) ---- */
 int wm_decode_begin(wm_ctx* ctx, const wm_gen_params* gp, int B);
 /* wm_decode_begin with the timestamp rules on (ts != NULL; NULL = wm_decode_begin).  WM_ERR_ARG (wm_last_error says why): a candidate tree

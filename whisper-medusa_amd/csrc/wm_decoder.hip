@@ -689,9 +689,15 @@ select1_body(const float* __restrict__ logits, const GenDev& gp, const unsigned 
     const int per = (gp.V + SEL_SP - 1) / SEL_SP, n0 = sp * per, n1 = min(gp.V, n0 + per);
     int4 rec = make_int4(0, 0, 0, 0);
     if (TS) rec = ts_row_record(gp, ts, ts_verify, s, ri_i, cur_len);
+    extern __shared__ unsigned rp_sh[];
+    const bool rp = TS && ts.rp != 0;               // repetition rules: the slice's two token sets from the row's own prefix
+    if (rp) rp_build(ts, rp_row_prefix(ts, ts_verify, s, ri_i, cur_len), n0, n1, -1, gp.V, rp_sh, tid, 256);
     auto pl = [&](int n) {
-        float v = proc_logit(x[n], n, cur_len, gp, mask, exppen);
+        float v = x[n];
+        if (rp) v = rp_pen(v, n, n0, ts, rp_sh);
+        v = proc_logit(v, n, cur_len, gp, mask, exppen);
         if (TS) v = ts_mask(v, n, rec, gp, ts);
+        if (rp && rp_banned(n, n0, gp.V, rp_sh)) v = -INFINITY;
         return v;
     };
     float mx = -INFINITY; int mi = 0x7fffffff;
@@ -813,7 +819,7 @@ select2_body(const float* __restrict__ logits, const GenDev& gp, const unsigned 
         // verify rows only: the record k_cand_fin folded from c_0 .. c_i; text masked when the row's decision says so
         const TsSel f = ts_finish(p1, ts.part1t + (size_t)row * SEL_SP * 4, gp.inv_temp);
         mx = f.mx; mi = f.mi; invz = 1.0f / f.z; forced = f.forced;
-        rec = ts.ver[s * WM_CAND_STRIDE + i];
+        rec = ts_row_record(gp, ts, 1, s, i, cur_len);
     } else {
 #pragma unroll
         for (int k = 0; k < SEL_SP; ++k) {
@@ -828,12 +834,28 @@ select2_body(const float* __restrict__ logits, const GenDev& gp, const unsigned 
         }
         invz = 1.0f / z;
     }
+    const int per = (gp.V + SEL_SP - 1) / SEL_SP, n0 = sp * per, n1 = min(gp.V, n0 + per);
+    extern __shared__ unsigned rp_sh[];
+    const bool rp = TS && ts.rp != 0;
+    const int probe = (TS && i + 1 < rps) ? cand[s * WM_CAND_STRIDE + i + 1] : -1;
+    if (rp) rp_build(ts, rp_row_prefix(ts, 1, s, i, cur_len), n0, n1, probe, gp.V, rp_sh, tid, 256);
     auto pl = [&](int n) {
-        float v = proc_logit(x[n], n, cur_len, gp, mask, exppen);
+        float v = x[n];
+        if (rp) v = rp_pen(v, n, n0, ts, rp_sh);
+        v = proc_logit(v, n, cur_len, gp, mask, exppen);
         if (TS) { v = ts_mask(v, n, rec, gp, ts); if (forced && n < ts.tb) v = -INFINITY; }
+        if (rp && rp_banned(n, n0, gp.V, rp_sh)) v = -INFINITY;
         return v;
     };
-    const int per = (gp.V + SEL_SP - 1) / SEL_SP, n0 = sp * per, n1 = min(gp.V, n0 + per);
+    // the probe token may lie outside this slice: its two bits come from rp_build's flags word
+    auto pl_probe = [&](int n) {
+        float v = x[n];
+        if (rp && (rp_sh[0] & 1u)) v = rp_penalise(v, ts.rp_pen);
+        v = proc_logit(v, n, cur_len, gp, mask, exppen);
+        if (TS) { v = ts_mask(v, n, rec, gp, ts); if (forced && n < ts.tb) v = -INFINITY; }
+        if (rp && (rp_sh[0] & 2u)) v = -INFINITY;
+        return v;
+    };
     float hs = 0.f;
     for (int n = n0 + tid; n < n1; n += 256) {
         const float v = pl(n);
@@ -863,7 +885,7 @@ select2_body(const float* __restrict__ logits, const GenDev& gp, const unsigned 
                 float pcv = 0.f;
                 if (i + 1 < rps) {
                     const int c = cand[s * WM_CAND_STRIDE + i + 1];
-                    const float vc = pl(c);
+                    const float vc = pl_probe(c);
                     pcv = (vc == -INFINITY) ? 0.f : expf((vc - mx) * gp.inv_temp) * invz;
                 }
                 pc[orow] = pcv;
@@ -947,7 +969,7 @@ cand_fin_body(const float* __restrict__ part1, const GenDev& gp, int* __restrict
     }
     if (TS) {
         __syncthreads();
-        if (tid == 0) {
+        if (tid == 0 && ts.on) {
             int4 st = ts.st[s];
             const int len = ts.L[s];
             for (int i = 0; i < rps; ++i) {
@@ -1098,7 +1120,7 @@ accept_body(const GenDev& gp, const int* __restrict__ cand, const int* __restric
     if (sel_n != nullptr && lane < 16) sel_src[s * 16 + lane] = (lane == 1 && sib_row >= 0) ? sib_row : lane;
     if (lane == 0) {
         const int Ln = Lcur + n_emit;
-        if (TS) {
+        if (TS && ts.on) {
             int4 st = ts.st[s];
             for (int j = 0; j < n_emit; ++j) st = ts_fold(st, (a == 0 && j == 1) ? amax[row0] : cand[s * WM_CAND_STRIDE + j], ts.tb);
             ts.st[s] = st;
@@ -1324,7 +1346,7 @@ accept_vanilla1_body(const GenDev& gp, int B, const int* __restrict__ amax, int*
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= B || finished[s]) return;
     const int Lcur = L[s], tok = amax[s];
-    if (TS) ts.st[s] = ts_fold(ts.st[s], tok, ts.tb);
+    if (TS && ts.on) ts.st[s] = ts_fold(ts.st[s], tok, ts.tb);
     if (Lcur < gp.Tids) ids[(size_t)s * gp.Tids + Lcur] = tok;
     L[s] = Lcur + 1; kvlen[s] = Lcur; niter[s] += 1;
     atomicAdd(reinterpret_cast<unsigned long long*>(hist + 16), 1ull);
@@ -1795,15 +1817,16 @@ int wm_dec_iteration(wm_ctx* ctx, int Mper_base)
     const int B = ctx->Bdec, K = ctx->K, rps = K + 1;
     const GenDev gp = ctx->gp;
     const TsDev ts = ctx->ts;
+    const size_t lds = rp_lds_bytes(ts, gp.V);
     if (gp.vanilla) {
         const int chunk = B;
         for (int b0 = 0; b0 < B; b0 += chunk) {
             const int nb = min(chunk, B - b0);
             int rc = wm_dec_pass(ctx, b0, nb, Mper_base, 0, 0, 0);
             if (rc) return rc;
-            if (ts.on) {            // (committed-state records: ts.st of stream b0 + row)
-                TsDev tsb = ts; tsb.st += b0;
-                k_select1_ts<false><<<dim3(SEL_SP, nb), dim3(256), 0, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L + b0, 1,
+            if (wm_rules_on(ts)) {  // (committed-state records: ts.st of stream b0 + row; prefix ids of stream b0 + row)
+                TsDev tsb = ts; tsb.st += b0; tsb.rp_ids += (size_t)b0 * ts.rp_stride;
+                k_select1_ts<false><<<dim3(SEL_SP, nb), dim3(256), lds, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L + b0, 1,
                                                                                ctx->part1, nullptr, nullptr, tsb, 0);
                 WM_HIP(hipGetLastError());
                 k_select_argmax_ts<<<dim3((nb + 63) / 64), dim3(64), 0, st>>>(ctx->part1, nb, b0, ctx->amax, ts);
@@ -1816,7 +1839,7 @@ int wm_dec_iteration(wm_ctx* ctx, int Mper_base)
             hipLaunchKernelGGL(k_select_argmax, dim3((nb + 63) / 64), dim3(64), 0, st, ctx->part1, nb, b0, ctx->amax);
             WM_HIP(hipGetLastError());
         }
-        if (ts.on)
+        if (wm_rules_on(ts))
             k_accept_vanilla1_ts<<<dim3((B + 63) / 64), dim3(64), 0, st>>>(gp, B, ctx->amax, ctx->ids, ctx->L, ctx->kvlen, ctx->finished,
                                                                                ctx->niter, ctx->hist, ctx->done, ts);
         else
@@ -1845,6 +1868,7 @@ int wm_dec_iter_rest(wm_ctx* ctx, int Mper_base)
     const int B = ctx->Bdec, K = ctx->K, rps = K + 1, nb = B;
     const GenDev gp = ctx->gp;
     const TsDev ts = ctx->ts;
+    const size_t lds = rp_lds_bytes(ts, gp.V);
     const bool carry = ctx->host_carry;
     ctx->hf_cur = ctx->hf;
     g_skinny_done = ctx->use_done ? ctx->done : nullptr;
@@ -1858,8 +1882,8 @@ int wm_dec_iter_rest(wm_ctx* ctx, int Mper_base)
     } else {
         // slice partials of every head's row (head 1's slices also keep their six best when the verify pass carries sibling rows), then ONE
         // block per stream turns them into the chain's candidates (+ the sibling tokens)
-        if (ts.on) {
-            k_select1_ts<false><<<dim3(SEL_SP, nb * rps), dim3(256), 0, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, rps, ctx->part1,
+        if (wm_rules_on(ts)) {
+            k_select1_ts<false><<<dim3(SEL_SP, nb * rps), dim3(256), lds, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, rps, ctx->part1,
                                                                                  nullptr, gp.sib > 0 ? ctx->sibpart : nullptr, ts, 0);
             WM_HIP(hipGetLastError());
             k_cand_fin_ts<<<dim3(nb), dim3(256), 0, st>>>(ctx->part1, gp, ctx->amax, ctx->cand, gp.sib > 0 ? ctx->sibpart : nullptr, ts);
@@ -1885,12 +1909,12 @@ int wm_dec_iter_rest(wm_ctx* ctx, int Mper_base)
     } else
         rc = wm_dec_pass(ctx, 0, nb, vr, 1, 0, 1);
     if (rc) return rc;
-    if (ts.on) {            // (chain only: timestamps with a candidate tree are refused by wm_decode_begin_ts)
-        k_select1_ts<true><<<dim3(SEL_SP, nb * vr), dim3(256), 0, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, vr, ctx->part1,
+    if (wm_rules_on(ts)) {  // (chain only: the rules are refused with a candidate tree by wm_decode_begin_ts)
+        k_select1_ts<true><<<dim3(SEL_SP, nb * vr), dim3(256), lds, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, vr, ctx->part1,
                                                                            nullptr, nullptr, ts, 1);
         WM_HIP(hipGetLastError());
         if (gp.accept_mode == WM_ACCEPT_TYPICAL)
-            k_select2_ts<<<dim3(SEL_SP, nb * vr), dim3(256), 0, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, ctx->cand, vr, 0,
+            k_select2_ts<<<dim3(SEL_SP, nb * vr), dim3(256), lds, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, ctx->cand, vr, 0,
                                                                          ctx->part1, ctx->part2, ctx->amax, ctx->pc, nullptr, ts);
         else
             k_select_argmax_ts<<<dim3((nb * vr + 63) / 64), dim3(64), 0, st>>>(ctx->part1, nb * vr, 0, ctx->amax, ts);
@@ -1958,6 +1982,7 @@ int wm_dec_step(wm_ctx* ctx, int)
     const int B = ctx->Bdec, K = ctx->K, rps = K + 1;
     const GenDev gp = ctx->gp;
     const TsDev ts = ctx->ts;
+    const size_t lds = rp_lds_bytes(ts, gp.V);
     g_skinny_done = ctx->use_done ? ctx->done : nullptr;
     g_skinny_ntiles = nullptr;
     if (B > 1024) { ctx->err = "merged-step schedule: more than 1024 streams"; return WM_ERR_ARG; }
@@ -1970,8 +1995,8 @@ int wm_dec_step(wm_ctx* ctx, int)
     int rc = wm_dec_stage_heads(ctx, B, 1, 0, 1);
     ctx->hblk = hblk_rows;
     if (rc) return rc;
-    if (ts.on) {
-        k_select1_ts<false><<<dim3(SEL_SP, B * rps), dim3(256), 0, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, rps, ctx->part1,
+    if (wm_rules_on(ts)) {
+        k_select1_ts<false><<<dim3(SEL_SP, B * rps), dim3(256), lds, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, rps, ctx->part1,
                                                                             nullptr, nullptr, ts, 0);
         WM_HIP(hipGetLastError());
         k_cand_fin_ts<<<dim3(B), dim3(256), 0, st>>>(ctx->part1, gp, ctx->amax, ctx->cand, nullptr, ts);
@@ -1990,12 +2015,12 @@ int wm_dec_step(wm_ctx* ctx, int)
     if (rc == WM_OK) rc = wm_dec_stage_heads(ctx, B * rps, 1, 0, 0);
     g_skinny_ntiles = nullptr;
     if (rc) return rc;
-    if (ts.on) {
-        k_select1_ts<true><<<dim3(SEL_SP, B * rps), dim3(256), 0, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, rps, ctx->part1,
+    if (wm_rules_on(ts)) {
+        k_select1_ts<true><<<dim3(SEL_SP, B * rps), dim3(256), lds, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, rps, ctx->part1,
                                                                            ctx->rowinfo, nullptr, ts, 1);
         WM_HIP(hipGetLastError());
         if (gp.accept_mode == WM_ACCEPT_TYPICAL)
-            k_select2_ts<<<dim3(SEL_SP, B * rps), dim3(256), 0, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, ctx->cand, rps, 0,
+            k_select2_ts<<<dim3(SEL_SP, B * rps), dim3(256), lds, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, ctx->cand, rps, 0,
                                                                          ctx->part1, ctx->part2, ctx->amax, ctx->pc, ctx->rowinfo, ts);
         else
             k_select_argmax_ts<<<dim3((B * rps + 63) / 64), dim3(64), 0, st>>>(ctx->part1, B * rps, 0, ctx->amax, ts);
@@ -2117,6 +2142,7 @@ __global__ void k_ts_tap_build(const int* __restrict__ pre, const int* __restric
     if (r >= R) return;
     int4 st = make_int4(0, 0, -1, 0);
     const int n = len[r];
+    if (!ts.on) return;                 // (repetition rules alone: the select kernels read the prefixes themselves)
     for (int t = max(gp.begin, 0); t < n; ++t) st = ts_fold(st, pre[(size_t)r * Tmax + t], ts.tb);
     ts.ver[r] = ts_record(st, n, gp.begin, ts.tb, gp.V, ts.mit);
 }
@@ -2125,14 +2151,16 @@ int wm_dec_select_rows(wm_ctx* ctx, const int* pre_dev, const int* len_dev, int 
 {
     hipStream_t st = ctx->stream;
     const GenDev gp = ctx->gp;
-    const TsDev ts = ctx->ts;
+    TsDev ts = ctx->ts;
+    ts.rp_ids = pre_dev; ts.rp_stride = Tmax; ts.rp_len = len_dev;      // repetition rules: the rows' own prefixes
+    const size_t lds = rp_lds_bytes(ts, gp.V);
     hipLaunchKernelGGL(k_ts_tap_build, dim3(1), dim3(64), 0, st, pre_dev, len_dev, R, Tmax, gp, ts);
     WM_HIP(hipGetLastError());
     // one "stream" of R + 1 rows: row i's probe token is cand[i + 1] (k_select2's p(c_{i+1})), its record ts.ver[i]
-    k_select1_ts<true><<<dim3(SEL_SP, R), dim3(256), 0, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, R + 1, ctx->part1,
+    k_select1_ts<true><<<dim3(SEL_SP, R), dim3(256), lds, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, R + 1, ctx->part1,
                                                                  nullptr, nullptr, ts, 1);
     WM_HIP(hipGetLastError());
-    k_select2_ts<<<dim3(SEL_SP, R), dim3(256), 0, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, ctx->cand, R + 1, 0,
+    k_select2_ts<<<dim3(SEL_SP, R), dim3(256), lds, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, ctx->cand, R + 1, 0,
                                                            ctx->part1, ctx->part2, ctx->amax, ctx->pc, nullptr, ts);
     WM_HIP(hipGetLastError());
     return WM_OK;

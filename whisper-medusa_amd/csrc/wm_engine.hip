@@ -309,7 +309,12 @@ extern "C" int wm_set_encoder_output(wm_ctx* ctx, const float* hidden, int B)
 static int wm_ts_setup(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* ts, TsDev* out)
 {
     TsDev t = ctx->ts;
-    t.on = 0; t.tb = 0; t.nots = -1; t.mit = -1; t.L = ctx->L;
+    t.on = 0; t.tb = ctx->V; t.nots = -1; t.mit = -1; t.L = ctx->L;      // (off: the whole vocabulary is the text region)
+    // repetition rules (wm_set_repeat_rules): the decode's prefixes are the committed ids and the candidates; taps / scoring point elsewhere
+    const bool pen = ctx->rep.repetition_penalty != 1.0f, ngram = ctx->rep.no_repeat_ngram_size > 0;
+    t.rp = (pen ? 1 : 0) | (ngram ? 2 : 0); t.rp_pen = ctx->rep.repetition_penalty; t.rp_g = ctx->rep.no_repeat_ngram_size;
+    t.rp_ids = ctx->ids; t.rp_stride = ctx->Tal; t.rp_len = nullptr; t.rp_cand = ctx->cand; t.rp_flags = nullptr;
+    if (t.rp && ctx->tn) { ctx->err = "repetition rules: not supported with a candidate tree (medusa_choices with top-k > 1)"; return WM_ERR_ARG; }
     if (ts) {
         if (ctx->tn) { ctx->err = "timestamps: not supported with a candidate tree (medusa_choices with top-k > 1)"; return WM_ERR_ARG; }
         const int tb = ts->timestamp_begin;
@@ -361,6 +366,19 @@ void wm_decode_invalidate(wm_ctx* ctx, bool drop_graphs)
     if (drop_graphs && ctx->graph_base) { (void)hipGraphExecDestroy(ctx->graph_base); ctx->graph_base = nullptr; }
 }
 
+// HF RepetitionPenaltyLogitsProcessor / NoRepeatNGramLogitsProcessor inside the select and scoring kernels (include/wm.h)
+extern "C" int wm_set_repeat_rules(wm_ctx* ctx, const wm_repeat_params* rp)
+{
+    if (!ctx) return WM_ERR_ARG;
+    if (!rp) { ctx->rep = wm_repeat_params{1.0f, 0}; return WM_OK; }
+    if (!(rp->repetition_penalty > 0.f) || !std::isfinite(rp->repetition_penalty)) {
+        ctx->err = "wm_set_repeat_rules: repetition_penalty must be a finite number > 0"; return WM_ERR_ARG; }
+    if (rp->no_repeat_ngram_size < 0 || rp->no_repeat_ngram_size > ctx->Tmax) {
+        ctx->err = "wm_set_repeat_rules: no_repeat_ngram_size must be in [0, n_tgt]"; return WM_ERR_ARG; }
+    ctx->rep = *rp;
+    return WM_OK;
+}
+
 extern "C" int wm_decode_begin(wm_ctx* ctx, const wm_gen_params* gp, int B) { return wm_decode_begin_ts(ctx, gp, nullptr, B); }
 
 extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* tsp, int B)
@@ -391,7 +409,8 @@ extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm
     g.fuse = ctx->host_carry ? 1 : (ctx->dev_carry ? (ctx->step_flow ? 3 : 2) : 0);
     g.sib = (ctx->host_carry && ctx->tn == 0 && ctx->sib_cfg > 0 && std::getenv("WM_NO_SIBLINGS") == nullptr) ? ctx->sib_cfg : 0;
     const bool same = ctx->graph && ctx->graph_B == B && std::memcmp(&g, &ctx->gp, sizeof(GenDev)) == 0 && ts.on == ctx->ts.on &&
-                      ts.tb == ctx->ts.tb && ts.nots == ctx->ts.nots && ts.mit == ctx->ts.mit;
+                      ts.tb == ctx->ts.tb && ts.nots == ctx->ts.nots && ts.mit == ctx->ts.mit && ts.rp == ctx->ts.rp &&
+                      ts.rp_pen == ctx->ts.rp_pen && ts.rp_g == ctx->ts.rp_g;
     if (!same && ctx->graph) { hipGraphExecDestroy(ctx->graph); ctx->graph = nullptr; }
     if (!same && ctx->graph_base) { hipGraphExecDestroy(ctx->graph_base); ctx->graph_base = nullptr; }
     ctx->gp = g; ctx->Bdec = B; ctx->ts = ts;
@@ -616,7 +635,7 @@ extern "C" int wm_select_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_tim
                               float* out_p_probe, float* out_entropy, int32_t* out_ts_forced)
 {
     if (!ctx) return WM_ERR_ARG;
-    if (!gp || !tsp || R < 1 || !logits || !prefixes || Tmax < 1 || !lens || !probe_tokens || !out_argmax || !out_p_probe || !out_entropy ||
+    if (!gp || (!tsp && ctx->rep.repetition_penalty == 1.0f && ctx->rep.no_repeat_ngram_size == 0) || R < 1 || !logits || !prefixes || Tmax < 1 || !lens || !probe_tokens || !out_argmax || !out_p_probe || !out_entropy ||
         !out_ts_forced) { ctx->err = "wm_select_rows: bad arguments"; return WM_ERR_ARG; }
     for (int r = 0; r < R; ++r)
         if (lens[r] < 1 || lens[r] > Tmax || probe_tokens[r] < 0 || probe_tokens[r] >= ctx->V) {

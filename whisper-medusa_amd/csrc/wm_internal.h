@@ -51,7 +51,17 @@ struct TsDev {
     float* part1t;                  // [Rcap][SEL_SP][4] timestamp-region slice partials {max, first argmax, sum exp at 1/T, sum exp at 1}
     int* forced;                    // [Rcap] the row's log-softmax decision masked all text (k_select2 / k_select_argmax)
     const int* L;                   // ctx->L (k_cand_fin: prefix length of verify row i is L + i + 1)
+    // repetition rules (wm_set_repeat_rules): ride in the same kernel family (launched when on || rp).  Nothing is kept per
+    // stream: every select / score block derives its slice of the two token sets from the row's prefix ids (wm_select.h rp_build)
+    int rp;                         // bit 0: repetition penalty, bit 1: no-repeat n-gram
+    float rp_pen; int rp_g;
+    const int* rp_ids; int rp_stride;   // prefix of stream s: rp_ids + s * rp_stride, cur_len ids (decode: ctx->ids; scoring: offset in the row's record .w)
+    const int* rp_len;              // tap (wm_select_rows): row i follows rp_ids + i * rp_stride, rp_len[i] ids; else NULL
+    const int* rp_cand;             // verify row i of stream s also follows rp_cand[s * WM_CAND_STRIDE + 0 .. i]
+    int* rp_flags;                  // scoring: [rows] the target's bits (1 penalised, 2 banned), k_score1 -> k_score2
 };
+// the rules kernel family (*_ts) runs when the timestamp rules or the repetition rules are on
+static inline bool wm_rules_on(const TsDev& t) { return t.on || t.rp; }
 
 // state after one more sampled token / the record of a row whose sampled prefix has state `st` (host: wm_decode_begin_ts, device: the select kernels)
 __host__ __device__ __forceinline__ int4 ts_fold(int4 st, int tok, int tb)
@@ -202,6 +212,7 @@ struct wm_ctx {
     bool use_done = false;
     GenDev gp{};
     TsDev ts{};                            // timestamp rules of the current decode (ts.on = 0: off); buffers allocated in wm_create
+    wm_repeat_params rep{1.0f, 0};         // wm_set_repeat_rules: sticky until cleared (neutral = off)
     int Bdec = 0;
     bool began = false, first_done = false;
     long long iters = 0;

@@ -24,6 +24,7 @@ struct wm_score_state {
     DevBuf<int4> desc, rec, sst;    // [rows] {logits row, cur_len (< 0: raw row), target (< 0: skip), out index}, records; [maxB] fold state
     DevBuf<float> p1, p1t, out;     // [rows][SEL_SP][4] text / timestamp partials; outputs
     DevBuf<int> lens, npr, ibuf;    // [maxB] each; tap: prefixes + lengths + targets
+    DevBuf<int> rpf;                // [rows] repetition rules: the target's bits (k_score1 -> k_score2)
 };
 
 void wm_score_free(wm_ctx* ctx)
@@ -38,7 +39,7 @@ static int score_reserve(wm_ctx* ctx, size_t rows, size_t nout, size_t nb, size_
     wm_score_state* sc = ctx->score;
     WM_HIP(sc->desc.reserve(rows)); WM_HIP(sc->rec.reserve(rows));
     WM_HIP(sc->p1.reserve(rows * SEL_SP * 4)); WM_HIP(sc->p1t.reserve(rows * SEL_SP * 4));
-    WM_HIP(sc->out.reserve(nout));
+    WM_HIP(sc->out.reserve(nout)); WM_HIP(sc->rpf.reserve(rows));
     WM_HIP(sc->lens.reserve(nb)); WM_HIP(sc->npr.reserve(nb)); WM_HIP(sc->sst.reserve(nb));
     WM_HIP(sc->ibuf.reserve(nibuf));
     return WM_OK;
@@ -63,7 +64,9 @@ __global__ void k_score_build(const int* __restrict__ ids, int Tids, const int* 
         if (ts.on && pos >= gp.begin && pos < T) st = ts_fold(st, id[pos], ts.tb);          // st: ids[begin : t)
         const bool scored = t >= P && t < T;
         desc[b * Mper + i] = make_int4(b * Mper + i, t, scored ? id[t] : -1, b * Tout + t);
-        rec[b * Mper + i] = ts.on ? ts_record(st, t, gp.begin, ts.tb, gp.V, ts.mit) : make_int4(0, 0, 0, 0);
+        int4 rc = ts.on ? ts_record(st, t, gp.begin, ts.tb, gp.V, ts.mit) : make_int4(0, 0, 0, 0);
+        rc.w = b * Tids;                // repetition rules: where the row's prefix ids[0 : t) start
+        rec[b * Mper + i] = rc;
     }
     sst[b] = st;
     const bool here = ns_id >= 0 && sot >= pos0 && sot < pos0 + Mper && sot < T;
@@ -81,7 +84,9 @@ __global__ void k_score_tap_build(const int* __restrict__ pre, const int* __rest
     const int n = len[r];
     if (ts.on) for (int t = max(gp.begin, 0); t < n; ++t) st = ts_fold(st, pre[(size_t)r * Tmax + t], ts.tb);
     desc[r] = make_int4(r, n, tgt[r], r);
-    rec[r] = ts.on ? ts_record(st, n, gp.begin, ts.tb, gp.V, ts.mit) : make_int4(0, 0, 0, 0);
+    int4 rc = ts.on ? ts_record(st, n, gp.begin, ts.tb, gp.V, ts.mit) : make_int4(0, 0, 0, 0);
+    rc.w = r * Tmax;
+    rec[r] = rc;
 }
 
 // running (max, sum of exp(v - max)) of one more value / of two partial results; -inf never enters
@@ -118,6 +123,14 @@ k_score1(const float* __restrict__ logits, GenDev gp, const unsigned char* __res
     const float4* x4 = reinterpret_cast<const float4*>(logits + (size_t)dsc.x * gp.Vpad);
     const int n4 = (gp.V + 3) / 4, per4 = (n4 + SEL_SP - 1) / SEL_SP, q0 = sp * per4, q1 = min(n4, q0 + per4);
     float mt = -INFINITY, zt = 0.f, ms = -INFINITY, zs = 0.f;
+    // repetition rules (not on the raw row): the slice's token sets from the row's own prefix ids[0 : cur_len), the target's bits for k_score2
+    extern __shared__ unsigned rp_sh[];
+    const bool rp = ts.rp != 0 && !raw;
+    const int n0 = 4 * q0;
+    if (rp) {
+        rp_build(ts, RpPre{ts.rp_ids + rec.w, cur_len, ts.rp_ids, 0}, n0, min(gp.V, 4 * q1), dsc.z, gp.V, rp_sh, tid, 256);
+        if (sp == 0 && tid == 0) ts.rp_flags[row] = (int)rp_sh[0];
+    }
     for (int q = q0 + tid; q < q1; q += 256) {
         const float4 v4 = x4[q];
         const float vals[4] = {v4.x, v4.y, v4.z, v4.w};
@@ -127,8 +140,10 @@ k_score1(const float* __restrict__ logits, GenDev gp, const unsigned char* __res
             if (n >= gp.V) continue;
             float v = vals[j];
             if (!raw) {
+                if (rp) v = rp_pen(v, n, n0, ts, rp_sh);
                 v = proc_logit(v, n, cur_len, gp, mask, exppen);
                 if (tson) v = ts_mask(v, n, rec, gp, ts);
+                if (rp && rp_banned(n, n0, gp.V, rp_sh)) v = -INFINITY;
             }
             if (v == -INFINITY) continue;
             if (n < tb) lse_push(mt, zt, v); else lse_push(ms, zs, v);
@@ -164,11 +179,14 @@ __global__ void k_score2(const float* __restrict__ logits, GenDev gp, const unsi
     const int n = dsc.z;
     float v = logits[(size_t)dsc.x * gp.Vpad + n];
     if (dsc.y >= 0) {
+        const int fl = ts.rp ? ts.rp_flags[row] : 0;
+        if (fl & 1) v = rp_penalise(v, ts.rp_pen);
         v = proc_logit(v, n, dsc.y, gp, mask, exppen);
         if (ts.on) {
             v = ts_mask(v, n, recs[row], gp, ts);
             if (f.forced && n < ts.tb) v = -INFINITY;
         }
+        if (fl & 2) v = -INFINITY;
     }
     out[dsc.w] = (v == -INFINITY) ? -INFINITY : (v - f.mx) - logf(f.z);
 }
@@ -187,10 +205,11 @@ static int score_setup(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_
     return WM_OK;
 }
 
-static int score_launch(wm_ctx* ctx, const GenDev& g, const TsDev& ts, int nrows)
+static int score_launch(wm_ctx* ctx, const GenDev& g, const TsDev& ts_in, int nrows)
 {
     wm_score_state* sc = ctx->score;
-    hipLaunchKernelGGL(k_score1, dim3(SEL_SP, nrows), dim3(256), 0, ctx->stream, ctx->logits, g, ctx->supmask, ctx->exppen, ts, sc->desc, sc->rec,
+    TsDev ts = ts_in; ts.rp_flags = sc->rpf;
+    hipLaunchKernelGGL(k_score1, dim3(SEL_SP, nrows), dim3(256), rp_lds_bytes(ts, g.V), ctx->stream, ctx->logits, g, ctx->supmask, ctx->exppen, ts, sc->desc, sc->rec,
                        sc->p1, sc->p1t);
     WM_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_score2, dim3((nrows + 63) / 64), dim3(64), 0, ctx->stream, ctx->logits, g, ctx->supmask, ctx->exppen, ts, sc->desc, sc->rec,
@@ -298,6 +317,7 @@ extern "C" int wm_score_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_time
         WM_HIP(hipMemcpyAsync(tgt, targets + r0, n * sizeof(int), hipMemcpyHostToDevice, st));
         WM_HIP(hipMemcpy2DAsync(ctx->logits, (size_t)ctx->Vpad * sizeof(float), logits + (size_t)r0 * ctx->V, (size_t)ctx->V * sizeof(float),
                                 (size_t)ctx->V * sizeof(float), n, hipMemcpyHostToDevice, st));
+        ts.rp_ids = pre; ts.rp_stride = Tmax;           // repetition rules: the rows' own prefixes
         hipLaunchKernelGGL(k_score_tap_build, dim3((n + 63) / 64), dim3(64), 0, st, pre, len, tgt, n, Tmax, g, ts, sc->desc, sc->rec);
         WM_HIP(hipGetLastError());
         if (int rc = score_launch(ctx, g, ts, n)) return rc;

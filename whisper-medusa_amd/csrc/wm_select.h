@@ -28,7 +28,61 @@ __device__ __forceinline__ float ts_mask(float v, int n, int4 rec, const GenDev&
 // the row's record: base / head rows of stream s from the committed state at L; verify row i from k_cand_fin's fold
 __device__ __forceinline__ int4 ts_row_record(const GenDev& gp, const TsDev& ts, int ts_verify, int s, int i, int cur_len)
 {
+    if (!ts.on) return make_int4(0, 0, 0, 0);          // (repetition rules alone: no timestamp mask; tb = V, nots = -1)
     return ts_verify ? ts.ver[s * WM_CAND_STRIDE + i] : ts_record(ts.st[s], cur_len, gp.begin, ts.tb, gp.V, ts.mit);
+}
+
+// ---- repetition rules (wm_set_repeat_rules; HF RepetitionPenaltyLogitsProcessor, then NoRepeatNGramLogitsProcessor, both BEFORE the
+// processors above) ----
+// A block that sweeps tokens [n0, n1) of a row builds, in dynamic LDS, two bitmaps over that range from the row's prefix ids (`pre`, then
+// `ext`: the candidates a verify row follows): the tokens of the prefix (penalised) and the tokens that followed an earlier occurrence of
+// its last g - 1 ids (banned).  The prefix is walked once per block, 256 ids at a time — never once per vocabulary element — and the
+// element test is two LDS bit reads.  sh[0] collects the same two bits for one token outside the range (the probe / target).
+struct RpPre { const int* pre; int len; const int* ext; int next; };
+__host__ __device__ __forceinline__ int rp_words(int V) { return V / (32 * SEL_SP) + 3; }      // covers ceil(V / SEL_SP) + 4 tokens (k_score1's float4 slices)
+static inline size_t rp_lds_bytes(const TsDev& ts, int V) { return ts.rp ? (size_t)(4 + 2 * rp_words(V)) * sizeof(unsigned) : 0; }
+__device__ __forceinline__ int rp_tok(const RpPre& p, int j) { return j < p.len ? p.pre[j] : p.ext[j - p.len]; }
+__device__ __forceinline__ void rp_build(const TsDev& ts, const RpPre& p, int n0, int n1, int probe, int V, unsigned* sh, int tid, int nthr)
+{
+    const int W = rp_words(V);
+    for (int k = tid; k < 4 + 2 * W; k += nthr) sh[k] = 0u;
+    __syncthreads();
+    const int T = p.len + p.next, g = ts.rp_g;
+    for (int j = tid; j < T; j += nthr) {
+        const int tok = rp_tok(p, j);
+        const bool in = tok >= n0 && tok < n1;
+        unsigned fl = 0u;
+        if (ts.rp & 1) {
+            fl |= 1u;
+            if (in) atomicOr(&sh[4 + ((tok - n0) >> 5)], 1u << ((tok - n0) & 31));
+        }
+        if ((ts.rp & 2) && T >= g && j >= g - 1) {          // the n-gram ending at j: pre[j-g+1 .. j-1] against the last g - 1 ids
+            bool same = true;
+            for (int k = 1; k < g && same; ++k) same = rp_tok(p, j - k) == rp_tok(p, T - k);
+            if (same) {
+                fl |= 2u;
+                if (in) atomicOr(&sh[4 + W + ((tok - n0) >> 5)], 1u << ((tok - n0) & 31));
+            }
+        }
+        if (tok == probe && fl) atomicOr(&sh[0], fl);
+    }
+    __syncthreads();
+}
+__device__ __forceinline__ float rp_penalise(float x, float p) { return x < 0.f ? x * p : __fdiv_rn(x, p); }
+// step 1 on the raw logit of token n in [n0, n1)
+__device__ __forceinline__ float rp_pen(float x, int n, int n0, const TsDev& ts, const unsigned* sh)
+{
+    return ((sh[4 + ((n - n0) >> 5)] >> ((n - n0) & 31)) & 1u) ? rp_penalise(x, ts.rp_pen) : x;
+}
+__device__ __forceinline__ bool rp_banned(int n, int n0, int V, const unsigned* sh)
+{
+    return (sh[4 + rp_words(V) + ((n - n0) >> 5)] >> ((n - n0) & 31)) & 1u;
+}
+// the prefix of a select row: the tap's own, else the stream's committed ids (+ the candidates c_0 .. c_i of verify row i)
+__device__ __forceinline__ RpPre rp_row_prefix(const TsDev& ts, int verify, int s, int i, int cur_len)
+{
+    if (ts.rp_len) return RpPre{ts.rp_ids + (size_t)i * ts.rp_stride, ts.rp_len[i], ts.rp_ids, 0};
+    return RpPre{ts.rp_ids + (size_t)s * ts.rp_stride, min(cur_len, ts.rp_stride), ts.rp_cand + s * WM_CAND_STRIDE, verify ? i + 1 : 0};
 }
 struct TsSel { float mx; int mi; float z; int forced; };
 // finish a row from its SEL_SP x 2 slice partials: the decision, then (arg-max, max, softmax denominator at 1/T) of what it leaves

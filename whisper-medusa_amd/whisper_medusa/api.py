@@ -434,7 +434,7 @@ class WhisperMedusaModel:
     # ---- generate ---------------------------------------------------------------------------
     def _gen_params(self, language, task, exponential_decay_length_penalty, max_new_tokens, max_length,
                     temperature, vanilla, posterior_threshold, posterior_alpha, suppress_tokens,
-                    begin_suppress_tokens, prompt_ids, timestamps: bool = False) -> GenParams:
+                    begin_suppress_tokens, prompt_ids, timestamps: bool = False, repetition_penalty=None, no_repeat_ngram_size=None) -> GenParams:
         cfg = self.config
         # G1, model.py:1519-1537; timestamps: without <|notimestamps|> (HF _retrieve_init_tokens with return_timestamps)
         prompt = _synth.default_prompt(cfg, language or "en", task or "transcribe", timestamps=timestamps)
@@ -473,7 +473,9 @@ class WhisperMedusaModel:
                          accept_mode=mode, temperature=1.0 if mode == ACCEPT_TYPICAL else 0.0, vanilla=bool(vanilla),
                          begin_suppress_index=begin_suppress_index, timestamps=bool(timestamps),
                          no_timestamps_token_id=cfg.no_timestamps_token_id if timestamps else -1,
-                         max_initial_timestamp_index=cfg.max_initial_timestamp_index if timestamps else None)
+                         max_initial_timestamp_index=cfg.max_initial_timestamp_index if timestamps else None,
+                         repetition_penalty=1.0 if repetition_penalty is None else float(repetition_penalty),
+                         no_repeat_ngram_size=0 if no_repeat_ngram_size is None else int(no_repeat_ngram_size))
 
     @torch.no_grad()
     def generate(self, input_features: Optional[torch.Tensor] = None, generation_config=None, logits_processor=None,
@@ -510,7 +512,8 @@ class WhisperMedusaModel:
             return_token_timestamps = pick("return_token_timestamps", return_token_timestamps)
             return_dict_in_generate = pick("return_dict_in_generate", return_dict_in_generate)
             for name in ("max_new_tokens", "max_length", "num_beams", "suppress_tokens", "begin_suppress_tokens",
-                         "exponential_decay_length_penalty", "posterior_threshold", "posterior_alpha"):
+                         "exponential_decay_length_penalty", "posterior_threshold", "posterior_alpha",
+                         "repetition_penalty", "no_repeat_ngram_size"):
                 if kwargs.get(name) is None and getattr(gc, name, None) is not None:
                     kwargs[name] = getattr(gc, name)
             if kwargs.get("do_sample") is None and getattr(gc, "do_sample", False):
@@ -520,7 +523,7 @@ class WhisperMedusaModel:
             own = getattr(self, "generation_config", None)
             ignored = []
             for name, dflt in (("temperature", 1.0), ("eos_token_id", None), ("pad_token_id", None), ("forced_decoder_ids", None),
-                               ("top_k", 50), ("top_p", 1.0), ("repetition_penalty", 1.0), ("no_repeat_ngram_size", 0),
+                               ("top_k", 50), ("top_p", 1.0),
                                ("length_penalty", 1.0), ("bad_words_ids", None), ("min_length", 0), ("min_new_tokens", None)):
                 v = getattr(gc, name, None)
                 if v is None or v == dflt or (own is not None and v == getattr(own, name, None)):
@@ -533,6 +536,22 @@ class WhisperMedusaModel:
                               UserWarning, stacklevel=2)
         if kwargs.get("do_sample"):
             raise NotImplementedError("sampling (do_sample=True) is not supported with medusa")      # model.py:1128-1156: no Medusa branch
+        # HF RepetitionPenaltyLogitsProcessor / NoRepeatNGramLogitsProcessor (GenerationMixin._get_logits_processor builds them from these two
+        # fields; the reference's generate() drops both): inside the engine's select kernels, every row under its own prefix
+        rep_pen, rep_g = kwargs.get("repetition_penalty"), kwargs.get("no_repeat_ngram_size")
+        rep_pen = 1.0 if rep_pen is None else float(rep_pen)
+        rep_g = 0 if rep_g is None else int(rep_g)
+        if not (rep_pen > 0.0 and np.isfinite(rep_pen)):
+            raise ValueError(f"`repetition_penalty` has to be a strictly positive float, but is {rep_pen}")        # HF's own check
+        if rep_g < 0:
+            raise ValueError(f"`no_repeat_ngram_size` has to be a positive integer or 0, but is {rep_g}")
+        if rep_pen != 1.0 or rep_g != 0:
+            if self.config.is_tree:
+                raise NotImplementedError("repetition_penalty / no_repeat_ngram_size are not supported with a candidate tree "
+                                          "(medusa_choices with top-k > 1)")
+            if logits_processor and any(type(p_).__name__ not in _LOWERABLE_PROCESSORS for p_ in logits_processor):
+                raise NotImplementedError("repetition_penalty / no_repeat_ngram_size are not supported on the host processor path "
+                                          "(logits_processor=); pass the HF processor objects there instead")
         if return_timestamps:
             # model.py:1171-1175 raises for every checkpoint; the engine runs HF's WhisperTimeStampLogitsProcessor in its decode loop
             #  where the vocabulary carries Whisper's timestamp block
@@ -606,7 +625,8 @@ class WhisperMedusaModel:
                               temperature if not isinstance(temperature, (tuple, list)) else temperature[0],
                               kwargs.get("vanilla", False), kwargs.get("posterior_threshold"),
                               kwargs.get("posterior_alpha"), kwargs.get("suppress_tokens"),
-                              kwargs.get("begin_suppress_tokens"), prompt_ids, timestamps=bool(return_timestamps))
+                              kwargs.get("begin_suppress_tokens"), prompt_ids, timestamps=bool(return_timestamps),
+                              repetition_penalty=rep_pen, no_repeat_ngram_size=rep_g)
         gp._time_precision = float(time_precision)
         if logits_processor or stopping_criteria:
             gp = lower_processors(gp, logits_processor, stopping_criteria)
@@ -637,6 +657,9 @@ class WhisperMedusaModel:
         if streamer is not None and B != 1:
             raise ValueError("streamer only supports batch size 1")        # HF streamers are batch-1
         if getattr(gp, "_host_processors", None):
+            if gp.repeat_rules:
+                raise NotImplementedError("repetition_penalty / no_repeat_ngram_size are not supported on the host processor path "
+                                          "(logits_processor=); pass the HF processor objects there instead")
             if tt_req is not None:
                 raise NotImplementedError("return_token_timestamps is not supported on the host processor path (logits_processor=)")
             if sc_req is not None:

@@ -343,6 +343,14 @@ class GenParams:
     no_timestamps_token_id: int = -1               # (timestamps: timestamp_begin = no_timestamps_token_id + 1)
     max_initial_timestamp_index: Optional[int] = None
 
+    # HF RepetitionPenaltyLogitsProcessor / NoRepeatNGramLogitsProcessor in the select kernels (wm_set_repeat_rules); neutral = off
+    repetition_penalty: float = 1.0
+    no_repeat_ngram_size: int = 0
+
+    @property
+    def repeat_rules(self) -> bool:
+        return float(self.repetition_penalty) != 1.0 or int(self.no_repeat_ngram_size) != 0
+
     @property
     def begin_index(self) -> int:
         return len(self.prompt) if self.begin_suppress_index is None else int(self.begin_suppress_index)

@@ -49,6 +49,10 @@ class WmTimestampParams(C.Structure):
                 ("begin_index", C.c_int32)]
 
 
+class WmRepeatParams(C.Structure):
+    _fields_ = [("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int32)]
+
+
 class WmAlignParams(C.Structure):
     _fields_ = [("heads", C.POINTER(C.c_int32)), ("n_heads", C.c_int32), ("median_filter_width", C.c_int32), ("time_precision", C.c_float)]
 
@@ -69,7 +73,7 @@ EXPORTS = ["wm_create", "wm_destroy", "wm_last_error", "wm_abi_version", "wm_bui
            "wm_get_encoder_output", "wm_forward_logits", "wm_get_cross_kv", "wm_profile_kernel",
            "wm_decode_begin_ts", "wm_select_rows",
            "wm_token_timestamps", "wm_get_align_probs", "wm_get_align_matrix", "wm_dtw",
-           "wm_score_tokens", "wm_score_rows"]
+           "wm_score_tokens", "wm_score_rows", "wm_set_repeat_rules"]
 
 _lib = {}
 
@@ -113,6 +117,7 @@ def load_library(path: Optional[str] = None, act_fp16: bool = False) -> C.CDLL:
     lib.wm_decode_begin_ts.argtypes = [vp, C.POINTER(WmGenParams), C.POINTER(WmTimestampParams), i32]
     lib.wm_select_rows.argtypes = [vp, C.POINTER(WmGenParams), C.POINTER(WmTimestampParams), i32, f32p, i32p, i32, i32p, i32p,
                                    i32p, f32p, f32p, i32p]
+    lib.wm_set_repeat_rules.argtypes = [vp, C.POINTER(WmRepeatParams)]
     lib.wm_decode_run.argtypes = [vp, i32, i32p]
     lib.wm_get_tokens.argtypes = [vp, i32, i32p, i32, i32p]
     lib.wm_get_stats.argtypes = [vp, C.POINTER(WmStats)]
@@ -274,8 +279,19 @@ class Engine:
         return WmTimestampParams(int(gp.no_timestamps_token_id) + 1, int(gp.no_timestamps_token_id), -1 if mit is None else int(mit),
                                  int(gp.begin_index))
 
+    def _set_repeat_rules(self, gp: GenParams) -> None:
+        """The context's repetition rules follow ``gp`` before every call that reads them (wm_set_repeat_rules is sticky): neutral fields
+        clear them, so a pooled context never inherits the rules of an earlier call."""
+        pen, g = float(getattr(gp, "repetition_penalty", 1.0)), int(getattr(gp, "no_repeat_ngram_size", 0))
+        if pen == 1.0 and g == 0:
+            self._check(self.lib.wm_set_repeat_rules(self.h, None), "wm_set_repeat_rules")
+        else:
+            rp = WmRepeatParams(pen, g)
+            self._check(self.lib.wm_set_repeat_rules(self.h, C.byref(rp)), "wm_set_repeat_rules")
+
     def decode(self, gp: GenParams, B: int, max_iters: int = 1 << 30, on_iteration=None) -> List[List[int]]:
         g, _keep = self._gen_struct(gp)
+        self._set_repeat_rules(gp)
         self._kv_stamp = object()             # the decode loop rewrites the self-attention cache: forward()'s cache handles go stale
         if gp.timestamps:                     # WhisperTimeStampLogitsProcessor in the loop (include/wm.h wm_decode_begin_ts)
             ts = self._ts_struct(gp)
@@ -323,10 +339,12 @@ class Engine:
         probe = np.ascontiguousarray(probe_tokens, dtype=np.int32)
         am = np.zeros(R, np.int32); pp = np.zeros(R, np.float32); H = np.zeros(R, np.float32); fo = np.zeros(R, np.int32)
         g, _keep = self._gen_struct(gp)
-        ts = self._ts_struct(gp)
+        self._set_repeat_rules(gp)
+        # (the repetition rules alone: no timestamp argument; otherwise the timestamp rules as ever)
+        ts = self._ts_struct(gp) if (gp.timestamps or not gp.repeat_rules) else None
         i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
         self._kv_stamp = object()
-        self._check(self.lib.wm_select_rows(self.h, C.byref(g), C.byref(ts), R, x.ctypes.data_as(f32p), pre.ctypes.data_as(i32p), Tmax,
+        self._check(self.lib.wm_select_rows(self.h, C.byref(g), C.byref(ts) if ts is not None else None, R, x.ctypes.data_as(f32p), pre.ctypes.data_as(i32p), Tmax,
                                             lens.ctypes.data_as(i32p), probe.ctypes.data_as(i32p), am.ctypes.data_as(i32p),
                                             pp.ctypes.data_as(f32p), H.ctypes.data_as(f32p), fo.ctypes.data_as(i32p)), "wm_select_rows")
         return dict(argmax=am, p_probe=pp, entropy=H, ts_forced=fo)
@@ -399,6 +417,7 @@ class Engine:
         g, _keep = self._gen_struct(gp)
         ts = self._ts_struct(gp) if gp.timestamps else None
         sp = WmScoreParams(int(no_speech_token_id) if want_ns else -1, int(sot_index))
+        self._set_repeat_rules(gp)
         i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
         self._kv_stamp = object()
         self._check(self.lib.wm_score_tokens(self.h, C.byref(g), C.byref(ts) if ts is not None else None, C.byref(sp), B, tok.ctypes.data_as(i32p), Tmax,
@@ -417,6 +436,7 @@ class Engine:
         tgt = np.ascontiguousarray(targets, dtype=np.int32)
         out = np.zeros(R, np.float32)
         g, _keep = self._gen_struct(gp)
+        self._set_repeat_rules(gp)
         ts = self._ts_struct(gp) if gp.timestamps else None
         i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
         self._kv_stamp = object()
