@@ -167,6 +167,16 @@ int wm_resample(wm_ctx* ctx, const float* in, int B, int channels, int n_in, int
  * wav: DEV float32 [B][n_samples] already padded/trimmed to n_samples = 320*n_ctx (480000).
  * feats: DEV float32 [B][n_mels][2*n_ctx]. */
 int wm_logmel(wm_ctx* ctx, const float* wav, int B, int n_samples, float* feats);
+/* Log-mel of whole recordings (WhisperFeatureExtractor(truncation=False)): the same arithmetic over n_samples / 160 frames, the clamp at
+ * the maximum of the whole recording.  wav: DEV float32 [B][n_samples], n_samples any positive multiple of 160 (clips of one call are
+ * zero-padded as audio to the longest: HF padding="longest"); feats: DEV float32 [B][n_mels][n_samples/160].  B <= max_batch. */
+int wm_logmel_long(wm_ctx* ctx, const float* wav, int B, int n_samples, float* feats);
+/* The windows of one round of sequential long-form decoding, one launch (HF _get_input_segment: slice at the stream's seek, zero pad):
+ *   out[w][m][f] = f < n_valid[w] ? feats[clip[w]][m][seek[w] + f] : 0.0f
+ * feats: DEV float32 [n_clips][n_mels][frames]; clip, seek, n_valid: HOST int32 [Bw]; out: DEV float32 [Bw][n_mels][2*n_ctx].
+ * WM_ERR_ARG, with out untouched: clip[w] outside [0, n_clips), seek[w] < 0, n_valid[w] outside [0, 2*n_ctx], seek[w] + n_valid[w] > frames. */
+int wm_gather_windows(wm_ctx* ctx, const float* feats, int n_clips, int frames, const int32_t* clip, const int32_t* seek,
+                      const int32_t* n_valid, int Bw, float* out);
 
 /* ---- F1+F2 encoder and cross-KV projection (replaces the encoder call of
  * _prepare_encoder_decoder_kwargs_for_generation, model.py:1005-1011, and the cross K/V

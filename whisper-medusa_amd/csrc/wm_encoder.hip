@@ -1629,23 +1629,99 @@ int wm_enc_resample(wm_ctx* ctx, const float* in, int B, int channels, int n_in,
     return WM_OK;
 }
 
+// the two log-mel launches over Tm = n_samples / 160 frames per clip (Tm is a run-time value: one 30 s window, or a whole recording)
+static int logmel_launch(wm_ctx* ctx, const float* wav, int B, int n_samples, int Tm, float* feats)
+{
+    hipStream_t st = ctx->stream;
+    WM_HIP(hipMemsetAsync(ctx->clipmax, 0x80, sizeof(int) * B, st));
+    hipLaunchKernelGGL(k_logmel_stft, dim3((Tm + 3) / 4, B), dim3(256), 0, st, wav, ctx->win, ctx->twiddle, ctx->melfb, feats,
+                       reinterpret_cast<int*>(ctx->clipmax), n_samples, Tm, ctx->cfg.n_mels);
+    WM_HIP(hipGetLastError());
+    const long per = (long)ctx->cfg.n_mels * Tm, total = per * B;
+    hipLaunchKernelGGL(k_logmel_norm, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, feats,
+                       reinterpret_cast<const int*>(ctx->clipmax), per, total);
+    WM_HIP(hipGetLastError());
+    return WM_OK;
+}
+
 int wm_enc_logmel(wm_ctx* ctx, const float* wav, int B, int n_samples, float* feats)
 {
     hipStream_t st = ctx->stream;
     if (B < 1 || B > ctx->maxB || n_samples != 160 * ctx->Tm) { ctx->err = "wm_logmel: bad B or n_samples (must be 320*n_ctx)"; return WM_ERR_ARG; }
     WM_HIP(hipEventRecord(ctx->ev0, st));
-    WM_HIP(hipMemsetAsync(ctx->clipmax, 0x80, sizeof(int) * B, st));
-    hipLaunchKernelGGL(k_logmel_stft, dim3((ctx->Tm + 3) / 4, B), dim3(256), 0, st, wav, ctx->win, ctx->twiddle, ctx->melfb, feats,
-                       reinterpret_cast<int*>(ctx->clipmax), n_samples, ctx->Tm, ctx->cfg.n_mels);
-    WM_HIP(hipGetLastError());
-    const long per = (long)ctx->cfg.n_mels * ctx->Tm, total = per * B;
-    hipLaunchKernelGGL(k_logmel_norm, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, feats,
-                       reinterpret_cast<const int*>(ctx->clipmax), per, total);
-    WM_HIP(hipGetLastError());
+    if (int rc = logmel_launch(ctx, wav, B, n_samples, ctx->Tm, feats)) return rc;
     WM_HIP(hipEventRecord(ctx->ev1, st));
     WM_HIP(hipEventSynchronize(ctx->ev1));
     WM_HIP(hipEventElapsedTime(&ctx->ms_logmel, ctx->ev0, ctx->ev1));
     return WM_OK;
+}
+
+// Whole-recording log-mel (HF WhisperFeatureExtractor(truncation=False)): the same launches over n_samples / 160 frames, the clamp at the
+// maximum of the whole recording.  The kernels index feats and wav in 64 bits; the one reflection at either edge is enough from 160
+// samples on (left: |n| <= 200 -> 2 (n_samples - 1) - 200 >= 118; right: n <= n_samples + 39).
+static int wm_enc_logmel_long(wm_ctx* ctx, const float* wav, int B, int n_samples, float* feats)
+{
+    if (B < 1 || B > ctx->maxB || n_samples < 160 || n_samples % 160 || n_samples > 0x7fffffff - 400) {
+        ctx->err = "wm_logmel_long: bad B (1 .. max_batch) or n_samples (a positive multiple of 160)"; return WM_ERR_ARG; }
+    if (int rc = logmel_launch(ctx, wav, B, n_samples, n_samples / 160, feats)) return rc;
+    WM_HIP(hipStreamSynchronize(ctx->stream));        // like wm_logmel: the result is complete when the call returns
+    return WM_OK;
+}
+
+// Windows of long-form decoding (HF _get_input_segment: slice at the stream's seek, then zero pad to the window):
+//   out[w][m][f] = f < n_valid[w] ? feats[clip[w]][m][seek[w] + f] : 0,   idx = {clip, seek, n_valid} x [Bw]
+// A copy: threads walk f (coalesced on both sides); seek is only known to be even and `frames` may be odd, so the loads stay scalar.
+__global__ void __launch_bounds__(256)
+k_gather_windows(const float* __restrict__ feats, const int* __restrict__ idx, float* __restrict__ out, int Bw, int n_mels, int frames, int F)
+{
+    const int f = blockIdx.x * 256 + threadIdx.x, m = blockIdx.y, w = blockIdx.z;
+    if (f >= F) return;
+    const int c = idx[w], seek = idx[Bw + w], nv = idx[2 * Bw + w];
+    float v = 0.f;
+    if (f < nv) v = feats[((size_t)c * n_mels + m) * (size_t)frames + (size_t)(seek + f)];
+    out[((size_t)w * n_mels + m) * F + f] = v;
+}
+
+static int wm_enc_gather_windows(wm_ctx* ctx, const float* feats, int n_clips, int frames, const int32_t* clip, const int32_t* seek,
+                                 const int32_t* n_valid, int Bw, float* out)
+{
+    hipStream_t st = ctx->stream;
+    const int F = ctx->Tm, n_mels = ctx->cfg.n_mels;
+    if (n_clips < 1 || frames < 1 || Bw < 1 || Bw > 65535) { ctx->err = "wm_gather_windows: bad n_clips, frames or Bw"; return WM_ERR_ARG; }
+    for (int w = 0; w < Bw; ++w) {
+        if (clip[w] < 0 || clip[w] >= n_clips) { ctx->err = "wm_gather_windows: clip index out of range"; return WM_ERR_ARG; }
+        if (seek[w] < 0 || n_valid[w] < 0 || n_valid[w] > F) { ctx->err = "wm_gather_windows: seek < 0 or n_valid outside [0, 2*n_ctx]"; return WM_ERR_ARG; }
+        if ((long)seek[w] + n_valid[w] > frames) { ctx->err = "wm_gather_windows: seek + n_valid exceeds frames"; return WM_ERR_ARG; }
+    }
+    // the three int lists travel through the encoder's im2col scratch (A1: rewritten by every wm_encode, read by nothing else)
+    int* gw = reinterpret_cast<int*>(ctx->A1);
+    if ((size_t)3 * Bw * sizeof(int) > (size_t)ctx->maxB * ctx->Tmpad * ctx->K1pad * sizeof(bf16_t)) {
+        ctx->err = "wm_gather_windows: more windows than the context's scratch holds"; return WM_ERR_ARG; }
+    std::vector<int> idx((size_t)3 * Bw);
+    for (int w = 0; w < Bw; ++w) { idx[w] = clip[w]; idx[Bw + w] = seek[w]; idx[2 * Bw + w] = n_valid[w]; }
+    WM_HIP(hipMemcpyAsync(gw, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_gather_windows, dim3((F + 255) / 256, n_mels, Bw), dim3(256), 0, st, feats, gw, out, Bw, n_mels, frames, F);
+    WM_HIP(hipGetLastError());
+    WM_HIP(hipStreamSynchronize(st));                 // the host vector goes out of scope; the windows are complete when the call returns
+    return WM_OK;
+}
+
+// The two C-ABI entries of the long-form front (include/wm.h).  They live with their kernels, not in wm_engine.hip: they touch nothing of
+// the decode path, whose sources carry the hash that stamps the committed traffic counters (bench.py kernels_sha).
+extern "C" int wm_logmel_long(wm_ctx* ctx, const float* wav, int B, int n_samples, float* feats)
+{
+    if (!ctx || !wav || !feats) return WM_ERR_ARG;
+    WM_HIP(hipSetDevice(ctx->device));
+    return wm_enc_logmel_long(ctx, wav, B, n_samples, feats);
+}
+
+extern "C" int wm_gather_windows(wm_ctx* ctx, const float* feats, int n_clips, int frames, const int32_t* clip, const int32_t* seek,
+                                 const int32_t* n_valid, int Bw, float* out)
+{
+    if (!ctx) return WM_ERR_ARG;
+    if (!feats || !clip || !seek || !n_valid || !out) { ctx->err = "wm_gather_windows: null argument"; return WM_ERR_ARG; }
+    WM_HIP(hipSetDevice(ctx->device));
+    return wm_enc_gather_windows(ctx, feats, n_clips, frames, clip, seek, n_valid, Bw, out);
 }
 
 // forward(encoder_outputs=...) (reference model.py:1223-1243 -> HF WhisperModel: a caller-supplied encoder_outputs[0] replaces the

@@ -400,11 +400,17 @@ class WhisperMedusaModel:
         return self.config.medusa_choices
 
     # ---- F0 ---------------------------------------------------------------------------------
-    def extract_features(self, wav: Union[np.ndarray, torch.Tensor, Sequence[np.ndarray]], sampling_rate: int = 16000) -> torch.Tensor:
+    def extract_features(self, wav: Union[np.ndarray, torch.Tensor, Sequence[np.ndarray]], sampling_rate: int = 16000,
+                         truncation: bool = True) -> torch.Tensor:
         """waveform(s) -> log-mel ``input_features`` [B, 80, 3000] on the GPU; pads / trims to 30 s like
         ``WhisperFeatureExtractor`` (eval_whisper_medusa.py:46-50).  Clips in a list are mono [n] or multi-channel
         [channels, n] (a bare 2-D array is a batch of mono clips); anything that is not 16 kHz mono first goes through the audio front door on the GPU
-        (channel mean + torchaudio-default resampling, README.md:120-125 of the reference)."""
+        (channel mean + torchaudio-default resampling, README.md:120-125 of the reference).
+
+        ``truncation=False`` (``WhisperFeatureExtractor(truncation=False, padding="longest")``, the input of sequential long-form
+        decoding): the clips are zero-padded as audio to the longest, rounded up to a multiple of 160 samples, and transformed whole in
+        one call -> [B, n_mels, frames]; every clip's own frame count (``len // 160``: what HF derives from ``attention_mask``) is left
+        in ``self.last_num_frames`` (LongTensor [B])."""
         n = 160 * self.config.n_mel_frames
         if isinstance(wav, (list, tuple)):
             clips = [np.asarray(w, dtype=np.float32) for w in wav]
@@ -414,6 +420,20 @@ class WhisperMedusaModel:
             clips = [a] if a.ndim == 1 else [r for r in a]          # 2-D array = batch of mono clips; multi-channel clips go in a list
         if len(clips) > self._max_batch:
             self.set_max_batch(len(clips))                          # wm_logmel checks B <= max_batch
+        if not truncation:
+            mono = []
+            for c in clips:
+                if c.ndim == 2 or sampling_rate != 16000:
+                    t = torch.from_numpy(np.atleast_2d(c)[None]).to(self.device)     # [1, channels, n_in]
+                    mono.append(self.engine.resample(t, sampling_rate, 16000)[0])
+                else:
+                    mono.append(torch.from_numpy(c).to(self.device))
+            n = max(160, -(-max(r.numel() for r in mono) // 160) * 160)
+            buf = torch.zeros(len(mono), n, dtype=torch.float32, device=self.device)
+            for i, r in enumerate(mono):
+                buf[i, : r.numel()] = r
+            self.last_num_frames = torch.tensor([r.numel() // 160 for r in mono], dtype=torch.long)
+            return self.engine.logmel_long(buf)
         buf = torch.zeros(len(clips), n, dtype=torch.float32, device=self.device)
         for i, c in enumerate(clips):
             if c.ndim == 2 or sampling_rate != 16000:
@@ -495,7 +515,10 @@ class WhisperMedusaModel:
 
         ``return_token_logprobs=True`` returns a GenerateEncoderDecoderOutput with ``token_logprobs [B, T]``, ``avg_logprob``,
         ``compression_ratio`` and ``no_speech_prob``; ``no_speech_threshold`` / ``logprob_threshold`` / ``compression_ratio_threshold`` run the
-        same scoring pass and gate on it (``skipped``, ``needs_fallback`` in the dict outputs and in ``self.last_scores``)."""
+        same scoring pass and gate on it (``skipped``, ``needs_fallback`` in the dict outputs and in ``self.last_scores``).
+
+        ``sequential_longform=True`` with ``return_timestamps=True``: ``input_features [B, n_mels, T]`` of any length — per-clip
+        lengths from ``attention_mask [B, T]`` or ``num_frames=`` — are transcribed by Whisper's sequential long-form loop."""
         if generation_config is not None:
             # HF semantics (model.py:936-943 -> GenerationMixin._prepare_generation_config): a copy of the passed config, updated by every
             # explicit argument of this call — an explicit argument wins, the config fills what the call leaves open.  Only the fields this
@@ -536,6 +559,9 @@ class WhisperMedusaModel:
                               UserWarning, stacklevel=2)
         if kwargs.get("do_sample"):
             raise NotImplementedError("sampling (do_sample=True) is not supported with medusa")      # model.py:1128-1156: no Medusa branch
+        if kwargs.get("sequential_longform"):
+            self._check_sequential(return_timestamps, condition_on_prev_tokens, temperature, return_token_timestamps, logits_processor,
+                                   stopping_criteria, kwargs.get("streamer"), prompt_ids, prompt_condition_type)
         # HF RepetitionPenaltyLogitsProcessor / NoRepeatNGramLogitsProcessor (GenerationMixin._get_logits_processor builds them from these two
         # fields; the reference's generate() drops both): inside the engine's select kernels, every row under its own prefix
         rep_pen, rep_g = kwargs.get("repetition_penalty"), kwargs.get("no_repeat_ngram_size")
@@ -600,6 +626,12 @@ class WhisperMedusaModel:
             raise ValueError("input_features is required")
         if input_features.dim() != 3:
             raise ValueError("input_features must be [B, n_mels, frames]")
+        if kwargs.get("sequential_longform"):
+            return self._generate_sequential(input_features, attention_mask, dict(kwargs, language=language, task=task, temperature=temperature,
+                                                                                  prompt_ids=prompt_ids, _sc_req=sc_req,
+                                                                                  return_dict_in_generate=return_dict_in_generate,
+                                                                                  return_segments=return_segments, time_precision=time_precision,
+                                                                                  time_precision_features=time_precision_features))
         if input_features.shape[-1] > self.config.n_mel_frames:
             if not kwargs.get("chunk_longform"):
                 raise NotImplementedError("Longform generation is not supported yet")              # model.py:1213-1214
@@ -1231,6 +1263,166 @@ class WhisperMedusaModel:
             return dict({"sequences": t, "segments": segs}, **(fields or {}))
         return t
 
+    # ---- sequential long-form: HF's seek loop around the short-form path ---------------------------------------------
+    def _check_sequential(self, return_timestamps, condition_on_prev_tokens, temperature, return_token_timestamps, logits_processor,
+                          stopping_criteria, streamer, prompt_ids, prompt_condition_type):
+        """What `sequential_longform=True` refuses, each under its own name."""
+        if condition_on_prev_tokens:
+            raise NotImplementedError("condition_on_prev_tokens=True is not supported with sequential_longform: every window of a clip is "
+                                      "decoded under the same prompt (conditioning needs one prompt per stream)")
+        if isinstance(temperature, (tuple, list)):
+            raise NotImplementedError("a tuple `temperature` (temperature fallback) is not supported with sequential_longform")
+        if return_token_timestamps:
+            raise NotImplementedError("return_token_timestamps is not supported together with sequential_longform")
+        if not self.config.supports_timestamps:
+            raise NotImplementedError("sequential_longform needs timestamp tokens and this checkpoint's vocabulary has no timestamp block "
+                                      "(vocab_size - no_timestamps_token_id - 1 != max_source_positions + 1)")
+        if not return_timestamps:
+            # HF: "to generate transcriptions longer than 30 s you have to pass return_timestamps=True": the seek is read off the timestamps
+            raise NotImplementedError("sequential_longform needs return_timestamps=True: the loop seeks to the last predicted timestamp")
+        if self.config.is_tree:
+            raise NotImplementedError("sequential_longform is not supported with a candidate tree (medusa_choices with top-k > 1)")
+        if logits_processor or stopping_criteria:
+            raise NotImplementedError("sequential_longform is not supported together with logits_processor= / stopping_criteria= "
+                                      "(the host processor path)")
+        if streamer is not None:
+            raise NotImplementedError("streamer= is not supported with sequential_longform (windows of several clips decode as one batch)")
+        if prompt_ids is not None and prompt_condition_type != "all-segments":
+            raise NotImplementedError("prompt_ids with sequential_longform needs prompt_condition_type='all-segments': every window of a "
+                                      "clip is decoded under the same prompt (HF's default, 'first-segment', needs one prompt per stream)")
+
+    def _generate_sequential(self, input_features, attention_mask, kw):
+        """`sequential_longform=True`: Whisper's own long-form algorithm (openai/whisper ``transcribe``; HF ``WhisperGenerationMixin.generate``
+        on more than one window of features), batched over recordings.  Every clip keeps a seek into its features; per round the windows of
+        all unfinished clips are cut out at their seeks in one launch (``wm_gather_windows``: slice, then zero pad, HF ``_get_input_segment``)
+        and decoded as one batch through the short-form path — timestamps on, the same prompt for every window of a clip, the scoring
+        side-request when thresholds are given —; each clip then seeks to its window's last timestamp pair (the unfinished tail is decoded
+        again, whole, by the next window) or, with no pair / a single closing timestamp / a window the no-speech gate skipped, by the whole
+        window (``timestamps.sequential_seek_loop``).  The language is detected once per clip, on its first window; clips of different
+        languages run as separate groups per round.  No conditioning on the previous window, no temperature fallback (both refused)."""
+        cfg = self.config
+        for k in ("sequential_longform", "chunk_longform", "streamer", "alignment_heads"):
+            kw.pop(k, None)
+        rdg, sreq, rseg = kw.pop("return_dict_in_generate", None), kw.pop("_sc_req", None), kw.pop("return_segments", False)
+        tprec, tprec_f = kw.pop("time_precision", 0.02), kw.pop("time_precision_features", 0.01)
+        num_frames = kw.pop("num_frames", None)
+        F, eos, pad = cfg.n_mel_frames, cfg.eos_token_id, cfg.pad_token_id
+        B, _, T = input_features.shape
+        # per-clip lengths: HF's way (max_frames = attention_mask.sum(-1)), or num_frames=, else the whole tensor
+        if attention_mask is not None:
+            max_frames = [int(v) for v in torch.as_tensor(attention_mask).sum(-1).flatten().tolist()]
+        elif num_frames is not None:
+            nf = num_frames.tolist() if hasattr(num_frames, "tolist") else num_frames
+            max_frames = [int(nf)] * B if isinstance(nf, (int, float)) else [int(v) for v in nf]
+        else:
+            max_frames = [T] * B
+        if len(max_frames) != B or any(v < 0 or v > T for v in max_frames):
+            raise ValueError(f"sequential_longform: one length in [0, {T}] per clip is needed (attention_mask [B, T] or num_frames [B])")
+        if B > self._max_batch:
+            self.set_max_batch(B)
+        feats = input_features.to(self.device, torch.float32).contiguous()
+        detect = kw.get("language") is None and cfg.is_multilingual and kw.pop("detect_language", True)
+        langs: List[Optional[str]] = [None if detect else kw.get("language")] * B
+        kw.pop("language", None)
+        kw.pop("detect_language", None)
+        prompts: List[Optional[List[int]]] = [None] * B
+        ms_sc = [0.0]
+
+        def decode_round(clips, seeks, snf):
+            win = self.engine.gather_windows(feats, clips, seeks, snf)
+            new = [q for q, b in enumerate(clips) if detect and langs[b] is None]
+            if new:     # (every clip's first window)
+                for q, l in zip(new, self.detect_language(win[new])):
+                    langs[clips[q]] = l
+            out: List[Optional[dict]] = [None] * len(clips)
+            groups = sorted({langs[b] for b in clips}, key=lambda v: (v is None, v or ""))
+            for l in groups:
+                widx = [q for q, b in enumerate(clips) if langs[b] == l]
+                reuse = {"_encoded_batch": len(clips)} if len(groups) == 1 and len(new) == len(clips) else {}
+                o = self.generate(win[widx], language=l, _language_resolved=True, return_timestamps=True, time_precision=tprec,
+                                  **reuse, **kw, **({"_sc_req": sreq} if sreq is not None else {}))
+                P = len(self._last_prompt)
+                rows = o.cpu()
+                if sreq is not None:
+                    ms_sc[0] += self.last_stats.get("ms_token_logprobs", 0.0)
+                    sc = {k: v.cpu() for k, v in self._last_sc.items() if not k.startswith("_")}
+                for j, q in enumerate(widx):
+                    prompts[clips[q]] = list(self._last_prompt)
+                    rec = dict(ids=_timestamps.generated_ids(rows[j].tolist(), P, eos), skipped=False, result=o[j])
+                    if sreq is not None:
+                        rec["scores"] = {k: v[j] for k, v in sc.items()}
+                        rec["skipped"] = bool(rec["scores"]["skipped"]) if "skipped" in rec["scores"] else False
+                    out[q] = rec
+            return out
+
+        windows = _timestamps.sequential_seek_loop(max_frames, F, decode_round, cfg.timestamp_begin, tprec, tprec_f,
+                                                   F // cfg.max_source_positions)
+        for b in range(B):
+            if prompts[b] is None:      # a clip without a single frame: nothing was decoded, its row is the default prompt + EOS
+                prompts[b] = list(self._gen_params(langs[b], kw.get("task"), None, None, None, None, False, None, None, None, None,
+                                                   kw.get("prompt_ids"), timestamps=True).prompt)
+        seqs = [_timestamps.assemble_sequence(prompts[b], windows[b], eos) for b in range(B)]
+        segs = [[sg for w in windows[b] for sg in w["segments"]] for b in range(B)]
+        Tm = max(len(s_) for s_ in seqs)
+        t = torch.full((B, Tm), pad, dtype=torch.long, device=self.device)
+        for i, s_ in enumerate(seqs):
+            t[i, : len(s_)] = torch.tensor(s_, dtype=torch.long)
+        if detect:
+            self.detected_languages = list(langs)
+        stats = dict(getattr(self, "last_stats", None) or {})
+        stats["longform_windows"] = [len(w) for w in windows]
+        self.last_stats = stats
+        fields = None
+        if sreq is not None:
+            # per clip: the kept tokens' scores (a window's kept segments are a prefix of its ids), their average and the compression ratio of the
+            # assembled ids; per window, ragged (clips take different numbers of windows): the gate's inputs and verdicts
+            lp = torch.zeros(B, Tm, dtype=torch.float32)
+            all_lp = []
+            for b in range(B):
+                P = len(prompts[b])
+                r, last_eos = [0.0] * P, 0.0
+                for w in windows[b]:
+                    if w["skipped"]:
+                        continue
+                    n = sum(int(sg["tokens"].numel()) for sg in w["segments"])
+                    wl = w["scores"]["token_logprobs"]
+                    r += [float(v) for v in wl[P: P + n]]
+                    k = P + len(w["ids"])                       # the window's own EOS, where it emitted one
+                    last_eos = float(wl[k]) if k < int(w["scores"]["lengths"]) else 0.0
+                    if rseg:
+                        o = P
+                        for sg in w["segments"]:
+                            m = int(sg["tokens"].numel())
+                            sg["token_logprobs"] = wl[o: o + m]
+                            o += m
+                r.append(last_eos)
+                all_lp.append(r)
+                lp[b, : len(r)] = torch.tensor(r, dtype=torch.float32)
+            Pb = [len(p_) for p_ in prompts]
+            fields = dict(token_logprobs=lp.to(self.device),
+                          avg_logprob=torch.tensor([_scores.avg_logprob(all_lp[i], Pb[i], len(seqs[i])) for i in range(B)], dtype=torch.float32, device=self.device),
+                          compression_ratio=torch.tensor([_scores.compression_ratio(seqs[i][Pb[i]:], cfg.vocab_size) for i in range(B)],
+                                                         dtype=torch.float32, device=self.device),
+                          lengths=torch.tensor([len(s_) for s_ in seqs], dtype=torch.long, device=self.device))
+            any_w = next((w for ws in windows for w in ws), None)
+            for k in ("no_speech_prob", "skipped", "needs_fallback"):
+                if any_w is not None and k in any_w["scores"]:
+                    fields[k] = [torch.stack([w["scores"][k] for w in ws]) if ws else torch.zeros(0) for ws in windows]
+            fields["window_avg_logprob"] = [torch.stack([w["scores"]["avg_logprob"] for w in ws]) if ws else torch.zeros(0) for ws in windows]
+            fields["window_seek"] = [torch.tensor([w["seek"] for w in ws], dtype=torch.long) for ws in windows]
+            self.last_scores = fields
+            self.last_stats["ms_token_logprobs"] = ms_sc[0]
+        if fields is not None and (sreq["want"] or rdg):
+            out = GenerateEncoderDecoderOutput(t, **fields)
+            if rseg or rdg:
+                out["segments"] = segs
+            return out
+        if rdg:     # (HF: return_dict_in_generate with return_timestamps sets return_segments)
+            return GenerateEncoderDecoderOutput(t, segments=segs)
+        if rseg:
+            return dict({"sequences": t, "segments": segs}, **(fields or {}))
+        return t
+
     @torch.no_grad()
     def generate_sharded(self, input_features: torch.Tensor, **kw) -> torch.Tensor:
         """Data-parallel generate() over the ranks of an initialised torch.distributed group (one process per GPU, SURVEY.md
@@ -1277,7 +1469,12 @@ class WhisperMedusaModel:
         return t
 
     def generate_from_wav(self, wav, **kw) -> torch.Tensor:
-        """log-mel on the GPU, then ``generate`` — the whole hot path of SURVEY.md §8a in one call."""
+        """log-mel on the GPU, then ``generate`` — the whole hot path of SURVEY.md §8a in one call.  ``sequential_longform=True``: the
+        log-mel of the whole recordings (``extract_features(truncation=False)``) and every clip's own length, then the sequential loop."""
+        if kw.get("sequential_longform"):
+            feats = self.extract_features(wav, kw.pop("sampling_rate", 16000), truncation=False)
+            kw.setdefault("num_frames", self.last_num_frames)
+            return self.generate(feats, **kw)
         return self.generate(self.extract_features(wav), **kw)
 
     # ---- forward ----------------------------------------------------------------------------

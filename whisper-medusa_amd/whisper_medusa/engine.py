@@ -73,7 +73,8 @@ EXPORTS = ["wm_create", "wm_destroy", "wm_last_error", "wm_abi_version", "wm_bui
            "wm_get_encoder_output", "wm_forward_logits", "wm_get_cross_kv", "wm_profile_kernel",
            "wm_decode_begin_ts", "wm_select_rows",
            "wm_token_timestamps", "wm_get_align_probs", "wm_get_align_matrix", "wm_dtw",
-           "wm_score_tokens", "wm_score_rows", "wm_set_repeat_rules"]
+           "wm_score_tokens", "wm_score_rows", "wm_set_repeat_rules",
+           "wm_logmel_long", "wm_gather_windows"]
 
 _lib = {}
 
@@ -111,6 +112,8 @@ def load_library(path: Optional[str] = None, act_fp16: bool = False) -> C.CDLL:
     lib.wm_resample_len.argtypes = [C.c_int64, i32, i32]; lib.wm_resample_len.restype = C.c_int64
     lib.wm_resample.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
     lib.wm_logmel.argtypes = [vp, vp, i32, i32, vp]
+    lib.wm_logmel_long.argtypes = [vp, vp, i32, i32, vp]
+    lib.wm_gather_windows.argtypes = [vp, vp, i32, i32, i32p, i32p, i32p, i32, vp]
     lib.wm_encode.argtypes = [vp, vp, i32]
     lib.wm_set_encoder_output.argtypes = [vp, vp, i32]
     lib.wm_decode_begin.argtypes = [vp, C.POINTER(WmGenParams), i32]
@@ -237,6 +240,34 @@ class Engine:
         self._inputs_ready()
         self._check(self.lib.wm_logmel(self.h, C.c_void_p(wav.data_ptr()), B, n, C.c_void_p(feats.data_ptr())), "wm_logmel")
         return feats
+
+    def logmel_long(self, wav: torch.Tensor) -> torch.Tensor:
+        """wav [B, n] float32 on the GPU, n any positive multiple of 160 -> features [B, n_mels, n / 160] of the whole recordings
+        (``WhisperFeatureExtractor(truncation=False)``: the clamp at each recording's own maximum)."""
+        wav = wav.to(self.device, torch.float32).contiguous()
+        B, n = wav.shape
+        feats = torch.empty(B, self.cfg.num_mel_bins, n // 160, dtype=torch.float32, device=wav.device)
+        self._inputs_ready()
+        self._check(self.lib.wm_logmel_long(self.h, C.c_void_p(wav.data_ptr()), B, n, C.c_void_p(feats.data_ptr())), "wm_logmel_long")
+        return feats
+
+    def gather_windows(self, feats: torch.Tensor, clip: Sequence[int], seek: Sequence[int], n_valid: Sequence[int],
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The windows of one long-form round in one launch (HF ``_get_input_segment``): feats [n_clips, n_mels, frames] on the GPU ->
+        [len(clip), n_mels, 2*n_ctx] with ``out[w, :, f] = feats[clip[w], :, seek[w] + f]`` for ``f < n_valid[w]`` and 0 behind."""
+        feats = feats.to(self.device, torch.float32).contiguous()
+        n_clips, n_mels, frames = feats.shape
+        Bw = len(clip)
+        if n_mels != self.cfg.num_mel_bins or len(seek) != Bw or len(n_valid) != Bw:
+            raise ValueError("gather_windows: feats must be [n_clips, n_mels, frames] with one clip, seek and n_valid per window")
+        if out is None:
+            out = torch.empty(Bw, n_mels, self.cfg.n_mel_frames, dtype=torch.float32, device=self.device)
+        c, s, v = (np.ascontiguousarray(a, dtype=np.int32) for a in (clip, seek, n_valid))
+        i32p = C.POINTER(C.c_int32)
+        self._inputs_ready()
+        self._check(self.lib.wm_gather_windows(self.h, C.c_void_p(feats.data_ptr()), n_clips, frames, c.ctypes.data_as(i32p), s.ctypes.data_as(i32p),
+                                               v.ctypes.data_as(i32p), Bw, C.c_void_p(out.data_ptr())), "wm_gather_windows")
+        return out
 
     # ---- F1/F2 ------------------------------------------------------------------------------
     def encode(self, feats: torch.Tensor) -> None:
