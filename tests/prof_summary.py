@@ -1,4 +1,6 @@
-"""Summarise a rocprofv3 rocpd database (kernel-trace) per kernel: python tests/prof_summary.py <db> [out.md] [--hbm-large-v2-b1]
+"""Summarise a rocprofv3 rocpd database (kernel-trace) per kernel: python tests/prof_summary.py <db> [out.md] [--hbm-large-v2-b1] [--shapes]
+--shapes: print (and write) instead the histogram of launch shapes, one line per (kernel name, grid, workgroup, dynamic LDS bytes) with its
+dispatch count, sorted: two trees issue the same launches when `diff` of the two outputs is empty (durations are left out on purpose).
 --hbm-large-v2-b1: the run was bench.py's default (whisper-large-v2 + Medusa-Linear K=10, ONE stream): a second table prices every
 decode-path launch on the bytes it must read from HBM (its weight matrix; the stream's cross K/V for the cross-attention) against 8 TB/s."""
 import re
@@ -7,6 +9,15 @@ import sys
 
 db = sys.argv[1]
 c = sqlite3.connect(db)
+if "--shapes" in sys.argv:
+    shapes = c.execute("select name, grid_x, grid_y, grid_z, workgroup_x, workgroup_y, workgroup_z, lds_size, count(*) from kernels "
+                       "group by 1, 2, 3, 4, 5, 6, 7, 8 order by 1, 2, 3, 4, 5, 6, 7, 8").fetchall()
+    out = "\n".join(f"{r[8]:7d}  grid {r[1]}x{r[2]}x{r[3]}  wg {r[4]}x{r[5]}x{r[6]}  lds {r[7]}  {r[0]}" for r in shapes)
+    print(out)
+    outs = [a for a in sys.argv[2:] if not a.startswith("--")]
+    if outs:
+        open(outs[0], "w").write(out + "\n")
+    sys.exit(0)
 rows = c.execute("select name, count(*), sum(end-start)/1e3, avg(end-start)/1e3, min(end-start)/1e3, max(end-start)/1e3 "
                  "from kernels group by name order by 3 desc").fetchall()
 tot = sum(r[2] for r in rows)

@@ -1383,12 +1383,94 @@ static inline int xattn_blocks_per_head(int NS, int heads_total)
 // =============================================================================================
 // host side
 // =============================================================================================
+// ---- the six weight-streaming GEMMs of a decoder layer: one definition each, shared by dec_layer and wm_dec_profile -------------------
+// R token rows of the fp32 residual h; pc = the prefetch job the launch carries for a later one (wm_skinny_gemm.h PfCarry; default: none).
+// LayerNorm fold (round 6, wm_common.h): the three LayerNorm-fed GEMMs read the operand gamma o h (ctx->xn) and the rows' statistics
+// partials (ctx->lnstats) that the launch producing h wrote (embed / final LayerNorm for LN1 of the first layer, FC2 of the layer below,
+// out-proj for LN2, cross-out for LN3) and apply mean / rstd to their accumulators: no LayerNorm launch, no statistics prologue.  Each
+// helper holds the choice between that form and the unfolded one (WM_LN_FOLD=0) once.
+// (Templates only to keep this change's device image the parent's byte for byte: a template's body is instantiated where it is first called, so
+// the kernels named here are emitted in dec_layer's launch order, as when dec_layer named the launchers itself.  Nothing depends on it: as plain
+// functions they merely move the GEMM kernels in front of the attention kernels in the code object — profiles/explicit_launch_state.md.)
+static inline FoldIn layer_fold_in(const wm_ctx* ctx, const float* c) { return FoldIn{ctx->lnstats, c, ctx->d / 16, ctx->Rcap, 1.0f / (float)ctx->d}; }
+
+// LN1 + QKV: q rows to ctx->qbuf, k rows / transposed v rows straight into the cache slabs kc / vc of the pass's first stream, Mper rows per
+// stream from position base[stream]; rowinfo != nullptr: the merged-step schedule's dense rows (EpQKVDecDense)
+template <int = 0> static hipError_t gemm_qkv(wm_ctx* ctx, const DecLayerW& w, int R, float* h, bf16_t* kc, bf16_t* vc, const int* base, int Mper, const int4* rowinfo,
+                           const PfCarry& pc = PfCarry{})
+{
+    const int d = ctx->d, K32 = d / 32, H = ctx->H;
+    const size_t xpl = (size_t)ctx->Rcap * d;
+    const WRef W{w.qkv_w, w.qkv_s};
+    if (ctx->ln_fold && rowinfo)
+        return launch_skinny_fold(ctx->lp, W, 3 * d / 16, K32, R, ctx->xn, xpl, layer_fold_in(ctx, w.qkv_c),
+                                  EpQKVDecDense{ctx->qbuf, kc, vc, w.qkv_bf, base, Mper, d, H, ctx->Tal, R, rowinfo}, pc);
+    if (ctx->ln_fold)
+        return launch_skinny_fold(ctx->lp, W, 3 * d / 16, K32, R, ctx->xn, xpl, layer_fold_in(ctx, w.qkv_c),
+                                  EpQKVDec{ctx->qbuf, kc, vc, w.qkv_bf, base, Mper, d, H, ctx->Tal, R}, pc);
+    if (rowinfo)
+        return launch_skinny_norm(ctx->lp, W, 3 * d / 16, K32, h, w.ln1_w, w.ln1_b, d, R, 1, 0, 1,
+                                  EpQKVDecDense{ctx->qbuf, kc, vc, w.qkv_b, base, Mper, d, H, ctx->Tal, R, rowinfo}, ctx->xbuf, xpl, pc);
+    return launch_skinny_norm(ctx->lp, W, 3 * d / 16, K32, h, w.ln1_w, w.ln1_b, d, R, 1, 0, 1,
+                              EpQKVDec{ctx->qbuf, kc, vc, w.qkv_b, base, Mper, d, H, ctx->Tal, R}, ctx->xbuf, xpl, pc);
+}
+
+// h += X W^T + bias (X: packed rows of K = 32 * Kc32 features); fold: also the operand gnext o h and the statistics partials of the LayerNorm
+// that follows (gnext = its gamma; nullptr: a final LayerNorm launch follows, the unfolded epilogue)
+template <int = 0> static hipError_t gemm_residual(wm_ctx* ctx, WRef W, const float* bias, int Kc32, const bf16_t* X, size_t plane, int R, float* h, const float* gnext,
+                                const PfCarry& pc)
+{
+    const int d = ctx->d;
+    if (ctx->ln_fold && gnext) {
+        EpResidualFold e{h, bias, d, R}; e.gnext = gnext; e.xo = ctx->xn; e.xplane = (size_t)ctx->Rcap * d; e.stats = ctx->lnstats; e.K32 = d / 32; e.sld = ctx->Rcap;
+        return launch_skinny_rows(ctx->lp, W, d / 16, Kc32, R, X, plane, e, pc);
+    }
+    return launch_skinny_rows(ctx->lp, W, d / 16, Kc32, R, X, plane, EpResidual{h, bias, d, R}, pc);
+}
+// self-attention out_proj + residual
+template <int = 0> static hipError_t gemm_out(wm_ctx* ctx, const DecLayerW& w, int R, float* h, const PfCarry& pc = PfCarry{})
+{
+    return gemm_residual(ctx, WRef{w.out_w, w.out_s}, w.out_b, ctx->d / 32, ctx->xbuf, (size_t)ctx->Rcap * ctx->d, R, h, w.ln2_w, pc);
+}
+// LN2 + cross-attention q (scaled) -> ctx->qbuf
+template <int = 0> static hipError_t gemm_cross_q(wm_ctx* ctx, const DecLayerW& w, int R, float* h, const PfCarry& pc = PfCarry{})
+{
+    const int d = ctx->d, K32 = d / 32;
+    const size_t xpl = (size_t)ctx->Rcap * d;
+    if (ctx->ln_fold)
+        return launch_skinny_fold(ctx->lp, WRef{w.cq_w, w.cq_s}, d / 16, K32, R, ctx->xn, xpl, layer_fold_in(ctx, w.cq_c), EpF32{ctx->qbuf, w.cq_bf, d, R, 0.125f}, pc);
+    return launch_skinny_norm(ctx->lp, WRef{w.cq_w, w.cq_s}, d / 16, K32, h, w.ln2_w, w.ln2_b, d, R, 1, 0, 1, EpF32{ctx->qbuf, w.cq_b, d, R, 0.125f},
+                              ctx->xbuf, xpl, pc);
+}
+// cross-attention out_proj + residual
+template <int = 0> static hipError_t gemm_cross_out(wm_ctx* ctx, const DecLayerW& w, int R, float* h, const PfCarry& pc = PfCarry{})
+{
+    return gemm_residual(ctx, WRef{w.cout_w, w.cout_s}, w.cout_b, ctx->d / 32, ctx->xbuf, (size_t)ctx->Rcap * ctx->d, R, h, w.ln3_w, pc);
+}
+// LN3 + fc1 + GELU -> ctx->fbuf (packed).  pf_extra: unfolded batched passes, the matrix the LayerNorm launch pulls in besides FC1's (FC2's)
+template <int = 0> static hipError_t gemm_fc1(wm_ctx* ctx, const DecLayerW& w, int R, float* h, const PfCarry& pc = PfCarry{}, const void* pf_extra = nullptr)
+{
+    const int d = ctx->d, K32 = d / 32, F32 = ctx->ffn / 32;
+    const size_t xpl = (size_t)ctx->Rcap * d, fpl = (size_t)ctx->Rcap * ctx->ffn;
+    if (ctx->ln_fold)
+        return launch_skinny_fold(ctx->lp, WRef{w.fc1_w, w.fc1_s}, ctx->ffn / 16, K32, R, ctx->xn, xpl, layer_fold_in(ctx, w.fc1_c),
+                                  EpPackedAct<1>{ctx->fbuf, ctx->fbuf + fpl, w.fc1_bf, F32, R}, pc);
+    return launch_skinny_norm(ctx->lp, WRef{w.fc1_w, w.fc1_s}, ctx->ffn / 16, K32, h, w.ln3_w, w.ln3_b, d, R, 1, 0, 1,
+                              EpPackedAct<1>{ctx->fbuf, ctx->fbuf + fpl, w.fc1_b, F32, R}, ctx->xbuf, xpl, pc, pf_extra);
+}
+// fc2 + residual; gnext = gamma of the LayerNorm the rows go to next under fold (the next layer's LN1), nullptr: the final LayerNorm launch
+template <int = 0> static hipError_t gemm_fc2(wm_ctx* ctx, const DecLayerW& w, int R, float* h, const float* gnext, const PfCarry& pc = PfCarry{})
+{
+    return gemm_residual(ctx, WRef{w.fc2_w, w.fc2_s}, w.fc2_b, ctx->ffn / 32, ctx->fbuf, (size_t)ctx->Rcap * ctx->ffn, R, h, gnext, pc);
+}
+
 static int dec_layer(wm_ctx* ctx, const DecLayerW& w, int slot, float* h, int b0, int nb, int Mper, const int* base, bool kv_only,
                      const int* sskip = nullptr, const DecLayerW* next = nullptr, const int4* rowinfo = nullptr, const int4* sinfo = nullptr)
 {
     hipStream_t st = ctx->stream;
+    DecLaunch& lp = ctx->lp;
     const int d = ctx->d, H = ctx->H, K32 = d / 32, R = nb * Mper, F32 = ctx->ffn / 32;
-    const size_t xpl = (size_t)ctx->Rcap * d, fpl = (size_t)ctx->Rcap * ctx->ffn;
+    const size_t xpl = (size_t)ctx->Rcap * d;
     bf16_t* kc = ctx->kc + ((size_t)slot * ctx->maxB + b0) * H * ctx->Tal * 64;
     bf16_t* vc = ctx->vc + ((size_t)slot * ctx->maxB + b0) * H * ctx->Tal * 64;
     const size_t xoff = ((size_t)slot * ctx->Benc + b0) * H * ctx->Spad * 64;
@@ -1400,7 +1482,8 @@ static int dec_layer(wm_ctx* ctx, const DecLayerW& w, int slot, float* h, int b0
     const float* vxs = x8 ? ctx->vxs + ((size_t)slot * ctx->Benc + b0) * H : nullptr;
     const unsigned xkb = x8 ? 64u : 128u;        // bytes of one key row of a head
     // In-launch prefetch (single-tile passes, WM_PREFETCH != 0): launch k carries extra blocks that pull the operand of launch
-    // k+1 into L2 (wm_skinny_gemm.h PfJob).  The self-attention launch is tiny, so LN1+QKV fetches for the launch after it.
+    // k+1 into L2 (wm_skinny_gemm.h PfJob): the job is an argument of the launch that carries it.  The self-attention launch is tiny, so
+    // LN1+QKV fetches for the launch after it.
     const bool pf = ctx->prefetch && R <= 16 && !kv_only;
     const bool f8 = w.qkv_s != nullptr;
     static const int skip_div = [] { const char* v = std::getenv("WM_XATTN_SKIP_DIV"); return v ? std::max(1, std::atoi(v)) : 3; }();
@@ -1408,31 +1491,21 @@ static int dec_layer(wm_ctx* ctx, const DecLayerW& w, int slot, float* h, int b0
     const int nz = nb * nqt;                     // (stream, query tile) pairs = z-blocks of the attention launches
     const int xheads = sskip ? std::max(1, H * nb / skip_div) : H * nz;
     const int xgrid = xattn_blocks_per_head(ctx->NS, xheads);
-    // LayerNorm fold (round 6, wm_common.h): the three LayerNorm-fed GEMMs read the operand gamma o h (ctx->xn) and the rows' statistics
-    // partials (ctx->lnstats) that the launch producing h wrote (embed / final LayerNorm for LN1 of the first layer, FC2 of the layer below,
-    // out-proj for LN2, cross-out for LN3) and apply mean / rstd to their accumulators: no LayerNorm launch, no statistics prologue.
-    const bool fold = ctx->ln_fold;
-    const FoldIn fin_base{ctx->lnstats, nullptr, d / 16, ctx->Rcap, 1.0f / (float)d};
-    auto fold_in = [&](const float* c) { FoldIn f = fin_base; f.c = c; return f; };
-    auto res_fold = [&](const float* bias, const float* gnext) {
-        EpResidualFold e{h, bias, d, R}; e.gnext = gnext; e.xo = ctx->xn; e.xplane = xpl; e.stats = ctx->lnstats; e.K32 = K32; e.sld = ctx->Rcap;
-        return e;
+    const bool fold = ctx->ln_fold;       // LayerNorm folded into the GEMM it feeds (the gemm_* helpers above)
+    // batched passes with the LayerNorm folded: no LayerNorm launch is left to pull the next GEMM's weights towards the chip, the launch that
+    // produces the residual rows carries that job (wm_skinny_gemm.h pf_batched); WM_PREFETCH=0 turns it off with the others
+    const bool pfb = fold && ctx->prefetch && R > 16;
+    const int MTp = (R + 15) / 16;
+    // the job a residual-producing launch (3, 6, 7, 8) carries: the weights of the GEMM (W, N16, Kc32) that follows it
+    auto carry_for = [&](const bf16_t* W, int N16, int Kc32, bool norm_loader) {
+        if (pf) return PfCarry{pf_for_gemm(W, f8, N16, Kc32, norm_loader), 0};
+        if (pfb) return pf_batched(W, nullptr, f8, N16, Kc32, MTp);
+        return PfCarry{};
     };
     // 1. LN1 + QKV; k rows / transposed v rows straight into the cache
-    if (pf) g_pf_job = pf_for_gemm(w.out_w, f8, d / 16, K32, false);
-    TL_SET(slot * 16 + 1 + 8192 * Mper);
-    if (fold && rowinfo)
-        WM_HIP(launch_skinny_fold(st, WRef{w.qkv_w, w.qkv_s}, 3 * d / 16, K32, R, ctx->xn, xpl, fold_in(w.qkv_c),
-                                  EpQKVDecDense{ctx->qbuf, kc, vc, w.qkv_bf, base, Mper, d, H, ctx->Tal, R, rowinfo}));
-    else if (fold)
-        WM_HIP(launch_skinny_fold(st, WRef{w.qkv_w, w.qkv_s}, 3 * d / 16, K32, R, ctx->xn, xpl, fold_in(w.qkv_c),
-                                  EpQKVDec{ctx->qbuf, kc, vc, w.qkv_bf, base, Mper, d, H, ctx->Tal, R}));
-    else if (rowinfo)
-        WM_HIP(launch_skinny_norm(st, WRef{w.qkv_w, w.qkv_s}, 3 * d / 16, K32, h, w.ln1_w, w.ln1_b, d, R, 1, 0, 1,
-                                  EpQKVDecDense{ctx->qbuf, kc, vc, w.qkv_b, base, Mper, d, H, ctx->Tal, R, rowinfo}, ctx->xbuf, xpl));
-    else
-        WM_HIP(launch_skinny_norm(st, WRef{w.qkv_w, w.qkv_s}, 3 * d / 16, K32, h, w.ln1_w, w.ln1_b, d, R, 1, 0, 1,
-                                  EpQKVDec{ctx->qbuf, kc, vc, w.qkv_b, base, Mper, d, H, ctx->Tal, R}, ctx->xbuf, xpl));
+    const PfCarry c1 = pf ? PfCarry{pf_for_gemm(w.out_w, f8, d / 16, K32, false), 0} : PfCarry{};
+    TL_SET(lp, slot * 16 + 1 + 8192 * Mper);
+    WM_HIP(gemm_qkv(ctx, w, R, h, kc, vc, base, Mper, rowinfo, c1));
     if (kv_only) return WM_OK;
     // fused cross-attention query (FuseQ above): single-tile passes with bf16 weights whose projection plan has a compiled instance
     // OFF by default: measured 14.6 us for the fused launch against 5.6 (LN2 + cross-q) + 2.2 (boundary) + 6.5 (cross-attention)
@@ -1460,30 +1533,20 @@ static int dec_layer(wm_ctx* ctx, const DecLayerW& w, int slot, float* h, int b0
                                                     : PfJob{nullptr, nullptr, 0u, 0u, 0ull});
         const int main_total = H * nz;
         const int zs = spf.n_jobs ? nz + (pf_round8(main_total) - main_total + (int)spf.n_jobs + H - 1) / H : nz;
-        TL_SET(slot * 16 + 2 + 8192 * Mper);
+        TL_SET(lp, slot * 16 + 2 + 8192 * Mper);
         hipLaunchKernelGGL((k_attn_mfma<false, false, NoFuseQ>), dim3(1, H, zs), dim3(256), sizeof(AttnLds<1>), st, kc, vc, ctx->qbuf, sinfo, sskip,
-                           Mper | (nz << 8), H | (1 << 8) | (nqt << 16) | (1 << 24), ctx->Tal, 0, g_skinny_done, K32, ctx->xbuf, xpl, nullptr, nullptr, nullptr, spf, NoFuseQ{}, ctx->cur_anc, base, (const float*)nullptr, (const float*)nullptr TL_PASS);
+                           Mper | (nz << 8), H | (1 << 8) | (nqt << 16) | (1 << 24), ctx->Tal, 0, lp.done, K32, ctx->xbuf, xpl, nullptr, nullptr, nullptr, spf, NoFuseQ{}, ctx->cur_anc, base, (const float*)nullptr, (const float*)nullptr TL_PASS(lp));
         WM_HIP(hipGetLastError());
     }
     // 3. out_proj + residual
-    if (pf) g_pf_job = pf_for_gemm(w.cq_w, f8, d / 16, K32, true);
-    TL_SET(slot * 16 + 3 + 8192 * Mper);
-    // batched passes with the LayerNorm folded: no LayerNorm launch is left to pull the next GEMM's weights towards the chip, the launch that
-    // produces the residual rows carries that job (wm_skinny_gemm.h pf_set_batched); WM_PREFETCH=0 turns it off with the others
-    const bool pfb = fold && ctx->prefetch && R > 16;
-    const int MTp = (R + 15) / 16;
-    if (pfb) pf_set_batched(w.cq_w, nullptr, f8, d / 16, K32, MTp);
-    if (fold) WM_HIP(launch_skinny_rows(st, WRef{w.out_w, w.out_s}, d / 16, K32, R, ctx->xbuf, xpl, res_fold(w.out_b, w.ln2_w)));
-    else WM_HIP(launch_skinny_rows(st, WRef{w.out_w, w.out_s}, d / 16, K32, R, ctx->xbuf, xpl, EpResidual{h, w.out_b, d, R}));
+    const PfCarry c3 = carry_for(w.cq_w, d / 16, K32, true);
+    TL_SET(lp, slot * 16 + 3 + 8192 * Mper);
+    WM_HIP(gemm_out(ctx, w, R, h, c3));
     // 4. LN2 + cross-attention q (its own launch unless fused into 5.)
     if (!fuse_cq) {
-        if (pf) g_pf_job = kvjob;
-        TL_SET(slot * 16 + 4 + 8192 * Mper);
-        if (fold)
-            WM_HIP(launch_skinny_fold(st, WRef{w.cq_w, w.cq_s}, d / 16, K32, R, ctx->xn, xpl, fold_in(w.cq_c), EpF32{ctx->qbuf, w.cq_bf, d, R, 0.125f}));
-        else
-            WM_HIP(launch_skinny_norm(st, WRef{w.cq_w, w.cq_s}, d / 16, K32, h, w.ln2_w, w.ln2_b, d, R, 1, 0, 1, EpF32{ctx->qbuf, w.cq_b, d, R, 0.125f},
-                                      ctx->xbuf, xpl));
+        const PfCarry c4 = pf ? PfCarry{kvjob, 0} : PfCarry{};
+        TL_SET(lp, slot * 16 + 4 + 8192 * Mper);
+        WM_HIP(gemm_cross_q(ctx, w, R, h, c4));
     }
     // 5. cross-attention over the encoder K/V, 256 keys per block
     // a base pass with per-stream carry skips the blocks of carrying streams (about half of them at the measured acceptance
@@ -1496,7 +1559,7 @@ static int dec_layer(wm_ctx* ctx, const DecLayerW& w, int slot, float* h, int b0
             const int main_total = xgrid * H * nz;
             zs = nz + (pf_round8(main_total) - main_total + (int)xpf.n_jobs + xgrid * H - 1) / (xgrid * H);
         }
-        TL_SET(slot * 16 + 5 + 8192 * Mper);
+        TL_SET(lp, slot * 16 + 5 + 8192 * Mper);
         static const bool xattn_nt = [] { const char* v = std::getenv("WM_XATTN_NT"); return v ? std::atoi(v) != 0 : true; }();
 #if WM_ACT_PLANES == 2
         if (fuse_cq) {
@@ -1510,8 +1573,8 @@ static int dec_layer(wm_ctx* ctx, const DecLayerW& w, int slot, float* h, int b0
                 auto kern = k_attn_mfma<true, true, FQ>;                                                                      \
                 WM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
                 hipLaunchKernelGGL(kern, dim3(xgrid, H, zs), dim3(64 * (KSv > 4 ? KSv : 4)), lds, st, kx, vx, ctx->qbuf, (const int4*)nullptr, sskip, \
-                                   Mper | (nz << 8), H | (ctx->NS << 8) | (nqt << 16) | (xgrid << 24), ctx->Spad, ctx->S, g_skinny_done, K32, ctx->xbuf, xpl, ctx->cml, ctx->co, ctx->ticket, xpf, \
-                                   FQ{ln, w.cq_w, w.cq_b}, nullptr, base, (const float*)nullptr, (const float*)nullptr TL_PASS);                                                    \
+                                   Mper | (nz << 8), H | (ctx->NS << 8) | (nqt << 16) | (xgrid << 24), ctx->Spad, ctx->S, lp.done, K32, ctx->xbuf, xpl, ctx->cml, ctx->co, ctx->ticket, xpf, \
+                                   FQ{ln, w.cq_w, w.cq_b}, nullptr, base, (const float*)nullptr, (const float*)nullptr TL_PASS(lp));                                                    \
             } while (0)
             if (cqp.nk == 8 && cqp.ksplit == 5) WM_XFUSE(8, 5);
             else if (cqp.nk == 8 && cqp.ksplit == 4) WM_XFUSE(8, 4);
@@ -1525,39 +1588,30 @@ static int dec_layer(wm_ctx* ctx, const DecLayerW& w, int slot, float* h, int b0
 #endif
         if (x8)
             hipLaunchKernelGGL((k_attn_mfma<true, true, NoFuseQ, true>), dim3(xgrid, H, zs), dim3(256), sizeof(AttnLds<WM_XATTN_SPB_MAX>), st, kx, vx, ctx->qbuf, sinfo, sskip,
-                               Mper | (nz << 8), H | (ctx->NS << 8) | (nqt << 16) | (xgrid << 24), ctx->Spad, ctx->S, g_skinny_done, K32, ctx->xbuf, xpl, ctx->cml, ctx->co, ctx->ticket, xpf, NoFuseQ{}, nullptr, base,
-                               kxs, vxs TL_PASS);
+                               Mper | (nz << 8), H | (ctx->NS << 8) | (nqt << 16) | (xgrid << 24), ctx->Spad, ctx->S, lp.done, K32, ctx->xbuf, xpl, ctx->cml, ctx->co, ctx->ticket, xpf, NoFuseQ{}, nullptr, base,
+                               kxs, vxs TL_PASS(lp));
         else if (xattn_nt)
             hipLaunchKernelGGL((k_attn_mfma<true, true, NoFuseQ>), dim3(xgrid, H, zs), dim3(256), sizeof(AttnLds<WM_XATTN_SPB_MAX>), st, kx, vx, ctx->qbuf, sinfo, sskip,
-                               Mper | (nz << 8), H | (ctx->NS << 8) | (nqt << 16) | (xgrid << 24), ctx->Spad, ctx->S, g_skinny_done, K32, ctx->xbuf, xpl, ctx->cml, ctx->co, ctx->ticket, xpf, NoFuseQ{}, nullptr, base, (const float*)nullptr, (const float*)nullptr TL_PASS);
+                               Mper | (nz << 8), H | (ctx->NS << 8) | (nqt << 16) | (xgrid << 24), ctx->Spad, ctx->S, lp.done, K32, ctx->xbuf, xpl, ctx->cml, ctx->co, ctx->ticket, xpf, NoFuseQ{}, nullptr, base, (const float*)nullptr, (const float*)nullptr TL_PASS(lp));
         else
             hipLaunchKernelGGL((k_attn_mfma<true, false, NoFuseQ>), dim3(xgrid, H, zs), dim3(256), sizeof(AttnLds<WM_XATTN_SPB_MAX>), st, kx, vx, ctx->qbuf, sinfo, sskip,
-                               Mper | (nz << 8), H | (ctx->NS << 8) | (nqt << 16) | (xgrid << 24), ctx->Spad, ctx->S, g_skinny_done, K32, ctx->xbuf, xpl, ctx->cml, ctx->co, ctx->ticket, xpf, NoFuseQ{}, nullptr, base, (const float*)nullptr, (const float*)nullptr TL_PASS);
+                               Mper | (nz << 8), H | (ctx->NS << 8) | (nqt << 16) | (xgrid << 24), ctx->Spad, ctx->S, lp.done, K32, ctx->xbuf, xpl, ctx->cml, ctx->co, ctx->ticket, xpf, NoFuseQ{}, nullptr, base, (const float*)nullptr, (const float*)nullptr TL_PASS(lp));
         WM_HIP(hipGetLastError());
     }
     // 6. out_proj + residual
-    if (pf) g_pf_job = pf_for_gemm(w.fc1_w, f8, ctx->ffn / 16, K32, true);
-    TL_SET(slot * 16 + 6 + 8192 * Mper);
-    if (pfb) pf_set_batched(w.fc1_w, nullptr, f8, ctx->ffn / 16, K32, MTp);
-    if (fold) WM_HIP(launch_skinny_rows(st, WRef{w.cout_w, w.cout_s}, d / 16, K32, R, ctx->xbuf, xpl, res_fold(w.cout_b, w.ln3_w)));
-    else WM_HIP(launch_skinny_rows(st, WRef{w.cout_w, w.cout_s}, d / 16, K32, R, ctx->xbuf, xpl, EpResidual{h, w.cout_b, d, R}));
+    const PfCarry c6 = carry_for(w.fc1_w, ctx->ffn / 16, K32, true);
+    TL_SET(lp, slot * 16 + 6 + 8192 * Mper);
+    WM_HIP(gemm_cross_out(ctx, w, R, h, c6));
     // 7. LN3 + fc1 + GELU
-    if (pf) g_pf_job = pf_for_gemm(w.fc2_w, f8, d / 16, F32, false);
-    if (ctx->prefetch && R > 16 && !fold) g_ln_pf_extra = w.fc2_w;     // batched passes: the LayerNorm launch pulls FC1 and FC2 (same size)
-    TL_SET(slot * 16 + 7 + 8192 * Mper);
-    if (pfb) pf_set_batched(w.fc2_w, nullptr, f8, d / 16, F32, MTp);
-    if (fold)
-        WM_HIP(launch_skinny_fold(st, WRef{w.fc1_w, w.fc1_s}, ctx->ffn / 16, K32, R, ctx->xn, xpl, fold_in(w.fc1_c),
-                                  EpPackedAct<1>{ctx->fbuf, ctx->fbuf + fpl, w.fc1_bf, F32, R}));
-    else
-        WM_HIP(launch_skinny_norm(st, WRef{w.fc1_w, w.fc1_s}, ctx->ffn / 16, K32, h, w.ln3_w, w.ln3_b, d, R, 1, 0, 1,
-                                  EpPackedAct<1>{ctx->fbuf, ctx->fbuf + fpl, w.fc1_b, F32, R}, ctx->xbuf, xpl));
-    if (pfb && next) pf_set_batched(next->qkv_w, nullptr, f8, 3 * d / 16, K32, MTp);
+    const PfCarry c7 = carry_for(w.fc2_w, d / 16, F32, false);
+    // unfolded batched passes: the LayerNorm launch pulls FC1 and FC2 (same size)
+    const void* ln_extra = (ctx->prefetch && R > 16 && !fold) ? w.fc2_w : nullptr;
+    TL_SET(lp, slot * 16 + 7 + 8192 * Mper);
+    WM_HIP(gemm_fc1(ctx, w, R, h, c7, ln_extra));
     // 8. fc2 + residual (fold: + the operand of the NEXT layer's LN1 + QKV; the last layer's rows go to the final LayerNorm launch instead)
-    if (pf && next) g_pf_job = pf_for_gemm(next->qkv_w, f8, 3 * d / 16, K32, true);
-    TL_SET(slot * 16 + 8 + 8192 * Mper);
-    if (fold && next) WM_HIP(launch_skinny_rows(st, WRef{w.fc2_w, w.fc2_s}, d / 16, F32, R, ctx->fbuf, fpl, res_fold(w.fc2_b, next->ln1_w)));
-    else WM_HIP(launch_skinny_rows(st, WRef{w.fc2_w, w.fc2_s}, d / 16, F32, R, ctx->fbuf, fpl, EpResidual{h, w.fc2_b, d, R}));
+    const PfCarry c8 = next ? carry_for(next->qkv_w, 3 * d / 16, K32, true) : PfCarry{};
+    TL_SET(lp, slot * 16 + 8 + 8192 * Mper);
+    WM_HIP(gemm_fc2(ctx, w, R, h, next ? next->ln1_w : nullptr, c8));
     return WM_OK;
 }
 
@@ -1607,7 +1661,7 @@ int wm_dec_fold_init(wm_ctx* ctx)
 int wm_dec_stage_layers(wm_ctx* ctx, int b0, int nb, int Mper, int mode)
 {
     hipStream_t st = ctx->stream;
-    g_skinny_done = ctx->use_done ? ctx->done : nullptr;
+    ctx->lp.done = ctx->use_done ? ctx->done : nullptr;
     const int d = ctx->d, R = nb * Mper;
     // mode 2 = merged step: per stream either its verify rows (as mode 1) or its one base row (k_step_begin: rowinfo / sinfo)
     const int* base = (mode == 0 ? ctx->kvlen : ctx->L) + b0;          // mode 2: positions come from rowinfo / sinfo
@@ -1655,7 +1709,7 @@ __global__ void k_fill_int(int* __restrict__ p, int n, int v)
 static int replay_tile(wm_ctx* ctx, int b0, int nb, int pos0, int Mper, int n_layers, const wm_replay_hooks& hk)
 {
     hipStream_t st = ctx->stream;
-    g_skinny_done = nullptr;
+    ctx->lp.done = nullptr;
     const int d = ctx->d, R = nb * Mper;
     const int* base = ctx->kvlen + b0;
     if (R > ctx->Rcap || Mper > 16 || Mper < 1 || n_layers > ctx->cfg.dec_layers) { ctx->err = "replay pass exceeds the row capacity of the context"; return WM_ERR_ARG; }
@@ -1735,7 +1789,7 @@ int wm_dec_stage_final(wm_ctx* ctx, int b0, int nb, int Mper, int mode, int medu
         if (rc) return rc;
         if (sskip) {
             hipLaunchKernelGGL(k_rows_take_carried, dim3(R), dim3(256), 0, st, ctx->hblk + (size_t)b0 * d, ctx->hb_keep + (size_t)b0 * d,
-                               sskip, d, R, g_skinny_done);
+                               sskip, d, R, ctx->lp.done);
             WM_HIP(hipGetLastError());
         }
     }
@@ -1747,14 +1801,15 @@ int wm_dec_stage_final(wm_ctx* ctx, int b0, int nb, int Mper, int mode, int medu
 int wm_dec_stage_heads(wm_ctx* ctx, int nsel, int sel_mul, int sel_off, int medusa)
 {
     hipStream_t st = ctx->stream;
-    TL_SET(1000);
+    DecLaunch& lp = ctx->lp;
+    TL_SET(lp, 1000);
     const int d = ctx->d, K32 = d / 32, K = ctx->K;
     const int nout = medusa ? K + 1 : 1;
     const size_t ypl = (size_t)ctx->Rcap * d;
     if (nsel * nout > ctx->Rcap) { ctx->err = "head stage exceeds the row capacity of the context"; return WM_ERR_ARG; }
     if (!ctx->block) {
         // Medusa-Linear: every head (incl. base head 0) = x + SiLU(W_k x + b_k), then proj_out (model.py:1274-1284)
-        WM_HIP(launch_skinny_norm(st, ctx->heads_w, nout * d / 16, K32, ctx->hf_cur, nullptr, nullptr, d, nsel, sel_mul, sel_off, 0,
+        WM_HIP(launch_skinny_norm(lp, ctx->heads_w, nout * d / 16, K32, ctx->hf_cur, nullptr, nullptr, d, nsel, sel_mul, sel_off, 0,
                                   EpHead{ctx->ybuf, ctx->ybuf + ypl, ctx->hf_cur, ctx->heads_b, d, K32, nout, 0, nsel, sel_mul, sel_off},
                                   ctx->xbuf, ypl));
     } else {
@@ -1763,13 +1818,13 @@ int wm_dec_stage_heads(wm_ctx* ctx, int nsel, int sel_mul, int sel_off, int medu
                            nullptr, nullptr, ctx->ybuf, ypl, K32, nout, 0, d, nsel, nullptr, nullptr);
         WM_HIP(hipGetLastError());
         if (medusa)
-            WM_HIP(launch_skinny_norm(st, ctx->heads_w, K * d / 16, K32, ctx->hblk, nullptr, nullptr, d, nsel, sel_mul, sel_off, 0,
+            WM_HIP(launch_skinny_norm(lp, ctx->heads_w, K * d / 16, K32, ctx->hblk, nullptr, nullptr, d, nsel, sel_mul, sel_off, 0,
                                       EpHead{ctx->ybuf, ctx->ybuf + ypl, ctx->hblk, ctx->heads_b, d, K32, nout, 1, nsel, sel_mul, sel_off},
                                       ctx->xbuf, ypl));
     }
     // shared vocabulary projection (tied proj_out, model.py:1277)
-    TL_SET(1001);
-    WM_HIP(launch_skinny_rows(st, ctx->vocab_w, ctx->Vpad / 16, K32, nsel * nout, ctx->ybuf, ypl,
+    TL_SET(lp, 1001);
+    WM_HIP(launch_skinny_rows(lp, ctx->vocab_w, ctx->Vpad / 16, K32, nsel * nout, ctx->ybuf, ypl,
                               EpLogits{ctx->logits, nullptr, ctx->Vpad, nsel * nout, 1.0f}));
     return WM_OK;
 }
@@ -1871,13 +1926,13 @@ int wm_dec_iter_rest(wm_ctx* ctx, int Mper_base)
     const size_t lds = rp_lds_bytes(ts, gp.V);
     const bool carry = ctx->host_carry;
     ctx->hf_cur = ctx->hf;
-    g_skinny_done = ctx->use_done ? ctx->done : nullptr;
+    ctx->lp.done = ctx->use_done ? ctx->done : nullptr;
     int rc = wm_dec_stage_heads(ctx, nb, Mper_base, Mper_base - 1, 1);
     if (rc) return rc;
     const int vr = ctx->tn ? ctx->tn : rps;                  // rows per stream of the verify pass: tree nodes / chain candidates
     if (ctx->tn) {
         hipLaunchKernelGGL(k_tree_cand, dim3(nb * rps), dim3(256), 0, st, ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, ctx->tree,
-                           ctx->cand, g_skinny_done);
+                           ctx->cand, ctx->lp.done);
         WM_HIP(hipGetLastError());
     } else {
         // slice partials of every head's row (head 1's slices also keep their six best when the verify pass carries sibling rows), then ONE
@@ -1983,8 +2038,8 @@ int wm_dec_step(wm_ctx* ctx, int)
     const GenDev gp = ctx->gp;
     const TsDev ts = ctx->ts;
     const size_t lds = rp_lds_bytes(ts, gp.V);
-    g_skinny_done = ctx->use_done ? ctx->done : nullptr;
-    g_skinny_ntiles = nullptr;
+    ctx->lp.done = ctx->use_done ? ctx->done : nullptr;
+    ctx->lp.ntiles = nullptr;
     if (B > 1024) { ctx->err = "merged-step schedule: more than 1024 streams"; return WM_ERR_ARG; }
     hipLaunchKernelGGL(k_step_begin, dim3(1), dim3(256), 0, st, ctx->carry, ctx->L, ctx->kvlen, ctx->finished, ctx->rowinfo, ctx->sinfo, ctx->steprows, rps, B, B * rps);
     WM_HIP(hipGetLastError());
@@ -2008,12 +2063,12 @@ int wm_dec_step(wm_ctx* ctx, int)
         WM_HIP(hipGetLastError());
     }
     // (d) ONE pass over the dense rows: verify rows and base rows; the launches are sized for B * rps rows, token tiles beyond the step's
-    //     rows exit at once (g_skinny_ntiles)
-    g_skinny_ntiles = ctx->steprows + 1;
+    //     rows exit at once (DecLaunch::ntiles)
+    ctx->lp.ntiles = ctx->steprows + 1;
     rc = wm_dec_stage_layers(ctx, 0, B, rps, 2);
     if (rc == WM_OK) rc = wm_dec_stage_final(ctx, 0, B, rps, 2, 0);
     if (rc == WM_OK) rc = wm_dec_stage_heads(ctx, B * rps, 1, 0, 0);
-    g_skinny_ntiles = nullptr;
+    ctx->lp.ntiles = nullptr;
     if (rc) return rc;
     if (wm_rules_on(ts)) {
         k_select1_ts<true><<<dim3(SEL_SP, B * rps), dim3(256), lds, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, rps, ctx->part1,
@@ -2053,10 +2108,11 @@ int wm_dec_step(wm_ctx* ctx, int)
 int wm_dec_profile(wm_ctx* ctx, int kernel, int rows, int reps, float* ms, double* bytes)
 {
     if (kernel < 0 || kernel > 7 || rows < 1 || rows > ctx->Rcap) { ctx->err = "wm_profile_kernel: bad arguments"; return WM_ERR_ARG; }
-    g_skinny_done = nullptr;
+    ctx->lp.done = nullptr;
+    ctx->lp.ntiles = nullptr;
     hipStream_t st = ctx->stream;
-    const int d = ctx->d, K32 = d / 32, R = rows, H = ctx->H, F32 = ctx->ffn / 32;
-    const size_t xpl = (size_t)ctx->Rcap * d, fpl = (size_t)ctx->Rcap * ctx->ffn;
+    const int d = ctx->d, K32 = d / 32, R = rows;
+    const size_t xpl = (size_t)ctx->Rcap * d;
     const DecLayerW& w = ctx->dec[0];
     WM_HIP(hipMemsetAsync(ctx->h, 0, (size_t)ctx->Rcap * d * sizeof(float), st));
     WM_HIP(hipMemsetAsync(ctx->kvlen, 0, sizeof(int) * ctx->maxB, st));
@@ -2064,45 +2120,16 @@ int wm_dec_profile(wm_ctx* ctx, int kernel, int rows, int reps, float* ms, doubl
     // the QKV epilogue scatters K / V rows into the self-attention cache: the rows go in as the verify pass would put them, Rcap / maxB
     // rows per stream from position 0 (<= 64 <= Tal; all of them on one stream would run past a head's slab once rows > Tal)
     const int mper = ctx->Rcap / ctx->maxB;
-    const bool fold = ctx->ln_fold;       // the launches as dec_layer issues them (LayerNorm folded: wm_common.h)
-    const FoldIn fin_base{ctx->lnstats, nullptr, d / 16, ctx->Rcap, 1.0f / (float)d};
-    auto fold_in = [&](const float* c) { FoldIn f = fin_base; f.c = c; return f; };
-    auto res_fold = [&](const float* bias, const float* gnext) {
-        EpResidualFold e{ctx->h, bias, d, R}; e.gnext = gnext; e.xo = ctx->xn; e.xplane = xpl; e.stats = ctx->lnstats; e.K32 = K32; e.sld = ctx->Rcap;
-        return e;
-    };
+    // the layer's GEMMs as dec_layer issues them (the same gemm_* helpers), without a prefetch carry; FC2 writes layer 0's own LN1 operand
     auto body = [&]() -> int {
-        if ((all || kernel == 1) && fold)
-            WM_HIP(launch_skinny_fold(st, WRef{w.qkv_w, w.qkv_s}, 3 * d / 16, K32, R, ctx->xn, xpl, fold_in(w.qkv_c),
-                                      EpQKVDec{ctx->qbuf, ctx->kc, ctx->vc, w.qkv_bf, ctx->kvlen, mper, d, H, ctx->Tal, R}));
-        else if (all || kernel == 1)
-            WM_HIP(launch_skinny_norm(st, WRef{w.qkv_w, w.qkv_s}, 3 * d / 16, K32, ctx->h, w.ln1_w, w.ln1_b, d, R, 1, 0, 1,
-                                      EpQKVDec{ctx->qbuf, ctx->kc, ctx->vc, w.qkv_b, ctx->kvlen, mper, d, H, ctx->Tal, R}, ctx->xbuf, xpl));
-        if ((all || kernel == 2) && fold)
-            WM_HIP(launch_skinny_rows(st, WRef{w.out_w, w.out_s}, d / 16, K32, R, ctx->xbuf, xpl, res_fold(w.out_b, w.ln2_w)));
-        else if (all || kernel == 2)
-            WM_HIP(launch_skinny_rows(st, WRef{w.out_w, w.out_s}, d / 16, K32, R, ctx->xbuf, xpl, EpResidual{ctx->h, w.out_b, d, R}));
-        if ((all || kernel == 3) && fold)
-            WM_HIP(launch_skinny_fold(st, WRef{w.cq_w, w.cq_s}, d / 16, K32, R, ctx->xn, xpl, fold_in(w.cq_c), EpF32{ctx->qbuf, w.cq_bf, d, R, 0.125f}));
-        else if (all || kernel == 3)
-            WM_HIP(launch_skinny_norm(st, WRef{w.cq_w, w.cq_s}, d / 16, K32, ctx->h, w.ln2_w, w.ln2_b, d, R, 1, 0, 1, EpF32{ctx->qbuf, w.cq_b, d, R, 0.125f},
-                                      ctx->xbuf, xpl));
-        if ((all || kernel == 4) && fold)
-            WM_HIP(launch_skinny_rows(st, WRef{w.cout_w, w.cout_s}, d / 16, K32, R, ctx->xbuf, xpl, res_fold(w.cout_b, w.ln3_w)));
-        else if (all || kernel == 4)
-            WM_HIP(launch_skinny_rows(st, WRef{w.cout_w, w.cout_s}, d / 16, K32, R, ctx->xbuf, xpl, EpResidual{ctx->h, w.cout_b, d, R}));
-        if ((all || kernel == 5) && fold)
-            WM_HIP(launch_skinny_fold(st, WRef{w.fc1_w, w.fc1_s}, ctx->ffn / 16, K32, R, ctx->xn, xpl, fold_in(w.fc1_c),
-                                      EpPackedAct<1>{ctx->fbuf, ctx->fbuf + fpl, w.fc1_bf, F32, R}));
-        else if (all || kernel == 5)
-            WM_HIP(launch_skinny_norm(st, WRef{w.fc1_w, w.fc1_s}, ctx->ffn / 16, K32, ctx->h, w.ln3_w, w.ln3_b, d, R, 1, 0, 1,
-                                      EpPackedAct<1>{ctx->fbuf, ctx->fbuf + fpl, w.fc1_b, F32, R}, ctx->xbuf, xpl));
-        if ((all || kernel == 6) && fold)
-            WM_HIP(launch_skinny_rows(st, WRef{w.fc2_w, w.fc2_s}, d / 16, F32, R, ctx->fbuf, fpl, res_fold(w.fc2_b, w.ln1_w)));
-        else if (all || kernel == 6)
-            WM_HIP(launch_skinny_rows(st, WRef{w.fc2_w, w.fc2_s}, d / 16, F32, R, ctx->fbuf, fpl, EpResidual{ctx->h, w.fc2_b, d, R}));
+        if (all || kernel == 1) WM_HIP(gemm_qkv(ctx, w, R, ctx->h, ctx->kc, ctx->vc, ctx->kvlen, mper, nullptr));
+        if (all || kernel == 2) WM_HIP(gemm_out(ctx, w, R, ctx->h));
+        if (all || kernel == 3) WM_HIP(gemm_cross_q(ctx, w, R, ctx->h));
+        if (all || kernel == 4) WM_HIP(gemm_cross_out(ctx, w, R, ctx->h));
+        if (all || kernel == 5) WM_HIP(gemm_fc1(ctx, w, R, ctx->h));
+        if (all || kernel == 6) WM_HIP(gemm_fc2(ctx, w, R, ctx->h, w.ln1_w));
         if (kernel == 7)
-            WM_HIP(launch_skinny_rows(st, ctx->vocab_w, ctx->Vpad / 16, K32, R, ctx->ybuf, xpl, EpLogits{ctx->logits, nullptr, ctx->Vpad, R, 1.0f}));
+            WM_HIP(launch_skinny_rows(ctx->lp, ctx->vocab_w, ctx->Vpad / 16, K32, R, ctx->ybuf, xpl, EpLogits{ctx->logits, nullptr, ctx->Vpad, R, 1.0f}));
         return WM_OK;
     };
     int rc = body();

@@ -108,6 +108,7 @@ extern "C" int wm_create(const wm_config* cfg, const wm_weights* w, int device, 
     CREATE_HIP(hipSetDevice(device));
     if (hip_stream) ctx->stream = reinterpret_cast<hipStream_t>(hip_stream);
     else { CREATE_HIP(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)); ctx->own_stream = true; }
+    ctx->lp.st = ctx->stream;
     CREATE_HIP(hipEventCreate(&ctx->ev0));
     CREATE_HIP(hipEventCreate(&ctx->ev1));
     { const char* v = std::getenv("WM_PREFETCH"); ctx->prefetch = !(v && std::atoi(v) == 0); }

@@ -116,11 +116,23 @@ struct TreeDev {
     int retrieve[WM_TREE_MAX_PATHS][16];            // [path][depth] -> node (retrieve_indices)
 };
 
+// What every launch of a decode pass is given besides its own operands (wm_skinny_gemm.h launchers, wm_decoder.hip).  One per context
+// (wm_ctx::lp): the entry points of wm_decoder.hip that start a pass write done / ntiles, the stage functions called after them read it.
+struct DecLaunch {
+    hipStream_t st = nullptr;           // the context's stream
+    const int* done = nullptr;          // device flag every kernel of the pass checks on entry (all streams finished); nullptr: none
+    const int* ntiles = nullptr;        // merged-step schedule: device word = 16-row token tiles that hold rows in this step; nullptr: all tiles
+#ifdef WM_TIMELINE
+    int tl_tag = 0;                     // timeline build: tag of the next launch (TL_SET / TL_PASS)
+#endif
+};
+
 struct wm_ctx {
     wm_config cfg{};
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
+    DecLaunch lp;                       // launch state of the decode pass being enqueued (lp.st == stream)
     std::string err;
 
     // derived sizes

@@ -38,7 +38,6 @@ struct TlRec { unsigned tag, block; unsigned long long rt0, rt1; unsigned c_prep
 static __device__ TlRec* g_tl_buf = nullptr;
 static __device__ unsigned* g_tl_idx = nullptr;
 static __device__ unsigned g_tl_cap = 0;
-static thread_local int g_tl_tag = 0;              // host: tag of the next launch
 struct TlProbe {
     unsigned long long rt0, c0; unsigned c_prep, c_mid; int tag;
     __device__ __forceinline__ void begin(int t) { tag = t; rt0 = __builtin_amdgcn_s_memrealtime(); c0 = __builtin_readcyclecounter(); c_mid = 0; c_prep = 0; }
@@ -53,20 +52,20 @@ struct TlProbe {
     }
 };
 #define TL_ARG , int tl_tag
-#define TL_PASS , g_tl_tag
+#define TL_PASS(lp) , (lp).tl_tag            // host: the tag travels with the pass's launch state (wm_internal.h DecLaunch)
 #define TL_BEGIN TlProbe tl_; tl_.begin(tl_tag);
 #define TL_PREP tl_.prep();
 #define TL_MID tl_.mid();
 #define TL_END tl_.end();
-#define TL_SET(t) (g_tl_tag = (t))
+#define TL_SET(lp, t) ((lp).tl_tag = (t))
 #else
 #define TL_ARG
-#define TL_PASS
+#define TL_PASS(lp)
 #define TL_BEGIN
 #define TL_PREP
 #define TL_MID
 #define TL_END
-#define TL_SET(t) ((void)0)
+#define TL_SET(lp, t) ((void)0)
 #endif
 
 // ---- weight fragments: raw load now, widen later (an fp8 fragment must not be converted before the batch is in flight) ----
@@ -116,14 +115,13 @@ __device__ __forceinline__ void glds16_f(const float* gsrc, char* lds_wave_base)
 // (Tried first as a second stream inside the hipGraph: the fork/join event nodes raised every launch boundary from 1.9 to
 // 12-14 us — profiles/r02_timeline_sidestream_prefetch.md.)
 struct PfJob { const char* p0; const char* p1; unsigned job_bytes; unsigned n_jobs; unsigned long long total; };
-static thread_local PfJob g_pf_job = {nullptr, nullptr, 0u, 0u, 0ull};     // host: rides on the next launch, which clears it
-// host: a second matrix OF THE SAME SIZE the next batched LayerNorm launch (R > 16 rows) should also pull in (LN3 + FC1: the FC2 weights, which
-// no launch in between can carry); cleared by that launch
-static thread_local const void* g_ln_pf_extra = nullptr;
-// host: the prefetch job of a BATCHED launch (k_rows_gemm / k_skinny2_gemm; round 6: with the LayerNorm folded there is no LayerNorm launch left to
-// carry the next GEMM's weights, so the launch that produces the residual row carries them); sliced = pf_block_sliced (token-tile consumer)
-static thread_local PfJob g_pf_batched = {nullptr, nullptr, 0u, 0u, 0ull};
-static thread_local int g_pf_batched_sliced = 0;
+// host: the job ONE launch carries, an argument of launch_skinny_rows / _fold / _norm (default: none).  A launch is either single-tile (R <= 16 rows:
+// k_skinny_gemm takes the job) or batched (R > 16; round 6: with the LayerNorm folded there is no LayerNorm launch left to carry the next GEMM's
+// weights, so the launch that produces the residual row carries them): k_rows_gemm takes the job and `sliced` (pf_block_sliced, cut for a token-tile
+// consumer), k_skinny2_gemm takes an unsliced job and drops a sliced one, k_skinny2_norm and k_tile_gemm carry none.  A job offered to a launch
+// that ends in k_tile_gemm is therefore dropped (a pure hint).  That route needs an unfolded GEMM of N16 >= 1024 row tiles and a job: the GEMMs
+// that are given one have N16 = d / 16 <= 80 or are folded, and the vocabulary projection is never given one.
+struct PfCarry { PfJob job = {nullptr, nullptr, 0u, 0u, 0ull}; int sliced = 0; };
 
 __device__ __forceinline__ void pf_block(const PfJob& pf, int job)
 {
@@ -1032,11 +1030,11 @@ k_tile_gemm(const bf16_t* __restrict__ W, int N16, int K32, int nk, const bf16_t
 }
 
 // ---- host-side launch plan -------------------------------------------------------------------
-static thread_local const int* g_skinny_done = nullptr;     // device flag checked by every launch of this translation unit
-// merged-step schedule (wm_decoder.hip wm_dec_step): the pass's rows are dense and their number changes from step to step while the launches
-// (a captured graph) are sized for the maximum: device word = 16-row token tiles that hold rows in this step; the batched kernels' blocks
-// of tiles beyond it exit at once.  nullptr (every other pass): all tiles of the launch.
-static thread_local const int* g_skinny_ntiles = nullptr;
+// Every launcher below takes the pass's launch state (wm_internal.h DecLaunch, kept on the context and written by the entry points of
+// wm_decoder.hip) where a stream would go: lp.st, lp.done = the device flag every kernel of the pass checks on entry, lp.ntiles = merged-step
+// schedule (wm_dec_step): the pass's rows are dense and their number changes from step to step while the launches (a captured graph) are sized
+// for the maximum: device word = 16-row token tiles that hold rows in this step; the batched kernels' blocks of tiles beyond it exit at once.
+// nullptr (every other pass): all tiles of the launch.
 struct SkinnyPlan { int ksplit, rt, nk, RT; };      // rt: row-tile groups per block (waves), RT: row tiles per wave (registers)
 
 // K-slices of at most 16 fragments (8 when the token operand is normalised in registers) and, if possible, >= 1024 waves.
@@ -1070,6 +1068,7 @@ static inline SkinnyPlan skinny_plan(int N16, int K32, bool norm_loader) {
     return p;
 }
 
+// the bytes block j of the skinny GEMM (W, N16, K32, loader kind) reads: one prefetch job per consumer block
 static inline PfJob pf_for_gemm(const bf16_t* W, bool fp8, int N16, int K32, bool norm_loader) {
     const SkinnyPlan p = skinny_plan(N16, K32, norm_loader);
     const int per_block = p.rt * p.RT, grid = (N16 + per_block - 1) / per_block;
@@ -1081,18 +1080,15 @@ static inline PfJob pf_for_gemm(const bf16_t* W, bool fp8, int N16, int K32, boo
 
 // The job a BATCHED launch (R > 16 rows) carries for the LayerNorm-folded GEMM (W, N16, K32) that follows it, `extra` = a second matrix of the
 // same size: MT == 2 -> consumer k_skinny2_gemm, one job per consumer block; MT >= 3 -> token-tile consumer, 64 KB pieces of XCD eighths.
-static inline void pf_set_batched(const bf16_t* W, const void* extra, bool fp8, int N16, int K32, int MT) {
+static inline PfCarry pf_batched(const bf16_t* W, const void* extra, bool fp8, int N16, int K32, int MT) {
     const SkinnyPlan p = skinny_plan(N16, K32, true);
     const unsigned long long wbytes = (unsigned long long)N16 * K32 * (fp8 ? 512 : 1024);
     if (MT == 2 && skinny_env("WM_SKINNY2", 1) && p.ksplit * p.rt <= 10) {
-        g_pf_batched = PfJob{reinterpret_cast<const char*>(W), reinterpret_cast<const char*>(extra), (unsigned)((unsigned long long)p.rt * K32 * (fp8 ? 512 : 1024)),
-                             (unsigned)((N16 + p.rt - 1) / p.rt), wbytes};
-        g_pf_batched_sliced = 0;
-    } else {
-        const unsigned long long slice = ((wbytes + 7) / 8 + 1023) & ~1023ull;
-        g_pf_batched = PfJob{reinterpret_cast<const char*>(W), reinterpret_cast<const char*>(extra), 65536u, (unsigned)(8 * ((slice + 65535) / 65536)), wbytes};
-        g_pf_batched_sliced = 1;
+        return PfCarry{PfJob{reinterpret_cast<const char*>(W), reinterpret_cast<const char*>(extra), (unsigned)((unsigned long long)p.rt * K32 * (fp8 ? 512 : 1024)),
+                             (unsigned)((N16 + p.rt - 1) / p.rt), wbytes}, 0};
     }
+    const unsigned long long slice = ((wbytes + 7) / 8 + 1023) & ~1023ull;
+    return PfCarry{PfJob{reinterpret_cast<const char*>(W), reinterpret_cast<const char*>(extra), 65536u, (unsigned)(8 * ((slice + 65535) / 65536)), wbytes}, 1};
 }
 
 // a weight matrix in the packed layout: bf16 (scale == nullptr) or fp8 e4m3 with one fp32 scale per output row
@@ -1102,7 +1098,7 @@ struct WRef {
 };
 
 template <int NK, int RT, bool W8, class Ld, class Ep, bool FOLD = false>
-static inline hipError_t launch_skinny_nk_rt(hipStream_t st, WRef W, int N16, int K32, const SkinnyPlan& p, const Ld& ld, const Ep& ep, const FoldIn& fold = FoldIn{}) {
+static inline hipError_t launch_skinny_nk_rt(const DecLaunch& lp, WRef W, int N16, int K32, const SkinnyPlan& p, const Ld& ld, const Ep& ep, const PfJob& pf, const FoldIn& fold = FoldIn{}) {
     const int per_block = p.rt * RT;
     const int grid = (N16 + per_block - 1) / per_block;
     const int threads = 64 * p.ksplit * p.rt;
@@ -1114,48 +1110,44 @@ static inline hipError_t launch_skinny_nk_rt(hipStream_t st, WRef W, int N16, in
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    const PfJob pf = g_pf_job;
-    g_pf_job = PfJob{nullptr, nullptr, 0u, 0u, 0ull};
     const int grid_all = pf.n_jobs ? pf_round8(grid) + (int)pf.n_jobs : grid;
     const LdArgs la = ld.pack();
     if (p.ksplit > 255 || p.rt > 255 || magic > 32767 || !ld.packs()) return hipErrorInvalidConfiguration;
-    hipLaunchKernelGGL(kern, dim3(grid_all), dim3(threads), lds, st, W.w, la.a, la.b, la.c, la.i0, la.i1, N16, K32, p.ksplit | (p.rt << 8) | (magic << 16), grid,
-                       W.scale, g_skinny_done, ep, pf, fold TL_PASS);
+    hipLaunchKernelGGL(kern, dim3(grid_all), dim3(threads), lds, lp.st, W.w, la.a, la.b, la.c, la.i0, la.i1, N16, K32, p.ksplit | (p.rt << 8) | (magic << 16), grid,
+                       W.scale, lp.done, ep, pf, fold TL_PASS(lp));
     return hipGetLastError();
 }
-// the bytes block j of the skinny GEMM (W, N16, K32, loader kind) reads: one prefetch job per consumer block
-static inline PfJob pf_for_gemm(const bf16_t* W, bool fp8, int N16, int K32, bool norm_loader);
 template <int NK, bool W8, class Ld, class Ep, bool FOLD = false>
-static inline hipError_t launch_skinny_nk(hipStream_t st, WRef W, int N16, int K32, const SkinnyPlan& p, const Ld& ld, const Ep& ep, const FoldIn& fold = FoldIn{}) {
+static inline hipError_t launch_skinny_nk(const DecLaunch& lp, WRef W, int N16, int K32, const SkinnyPlan& p, const Ld& ld, const Ep& ep, const PfJob& pf, const FoldIn& fold = FoldIn{}) {
     if constexpr (NK <= 8) {
-        if (p.RT == 2 && p.ksplit >= 2) return launch_skinny_nk_rt<NK, 2, W8, Ld, Ep, FOLD>(st, W, N16, K32, p, ld, ep, fold);
+        if (p.RT == 2 && p.ksplit >= 2) return launch_skinny_nk_rt<NK, 2, W8, Ld, Ep, FOLD>(lp, W, N16, K32, p, ld, ep, pf, fold);
     }
-    return launch_skinny_nk_rt<NK, 1, W8, Ld, Ep, FOLD>(st, W, N16, K32, p, ld, ep, fold);
+    return launch_skinny_nk_rt<NK, 1, W8, Ld, Ep, FOLD>(lp, W, N16, K32, p, ld, ep, pf, fold);
 }
 
 template <bool W8, class Ld, class Ep, bool FOLD = false>
-static inline hipError_t launch_skinny_w(hipStream_t st, WRef W, int N16, int K32, const SkinnyPlan& p, const Ld& ld, const Ep& ep, const FoldIn& fold = FoldIn{}) {
+static inline hipError_t launch_skinny_w(const DecLaunch& lp, WRef W, int N16, int K32, const SkinnyPlan& p, const Ld& ld, const Ep& ep, const PfJob& pf, const FoldIn& fold = FoldIn{}) {
     if (p.ksplit * p.rt > 10 || p.ksplit * p.nk != K32 || (Ld::kNorm && p.nk > 8)) return hipErrorInvalidConfiguration;
     if (Ld::kNorm && K32 * 16 > ((p.nk + 3) / 4) * 64 * p.ksplit * p.rt) return hipErrorInvalidConfiguration;      // gamma | beta float4 per thread (LdNormT::issue)
     switch (p.nk) {
-        case 4: return launch_skinny_nk<4, W8, Ld, Ep, FOLD>(st, W, N16, K32, p, ld, ep, fold);
-        case 8: return launch_skinny_nk<8, W8, Ld, Ep, FOLD>(st, W, N16, K32, p, ld, ep, fold);
-        case 12: if constexpr (!Ld::kNorm && !FOLD) return launch_skinny_nk<12, W8>(st, W, N16, K32, p, ld, ep); break;      // (a folded GEMM keeps the LayerNorm plan: <= 8 fragments per K-slice)
-        case 16: if constexpr (!Ld::kNorm && !FOLD) return launch_skinny_nk<16, W8>(st, W, N16, K32, p, ld, ep); break;
+        case 4: return launch_skinny_nk<4, W8, Ld, Ep, FOLD>(lp, W, N16, K32, p, ld, ep, pf, fold);
+        case 8: return launch_skinny_nk<8, W8, Ld, Ep, FOLD>(lp, W, N16, K32, p, ld, ep, pf, fold);
+        case 12: if constexpr (!Ld::kNorm && !FOLD) return launch_skinny_nk<12, W8>(lp, W, N16, K32, p, ld, ep, pf); break;     // (a folded GEMM keeps the LayerNorm plan: <= 8 fragments per K-slice)
+        case 16: if constexpr (!Ld::kNorm && !FOLD) return launch_skinny_nk<16, W8>(lp, W, N16, K32, p, ld, ep, pf); break;
         default: break;
     }
     return hipErrorInvalidConfiguration;
 }
 
 template <class Ld, class Ep, bool FOLD = false>
-static inline hipError_t launch_skinny(hipStream_t st, WRef W, int N16, int K32, const SkinnyPlan& p, const Ld& ld, const Ep& ep, const FoldIn& fold = FoldIn{}) {
-    if (W.scale) return launch_skinny_w<true, Ld, Ep, FOLD>(st, W, N16, K32, p, ld, ep, fold);
-    return launch_skinny_w<false, Ld, Ep, FOLD>(st, W, N16, K32, p, ld, ep, fold);
+static inline hipError_t launch_skinny(const DecLaunch& lp, WRef W, int N16, int K32, const SkinnyPlan& p, const Ld& ld, const Ep& ep, const PfJob& pf, const FoldIn& fold = FoldIn{}) {
+    if (W.scale) return launch_skinny_w<true, Ld, Ep, FOLD>(lp, W, N16, K32, p, ld, ep, pf, fold);
+    return launch_skinny_w<false, Ld, Ep, FOLD>(lp, W, N16, K32, p, ld, ep, pf, fold);
 }
 
 template <int NKR, int RT, bool W8, class Ep, bool FOLD = false, int TT = 2>
-static inline hipError_t launch_rows_gemm_w(hipStream_t st, WRef W, int N16, int K32, const SkinnyPlan& p,
-                                            const bf16_t* X, size_t plane, int MT, const Ep& ep, const FoldIn& fold = FoldIn{}) {
+static inline hipError_t launch_rows_gemm_w(const DecLaunch& lp, WRef W, int N16, int K32, const SkinnyPlan& p,
+                                            const bf16_t* X, size_t plane, int MT, const Ep& ep, const PfCarry& pc, const FoldIn& fold = FoldIn{}) {
     const dim3 grid((N16 + RT - 1) / RT, (MT + TT - 1) / TT);
     const size_t lds = (p.ksplit > 1 ? (size_t)RT * TT * p.ksplit * 1024 : 0) + (FOLD ? (size_t)TT * 2 * fold.T16 * sizeof(float2) : 0);
     if (FOLD && TT * 2 * fold.T16 > 64 * p.ksplit) return hipErrorInvalidConfiguration;      // TT x 16 rows x T16 / 8 partial groups, one per thread
@@ -1164,30 +1156,29 @@ static inline hipError_t launch_rows_gemm_w(hipStream_t st, WRef W, int N16, int
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    const PfJob pf = g_pf_batched; const int pfs = g_pf_batched_sliced;
-    g_pf_batched = PfJob{nullptr, nullptr, 0u, 0u, 0ull};
+    const PfJob& pf = pc.job;
     const dim3 grid_all(grid.x, grid.y + (pf.n_jobs ? (pf.n_jobs + grid.x - 1) / grid.x : 0));
-    hipLaunchKernelGGL(kern, grid_all, dim3(64 * p.ksplit), lds, st, W.w, X, plane, g_skinny_done, g_skinny_ntiles, N16, K32, p.ksplit, MT, W.scale, ep, fold, pf, pfs TL_PASS);
+    hipLaunchKernelGGL(kern, grid_all, dim3(64 * p.ksplit), lds, lp.st, W.w, X, plane, lp.done, lp.ntiles, N16, K32, p.ksplit, MT, W.scale, ep, fold, pf, pc.sliced TL_PASS(lp));
     return hipGetLastError();
 }
 
 template <int NKR, int RT, class Ep, bool FOLD = false>
-static inline hipError_t launch_rows_gemm(hipStream_t st, WRef W, int N16, int K32, const SkinnyPlan& p,
-                                          const bf16_t* X, size_t plane, int MT, const Ep& ep, const FoldIn& fold = FoldIn{}) {
-    if (W.scale) return launch_rows_gemm_w<NKR, RT, true, Ep, FOLD>(st, W, N16, K32, p, X, plane, MT, ep, fold);
-    return launch_rows_gemm_w<NKR, RT, false, Ep, FOLD>(st, W, N16, K32, p, X, plane, MT, ep, fold);
+static inline hipError_t launch_rows_gemm(const DecLaunch& lp, WRef W, int N16, int K32, const SkinnyPlan& p,
+                                          const bf16_t* X, size_t plane, int MT, const Ep& ep, const PfCarry& pc, const FoldIn& fold = FoldIn{}) {
+    if (W.scale) return launch_rows_gemm_w<NKR, RT, true, Ep, FOLD>(lp, W, N16, K32, p, X, plane, MT, ep, pc, fold);
+    return launch_rows_gemm_w<NKR, RT, false, Ep, FOLD>(lp, W, N16, K32, p, X, plane, MT, ep, pc, fold);
 }
 
 template <int NKR, class Ep, bool FOLD = false>
-static inline hipError_t launch_skinny_mt_nk(hipStream_t st, WRef W, int N16, int K32, const SkinnyPlan& p,
-                                             const bf16_t* X, size_t plane, int MT, const Ep& ep, const FoldIn& fold = FoldIn{}) {
+static inline hipError_t launch_skinny_mt_nk(const DecLaunch& lp, WRef W, int N16, int K32, const SkinnyPlan& p,
+                                             const bf16_t* X, size_t plane, int MT, const Ep& ep, const PfCarry& pc, const FoldIn& fold = FoldIn{}) {
     static const int min_blocks = skinny_env("WM_ROWS_GEMM_MIN_BLOCKS", 400);
     // weight row tiles per wave: as many as still leave >= 400 blocks (~1.5 per CU; swept 100..800 at 8 and 32 streams) (register blocking divides the L2 re-reads
     // of the token operand; with few token tiles the chip has to be filled by features instead).  Same results.
     const int groups = (MT + 1) / 2;
-    if (((N16 + 3) / 4) * groups >= min_blocks) return launch_rows_gemm<NKR, 4, Ep, FOLD>(st, W, N16, K32, p, X, plane, MT, ep, fold);
-    if (((N16 + 1) / 2) * groups >= min_blocks) return launch_rows_gemm<NKR, 2, Ep, FOLD>(st, W, N16, K32, p, X, plane, MT, ep, fold);
-    return launch_rows_gemm<NKR, 1, Ep, FOLD>(st, W, N16, K32, p, X, plane, MT, ep, fold);
+    if (((N16 + 3) / 4) * groups >= min_blocks) return launch_rows_gemm<NKR, 4, Ep, FOLD>(lp, W, N16, K32, p, X, plane, MT, ep, pc, fold);
+    if (((N16 + 1) / 2) * groups >= min_blocks) return launch_rows_gemm<NKR, 2, Ep, FOLD>(lp, W, N16, K32, p, X, plane, MT, ep, pc, fold);
+    return launch_rows_gemm<NKR, 1, Ep, FOLD>(lp, W, N16, K32, p, X, plane, MT, ep, pc, fold);
 }
 
 // ---- LDS-ring token-tile GEMM: tile shape and launch ----
@@ -1212,7 +1203,7 @@ static inline TilePlan tile_plan(int N16, int MT) {
 }
 
 template <int F, int TT, class Ep>
-static inline hipError_t launch_tile_gemm_ft(hipStream_t st, const bf16_t* W, int N16, int K32, int nk, const bf16_t* X, size_t plane, int MT, const Ep& ep) {
+static inline hipError_t launch_tile_gemm_ft(const DecLaunch& lp, const bf16_t* W, int N16, int K32, int nk, const bf16_t* X, size_t plane, int MT, const Ep& ep) {
     typedef TileGemmCfg<F, TT> C;
     const int n_fb = (N16 + 4 * F - 1) / (4 * F), n_tg = (MT + TT - 1) / TT;
     constexpr int lds = C::R * C::STAGE;
@@ -1223,14 +1214,14 @@ static inline hipError_t launch_tile_gemm_ft(hipStream_t st, const bf16_t* W, in
         if (e != hipSuccess) return e;
         attr_done = true;
     }
-    hipLaunchKernelGGL(kern, dim3(n_fb * n_tg), dim3(512), lds, st, W, N16, K32, nk, X, plane, MT, n_fb, n_tg, g_skinny_done, ep, g_skinny_ntiles);
+    hipLaunchKernelGGL(kern, dim3(n_fb * n_tg), dim3(512), lds, lp.st, W, N16, K32, nk, X, plane, MT, n_fb, n_tg, lp.done, ep, lp.ntiles);
     return hipGetLastError();
 }
 
 template <class Ep>
-static inline hipError_t launch_tile_gemm(hipStream_t st, const bf16_t* W, int N16, int K32, int nk, const bf16_t* X, size_t plane, int MT, const Ep& ep) {
+static inline hipError_t launch_tile_gemm(const DecLaunch& lp, const bf16_t* W, int N16, int K32, int nk, const bf16_t* X, size_t plane, int MT, const Ep& ep) {
     const TilePlan t = tile_plan(N16, MT);
-#define WM_TG(Fv, TTv) if constexpr ((8 * Fv + 2 * TTv * WM_ACT_PLANES) % 8 == 0) if (t.F == Fv && t.TT == TTv) return launch_tile_gemm_ft<Fv, TTv>(st, W, N16, K32, nk, X, plane, MT, ep)
+#define WM_TG(Fv, TTv) if constexpr ((8 * Fv + 2 * TTv * WM_ACT_PLANES) % 8 == 0) if (t.F == Fv && t.TT == TTv) return launch_tile_gemm_ft<Fv, TTv>(lp, W, N16, K32, nk, X, plane, MT, ep)
     WM_TG(1, 2); WM_TG(1, 4); WM_TG(1, 6); WM_TG(1, 8);
     WM_TG(2, 2); WM_TG(2, 4); WM_TG(2, 6); WM_TG(2, 8);
 #undef WM_TG
@@ -1248,57 +1239,56 @@ static inline bool use_tile_gemm(int N16, int K32, int MT, bool w8, int nk) {
 }
 
 template <int NK, bool W8, class Ep, bool FOLD = false>
-static inline hipError_t launch_skinny2_nk(hipStream_t st, WRef W, int N16, int K32, const SkinnyPlan& p, const bf16_t* X, size_t plane, int R, const Ep& ep,
-                                           const FoldIn& fold = FoldIn{}) {
+static inline hipError_t launch_skinny2_nk(const DecLaunch& lp, WRef W, int N16, int K32, const SkinnyPlan& p, const bf16_t* X, size_t plane, int R, const Ep& ep,
+                                           const PfCarry& pc, const FoldIn& fold = FoldIn{}) {
     const int grid = (N16 + p.rt - 1) / p.rt, threads = 64 * p.ksplit * p.rt;
     const size_t lds = (p.ksplit > 1 ? (size_t)p.rt * 2 * p.ksplit * 1024 : 0) + (FOLD ? (size_t)4 * fold.T16 * sizeof(float2) : 0);
     if (FOLD && 4 * fold.T16 > threads) return hipErrorInvalidConfiguration;      // 32 rows x T16 / 8 partial groups, one per thread
     const int magic = (256 + p.ksplit - 1) / p.ksplit;
-    PfJob pf = g_pf_batched;
-    g_pf_batched = PfJob{nullptr, nullptr, 0u, 0u, 0ull};
-    if (g_pf_batched_sliced) pf.n_jobs = 0;          // (a job cut for the token-tile consumer: not this kernel's kind)
+    PfJob pf = pc.job;
+    if (pc.sliced) pf.n_jobs = 0;          // (a job cut for the token-tile consumer: not this kernel's kind)
     const int grid_all = pf.n_jobs ? pf_round8(grid) + (int)pf.n_jobs : grid;
-    hipLaunchKernelGGL((k_skinny2_gemm<NK, W8, Ep, FOLD>), dim3(grid_all), dim3(threads), lds, st, W.w, X, plane, g_skinny_done, N16, K32, p.ksplit | (p.rt << 8) | (magic << 16), R,
+    hipLaunchKernelGGL((k_skinny2_gemm<NK, W8, Ep, FOLD>), dim3(grid_all), dim3(threads), lds, lp.st, W.w, X, plane, lp.done, N16, K32, p.ksplit | (p.rt << 8) | (magic << 16), R,
                        W.scale, ep, fold, pf);
     return hipGetLastError();
 }
 template <bool W8, class Ep, bool FOLD = false>
-static inline hipError_t launch_skinny2_w(hipStream_t st, WRef W, int N16, int K32, const SkinnyPlan& p, const bf16_t* X, size_t plane, int R, const Ep& ep,
-                                          const FoldIn& fold = FoldIn{}) {
+static inline hipError_t launch_skinny2_w(const DecLaunch& lp, WRef W, int N16, int K32, const SkinnyPlan& p, const bf16_t* X, size_t plane, int R, const Ep& ep,
+                                          const PfCarry& pc, const FoldIn& fold = FoldIn{}) {
     switch (p.nk) {
-        case 4: return launch_skinny2_nk<4, W8, Ep, FOLD>(st, W, N16, K32, p, X, plane, R, ep, fold);
-        case 8: return launch_skinny2_nk<8, W8, Ep, FOLD>(st, W, N16, K32, p, X, plane, R, ep, fold);
-        case 12: if constexpr (!FOLD) return launch_skinny2_nk<12, W8>(st, W, N16, K32, p, X, plane, R, ep); break;
-        case 16: if constexpr (!FOLD) return launch_skinny2_nk<16, W8>(st, W, N16, K32, p, X, plane, R, ep); break;
+        case 4: return launch_skinny2_nk<4, W8, Ep, FOLD>(lp, W, N16, K32, p, X, plane, R, ep, pc, fold);
+        case 8: return launch_skinny2_nk<8, W8, Ep, FOLD>(lp, W, N16, K32, p, X, plane, R, ep, pc, fold);
+        case 12: if constexpr (!FOLD) return launch_skinny2_nk<12, W8>(lp, W, N16, K32, p, X, plane, R, ep, pc); break;
+        case 16: if constexpr (!FOLD) return launch_skinny2_nk<16, W8>(lp, W, N16, K32, p, X, plane, R, ep, pc); break;
         default: break;
     }
     return hipErrorInvalidConfiguration;
 }
 template <class Ep, bool FOLD = false>
-static inline hipError_t launch_skinny2(hipStream_t st, WRef W, int N16, int K32, const SkinnyPlan& p, const bf16_t* X, size_t plane, int R, const Ep& ep,
-                                        const FoldIn& fold = FoldIn{}) {
-    if (W.scale) return launch_skinny2_w<true, Ep, FOLD>(st, W, N16, K32, p, X, plane, R, ep, fold);
-    return launch_skinny2_w<false, Ep, FOLD>(st, W, N16, K32, p, X, plane, R, ep, fold);
+static inline hipError_t launch_skinny2(const DecLaunch& lp, WRef W, int N16, int K32, const SkinnyPlan& p, const bf16_t* X, size_t plane, int R, const Ep& ep,
+                                        const PfCarry& pc, const FoldIn& fold = FoldIn{}) {
+    if (W.scale) return launch_skinny2_w<true, Ep, FOLD>(lp, W, N16, K32, p, X, plane, R, ep, pc, fold);
+    return launch_skinny2_w<false, Ep, FOLD>(lp, W, N16, K32, p, X, plane, R, ep, pc, fold);
 }
 
 template <class Ep, bool FOLD = false>
-static inline hipError_t launch_skinny_mt(hipStream_t st, WRef W, int N16, int K32, const SkinnyPlan& p,
-                                          const bf16_t* X, size_t plane, int MT, int R, const Ep& ep, const FoldIn& fold = FoldIn{}) {
-    // the LDS-ring tile kernel (same accumulation order, bit-identical results)
+static inline hipError_t launch_skinny_mt(const DecLaunch& lp, WRef W, int N16, int K32, const SkinnyPlan& p,
+                                          const bf16_t* X, size_t plane, int MT, int R, const Ep& ep, const PfCarry& pc, const FoldIn& fold = FoldIn{}) {
+    // the LDS-ring tile kernel (same accumulation order, bit-identical results; it carries no prefetch job: pc is dropped)
     if constexpr (!FOLD) {
         if (use_tile_gemm(N16, K32, MT, W.scale != nullptr, p.nk))
-            return launch_tile_gemm(st, W.w, N16, K32, p.nk, X, plane, MT, ep);
+            return launch_tile_gemm(lp, W.w, N16, K32, p.nk, X, plane, MT, ep);
     }
     // two token tiles: the weight-streaming kernel with a second token tile (WM_SKINNY2=0: the register-blocked kernel)
     const bool s2_dbg = (FOLD ? skinny_env("WM_SKINNY2_FOLD", 1) : 1) && (std::is_same<Ep, EpResidualFold>::value ? skinny_env("WM_SKINNY2_RESFOLD", 1) : 1);
     if (MT == 2 && skinny_env("WM_SKINNY2", 1) && s2_dbg && p.ksplit * p.rt <= 10 && p.ksplit * p.nk == K32)
-        return launch_skinny2<Ep, FOLD>(st, W, N16, K32, p, X, plane, R, ep, fold);
+        return launch_skinny2<Ep, FOLD>(lp, W, N16, K32, p, X, plane, R, ep, pc, fold);
     if constexpr (!FOLD) {
-        if (p.nk == 16) return launch_skinny_mt_nk<16>(st, W, N16, K32, p, X, plane, MT, ep);
-        if (p.nk == 12) return launch_skinny_mt_nk<12>(st, W, N16, K32, p, X, plane, MT, ep);
+        if (p.nk == 16) return launch_skinny_mt_nk<16>(lp, W, N16, K32, p, X, plane, MT, ep, pc);
+        if (p.nk == 12) return launch_skinny_mt_nk<12>(lp, W, N16, K32, p, X, plane, MT, ep, pc);
     }
-    if (p.nk == 8) return launch_skinny_mt_nk<8, Ep, FOLD>(st, W, N16, K32, p, X, plane, MT, ep, fold);
-    if (p.nk == 4) return launch_skinny_mt_nk<4, Ep, FOLD>(st, W, N16, K32, p, X, plane, MT, ep, fold);
+    if (p.nk == 8) return launch_skinny_mt_nk<8, Ep, FOLD>(lp, W, N16, K32, p, X, plane, MT, ep, pc, fold);
+    if (p.nk == 4) return launch_skinny_mt_nk<4, Ep, FOLD>(lp, W, N16, K32, p, X, plane, MT, ep, pc, fold);
     return hipErrorInvalidConfiguration;
 }
 
@@ -1306,28 +1296,30 @@ static inline hipError_t launch_skinny_mt(hipStream_t st, WRef W, int N16, int K
 // fold = the rows' statistics partials + c = W gamma; the epilogue's bias is b' = b + W beta.  The plan is the LayerNorm plan (<= 8 fragments per
 // K-slice: 64 ksplit threads >= 32 d / 128 partial groups, whatever d_model), shared by the 16-row, two-tile and token-tile kernels.
 template <class Ep>
-static inline hipError_t launch_skinny_fold(hipStream_t st, WRef W, int N16, int K32, int R, const bf16_t* X, size_t plane, const FoldIn& fold, const Ep& ep) {
+static inline hipError_t launch_skinny_fold(const DecLaunch& lp, WRef W, int N16, int K32, int R, const bf16_t* X, size_t plane, const FoldIn& fold, const Ep& ep,
+                                            const PfCarry& pc = PfCarry{}) {
     const SkinnyPlan p = skinny_plan(N16, K32, true);
     if (p.nk > 8 || fold.T16 * 16 != K32 * 32) return hipErrorInvalidConfiguration;
-    if (R <= 16) return launch_skinny<LdPacked, Ep, true>(st, W, N16, K32, p, LdPacked{X, K32, plane, R}, ep, fold);
-    return launch_skinny_mt<Ep, true>(st, W, N16, K32, p, X, plane, (R + 15) / 16, R, ep, fold);
+    if (R <= 16) return launch_skinny<LdPacked, Ep, true>(lp, W, N16, K32, p, LdPacked{X, K32, plane, R}, ep, pc.job, fold);
+    return launch_skinny_mt<Ep, true>(lp, W, N16, K32, p, X, plane, (R + 15) / 16, R, ep, pc, fold);
 }
 
 // out = X (R token rows, packed hi/lo planes in global memory) times W^T (N = 16*N16 features, K = 32*K32)
 template <class Ep>
-static inline hipError_t launch_skinny_rows(hipStream_t st, WRef W, int N16, int K32, int R, const bf16_t* X, size_t plane,
-                                            const Ep& ep) {
+static inline hipError_t launch_skinny_rows(const DecLaunch& lp, WRef W, int N16, int K32, int R, const bf16_t* X, size_t plane,
+                                            const Ep& ep, const PfCarry& pc = PfCarry{}) {
     const SkinnyPlan p = skinny_plan(N16, K32, false);
-    if (R <= 16) return launch_skinny(st, W, N16, K32, p, LdPacked{X, K32, plane, R}, ep);
-    return launch_skinny_mt(st, W, N16, K32, p, X, plane, (R + 15) / 16, R, ep);
+    if (R <= 16) return launch_skinny(lp, W, N16, K32, p, LdPacked{X, K32, plane, R}, ep, pc.job);
+    return launch_skinny_mt(lp, W, N16, K32, p, X, plane, (R + 15) / 16, R, ep, pc);
 }
 
 template <class Ld, class Ep>
-static inline hipError_t launch_skinny_norm_t(hipStream_t st, WRef W, int N16, int K32, const Ld& ld, const Ep& ep, bf16_t* xscr, size_t plane) {
+static inline hipError_t launch_skinny_norm_t(const DecLaunch& lp, WRef W, int N16, int K32, const Ld& ld, const Ep& ep, bf16_t* xscr, size_t plane,
+                                              const PfCarry& pc, const void* pf_extra) {
     const SkinnyPlan p = skinny_plan(N16, K32, true);
     const int R = ld.M;
     if (p.nk > 8 || K32 * 32 != ld.d || K32 * 16 > ((p.nk + 3) / 4) * 64 * p.ksplit) return hipErrorInvalidConfiguration;
-    if (R <= 16) return launch_skinny(st, W, N16, K32, p, ld, ep);
+    if (R <= 16) return launch_skinny(lp, W, N16, K32, p, ld, ep, pc.job);
     const int MT = (R + 15) / 16;
     // two token tiles: LayerNorm fused into the two-tile weight-streaming kernel.  OFF by default (WM_SKINNY2_NORM=1 turns it on): measured
     // slower than the LayerNorm launch + unfused kernel (vanilla step at 32 streams 4.02 vs 3.68 ms, tests/microbench/r03_call4.sh) — every
@@ -1338,11 +1330,11 @@ static inline hipError_t launch_skinny_norm_t(hipStream_t st, WRef W, int N16, i
         const size_t lds = (size_t)ld.lds_bytes() + (p.ksplit > 1 ? (size_t)p.rt * 2 * p.ksplit * 1024 : 0);
         const int magic = (256 + p.ksplit - 1) / p.ksplit;
         if (W.scale) {
-            if (p.nk == 8) hipLaunchKernelGGL((k_skinny2_norm<8, true, Ld, Ep>), dim3(grid), dim3(threads), lds, st, W.w, W.scale, N16, K32, p.ksplit, p.rt, magic, g_skinny_done, ld, ep);
-            else hipLaunchKernelGGL((k_skinny2_norm<4, true, Ld, Ep>), dim3(grid), dim3(threads), lds, st, W.w, W.scale, N16, K32, p.ksplit, p.rt, magic, g_skinny_done, ld, ep);
+            if (p.nk == 8) hipLaunchKernelGGL((k_skinny2_norm<8, true, Ld, Ep>), dim3(grid), dim3(threads), lds, lp.st, W.w, W.scale, N16, K32, p.ksplit, p.rt, magic, lp.done, ld, ep);
+            else hipLaunchKernelGGL((k_skinny2_norm<4, true, Ld, Ep>), dim3(grid), dim3(threads), lds, lp.st, W.w, W.scale, N16, K32, p.ksplit, p.rt, magic, lp.done, ld, ep);
         } else {
-            if (p.nk == 8) hipLaunchKernelGGL((k_skinny2_norm<8, false, Ld, Ep>), dim3(grid), dim3(threads), lds, st, W.w, W.scale, N16, K32, p.ksplit, p.rt, magic, g_skinny_done, ld, ep);
-            else hipLaunchKernelGGL((k_skinny2_norm<4, false, Ld, Ep>), dim3(grid), dim3(threads), lds, st, W.w, W.scale, N16, K32, p.ksplit, p.rt, magic, g_skinny_done, ld, ep);
+            if (p.nk == 8) hipLaunchKernelGGL((k_skinny2_norm<8, false, Ld, Ep>), dim3(grid), dim3(threads), lds, lp.st, W.w, W.scale, N16, K32, p.ksplit, p.rt, magic, lp.done, ld, ep);
+            else hipLaunchKernelGGL((k_skinny2_norm<4, false, Ld, Ep>), dim3(grid), dim3(threads), lds, lp.st, W.w, W.scale, N16, K32, p.ksplit, p.rt, magic, lp.done, ld, ep);
         }
         return hipGetLastError();
     }
@@ -1351,8 +1343,7 @@ static inline hipError_t launch_skinny_norm_t(hipStream_t st, WRef W, int N16, i
     PfJob pf{nullptr, nullptr, 0u, 0u, 0ull};
     int grid = MT, pf_sliced = 1;
     const unsigned long long wbytes = (unsigned long long)N16 * K32 * (W.scale ? 512 : 1024);
-    const char* extra = reinterpret_cast<const char*>(g_ln_pf_extra);
-    g_ln_pf_extra = nullptr;
+    const char* extra = reinterpret_cast<const char*>(pf_extra);
     if (ln_pf && MT == 2 && skinny_env("WM_SKINNY2", 1) && p.ksplit * p.rt <= 10) {
         // consumer = k_skinny2_gemm: block j reads the p.rt row tiles j*p.rt.. — one job per consumer block
         const unsigned job_bytes = (unsigned)((unsigned long long)p.rt * K32 * (W.scale ? 512 : 1024));
@@ -1371,22 +1362,24 @@ static inline hipError_t launch_skinny_norm_t(hipStream_t st, WRef W, int N16, i
     if (pf.n_jobs) grid = pf_round8(nmain) + (int)pf.n_jobs;
     const LdArgs la = ld.pack();
     if (!ld.packs() || p.ksplit > 255) return hipErrorInvalidConfiguration;
-    if (p.nk == 8) hipLaunchKernelGGL((k_ln_tiles<8, Ld>), dim3(grid), dim3(64 * p.ksplit), ld.lds_bytes(), st, la.a, la.b, la.c, la.i0, la.i1, K32, p.ksplit | (sub << 8), nmain,
-                                      g_skinny_ntiles, xscr, plane, g_skinny_done, pf, pf_sliced);
-    else if (p.nk == 4) hipLaunchKernelGGL((k_ln_tiles<4, Ld>), dim3(grid), dim3(64 * p.ksplit), ld.lds_bytes(), st, la.a, la.b, la.c, la.i0, la.i1, K32, p.ksplit | (sub << 8), nmain,
-                                           g_skinny_ntiles, xscr, plane, g_skinny_done, pf, pf_sliced);
+    if (p.nk == 8) hipLaunchKernelGGL((k_ln_tiles<8, Ld>), dim3(grid), dim3(64 * p.ksplit), ld.lds_bytes(), lp.st, la.a, la.b, la.c, la.i0, la.i1, K32, p.ksplit | (sub << 8), nmain,
+                                      lp.ntiles, xscr, plane, lp.done, pf, pf_sliced);
+    else if (p.nk == 4) hipLaunchKernelGGL((k_ln_tiles<4, Ld>), dim3(grid), dim3(64 * p.ksplit), ld.lds_bytes(), lp.st, la.a, la.b, la.c, la.i0, la.i1, K32, p.ksplit | (sub << 8), nmain,
+                                           lp.ntiles, xscr, plane, lp.done, pf, pf_sliced);
     else return hipErrorInvalidConfiguration;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    return launch_skinny_mt(st, W, N16, K32, p, xscr, plane, MT, R, ep);
+    return launch_skinny_mt(lp, W, N16, K32, p, xscr, plane, MT, R, ep, pc);
 }
 
 // LayerNorm-fused GEMM over R token rows.  R <= 16: one fused launch.  R > 16: the same LayerNorm code writes
 // the packed hi/lo operand to `xscr` (global), then the register-blocked token-tile kernel runs.
+// pf_extra: a second matrix OF THE SAME SIZE the batched LayerNorm launch (R > 16 rows) should also pull in (LN3 + FC1: the FC2 weights, which
+// no launch in between can carry).
 template <class Ep>
-static inline hipError_t launch_skinny_norm(hipStream_t st, WRef W, int N16, int K32, const float* h, const float* gamma,
+static inline hipError_t launch_skinny_norm(const DecLaunch& lp, WRef W, int N16, int K32, const float* h, const float* gamma,
                                             const float* beta, int d, int R, int row_mul, int row_off, int do_norm, const Ep& ep,
-                                            bf16_t* xscr, size_t plane) {
-    if (do_norm) return launch_skinny_norm_t(st, W, N16, K32, LdNorm{h, gamma, beta, d, K32, R, row_mul, row_off}, ep, xscr, plane);
-    return launch_skinny_norm_t(st, W, N16, K32, LdIdent{h, gamma, beta, d, K32, R, row_mul, row_off}, ep, xscr, plane);
+                                            bf16_t* xscr, size_t plane, const PfCarry& pc = PfCarry{}, const void* pf_extra = nullptr) {
+    if (do_norm) return launch_skinny_norm_t(lp, W, N16, K32, LdNorm{h, gamma, beta, d, K32, R, row_mul, row_off}, ep, xscr, plane, pc, pf_extra);
+    return launch_skinny_norm_t(lp, W, N16, K32, LdIdent{h, gamma, beta, d, K32, R, row_mul, row_off}, ep, xscr, plane, pc, pf_extra);
 }
