@@ -283,6 +283,22 @@ int wm_score_tokens(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_par
                     int B, const int32_t* tokens /* HOST [B][Tmax] */, int Tmax, const int32_t* lens /* HOST [B] */, const int32_t* n_prompt /* HOST [B] */,
                     float* logprobs /* HOST [B][Tmax] */, float* no_speech_prob /* HOST [B] or NULL */, float* ms /* may be NULL */);
 
+/* ---- token alternatives: the best ids of every scored row and the rank of the emitted one (additive to ABI v9; csrc/wm_score.hip) ----
+ * Stands in for what a caller of HF's output_scores does with `scores[i]` (torch.topk of its log_softmax) and for the `top_logprobs` of the
+ * OpenAI-style APIs, without the rows leaving the device: two kernels behind the scoring kernels of wm_score_tokens, on the same processed rows
+ * AFTER the timestamp rules' log-softmax decision (a row the decision forces to a timestamp keeps no text). */
+#define WM_TOPK_MAX 8
+/* wm_score_tokens plus, for every scored position n_prompt <= t < lens: top_ids[b][t][0 .. topk) / top_logprobs[b][t][0 .. topk) = the topk best
+ * tokens of the processed row and their log_softmax values, ordered by value descending, then id ascending; a row that keeps fewer than topk finite
+ * entries ends in (-1, -inf).  An id's entry is bit-equal to logprobs[b][t] where it is the emitted id.  ranks[b][t] = 1 + the number of tokens ahead
+ * of tokens[b][t] in that order, 0 where it is masked.  Unscored positions: -1, -inf, 0.  logprobs / no_speech_prob / *ms and every error as
+ * wm_score_tokens, from the same launches; WM_ERR_ARG (wm_last_error names it) for topk outside [1, WM_TOPK_MAX]. */
+int wm_score_tokens_topk(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* ts /* NULL: rules off */, const wm_score_params* sp /* may be NULL */,
+                         int B, const int32_t* tokens /* HOST [B][Tmax] */, int Tmax, const int32_t* lens /* HOST [B] */, const int32_t* n_prompt /* HOST [B] */,
+                         int topk, float* logprobs /* HOST [B][Tmax] */, float* no_speech_prob /* HOST [B] or NULL */,
+                         int32_t* top_ids /* HOST [B][Tmax][topk] */, float* top_logprobs /* HOST [B][Tmax][topk] */, int32_t* ranks /* HOST [B][Tmax] */,
+                         float* ms /* may be NULL */);
+
 /* ---- parity taps (test-only views of intermediate state; no reference equivalent except
  * forward(), model.py:1223-1347) ---- */
 /* encoder output [B][n_ctx][d_model] as float32 to HOST */
@@ -310,6 +326,11 @@ int wm_select_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_para
  * decode state (begin again afterwards).  Any R >= 1. */
 int wm_score_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* ts, int R, const float* logits, const int32_t* prefixes,
                   int Tmax, const int32_t* lens, const int32_t* targets, float* out_logprob);
+/* Alternatives parity tap, the counterpart of wm_score_rows with the same rows, prefixes, lengths, targets, checks and error codes: row r through the
+ * scoring kernels and the two top-k kernels.  Outputs (HOST): top_ids / top_logprobs [R][topk] and ranks [R] as wm_score_tokens_topk defines them.
+ * WM_ERR_ARG (wm_last_error names it) for topk outside [1, WM_TOPK_MAX].  Overwrites the processors' tables of the decode state.  Any R >= 1. */
+int wm_topk_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* ts, int R, const float* logits, const int32_t* prefixes,
+                 int Tmax, const int32_t* lens, const int32_t* targets, int topk, int32_t* top_ids, float* top_logprobs, int32_t* ranks);
 /* Alignment parity taps: views of the last wm_token_timestamps call.  WM_ERR_STATE for a stream whose workspace group is no longer
  * resident (only the last group is) or that had fewer than 2 rows.  Probabilities of alignment head a (the softmax of HF WhisperAttention's
  * cross branch, modeling_whisper.py, before any crop): HOST float32 [N][n_ctx]. */

@@ -509,13 +509,18 @@ class WhisperMedusaModel:
                  attention_mask: Optional[torch.Tensor] = None, time_precision: float = 0.02,
                  time_precision_features: float = 0.01, return_token_timestamps: Optional[bool] = None,
                  return_segments: bool = False, return_dict_in_generate: Optional[bool] = None,
-                 force_unique_generate_call: Optional[bool] = None, return_token_logprobs: Optional[bool] = None, **kwargs):
+                 force_unique_generate_call: Optional[bool] = None, return_token_logprobs: Optional[bool] = None,
+                 top_logprobs: Optional[int] = None, **kwargs):
         """Same signature as the reference (model.py:1419-1449).  Returns ``LongTensor [B, T]`` holding the
         prompt + generated ids, right-padded with ``pad_token_id`` (model.py:1747-1762).
 
         ``return_token_logprobs=True`` returns a GenerateEncoderDecoderOutput with ``token_logprobs [B, T]``, ``avg_logprob``,
         ``compression_ratio`` and ``no_speech_prob``; ``no_speech_threshold`` / ``logprob_threshold`` / ``compression_ratio_threshold`` run the
         same scoring pass and gate on it (``skipped``, ``needs_fallback`` in the dict outputs and in ``self.last_scores``).
+
+        ``top_logprobs=k`` (1..8) implies that pass and the dict output and adds the k best tokens of every scored row:
+        ``top_token_ids [B, T, k]``, ``top_token_logprobs [B, T, k]`` (value descending, then id ascending) and ``token_ranks [B, T]``, the
+        rank of the emitted id in its row (0: masked); -1 / -inf / 0 where nothing is scored.
 
         ``sequential_longform=True`` with ``return_timestamps=True``: ``input_features [B, n_mels, T]`` of any length — per-clip
         lengths from ``attention_mask [B, T]`` or ``num_frames=`` — are transcribed by Whisper's sequential long-form loop."""
@@ -559,6 +564,12 @@ class WhisperMedusaModel:
                               UserWarning, stacklevel=2)
         if kwargs.get("do_sample"):
             raise NotImplementedError("sampling (do_sample=True) is not supported with medusa")      # model.py:1128-1156: no Medusa branch
+        if top_logprobs is not None:
+            if isinstance(top_logprobs, bool) or not isinstance(top_logprobs, (int, np.integer)) or not 1 <= int(top_logprobs) <= _scores.TOPK_MAX:
+                raise ValueError(f"`top_logprobs` has to be an integer in 1..{_scores.TOPK_MAX}, but is {top_logprobs!r}")
+            if kwargs.get("sequential_longform") or kwargs.get("chunk_longform"):
+                raise NotImplementedError("top_logprobs is not supported with chunk_longform / sequential_longform (short-form only)")
+            top_logprobs = int(top_logprobs)
         if kwargs.get("sequential_longform"):
             self._check_sequential(return_timestamps, condition_on_prev_tokens, temperature, return_token_timestamps, logits_processor,
                                    stopping_criteria, kwargs.get("streamer"), prompt_ids, prompt_condition_type)
@@ -593,7 +604,8 @@ class WhisperMedusaModel:
         # model.py:1201-1205 raises for no_speech_threshold and ignores the other two; the engine scores the final ids in a teacher-forced
         # replay whenever one of these arguments is given — none of them: no new launch
         sc_req = None
-        if return_token_logprobs or no_speech_threshold is not None or logprob_threshold is not None or compression_ratio_threshold is not None:
+        if return_token_logprobs or top_logprobs is not None or no_speech_threshold is not None or logprob_threshold is not None \
+                or compression_ratio_threshold is not None:
             if no_speech_threshold is not None and self.config.no_speech_token_id is None:
                 raise NotImplementedError("no_speech_threshold needs a <|nospeech|> token (no_timestamps_token_id - 1) inside the vocabulary")
             if no_speech_threshold is not None and self._engine is None:
@@ -601,9 +613,10 @@ class WhisperMedusaModel:
                 raise NotImplementedError("no_speech_detection is not supported with medusa without the HIP engine's scoring pass: "
                                           "call model.to('cuda') first (no_speech_threshold)")
             if logits_processor and any(type(p_).__name__ not in _LOWERABLE_PROCESSORS for p_ in logits_processor):
-                raise NotImplementedError("token log-probabilities / quality gating are not supported on the host processor path (logits_processor=)")
-            sc_req = dict(want=bool(return_token_logprobs), no_speech_threshold=no_speech_threshold, logprob_threshold=logprob_threshold,
-                          compression_ratio_threshold=compression_ratio_threshold)
+                raise NotImplementedError(("top_logprobs / " if top_logprobs is not None else "") +
+                                          "token log-probabilities / quality gating are not supported on the host processor path (logits_processor=)")
+            sc_req = dict(want=bool(return_token_logprobs) or top_logprobs is not None, no_speech_threshold=no_speech_threshold,
+                          logprob_threshold=logprob_threshold, compression_ratio_threshold=compression_ratio_threshold, top_k=top_logprobs)
         sc_side = kwargs.pop("_sc_req", None)       # called by the language / long-form wrappers: plain tensor back, scores in self._last_sc
         if sc_side is not None:
             sc_req = sc_side
@@ -695,7 +708,8 @@ class WhisperMedusaModel:
             if tt_req is not None:
                 raise NotImplementedError("return_token_timestamps is not supported on the host processor path (logits_processor=)")
             if sc_req is not None:
-                raise NotImplementedError("token log-probabilities / quality gating are not supported on the host processor path (logits_processor=)")
+                raise NotImplementedError(("top_logprobs / " if sc_req.get("top_k") else "") +
+                                          "token log-probabilities / quality gating are not supported on the host processor path (logits_processor=)")
             seqs = self._decode_host_processors(feats, gp, streamer, host_crit)
             return self._outputs(seqs, gp, return_dict_in_generate, return_segments)
         # language detection just encoded exactly these clips on this engine (one language group, same order): its encoder output and
@@ -763,7 +777,12 @@ class WhisperMedusaModel:
         P = len(gp.prompt)
         ns_id = cfg.no_speech_token_id
         # <|startoftranscript|> sits behind the prompt_ids: index len(prompt_ids) (HF's WhisperNoSpeechDetection reads index 0 there)
-        lp, nsp, ms = eng.score_tokens(own, P, gp, ns_id, P - gp.begin_index if gp.begin_suppress_index is not None else 0)
+        sot = P - gp.begin_index if gp.begin_suppress_index is not None else 0
+        k = req.get("top_k")
+        if k:       # token alternatives: the same launches plus the top-k kernels; never without the argument
+            lp, nsp, tid, tlp, rk, ms = eng.score_tokens_topk(own, P, gp, k, ns_id, sot)
+        else:
+            lp, nsp, ms = eng.score_tokens(own, P, gp, ns_id, sot)
         infos, out = [], []
         for b, s in enumerate(own):
             row = lp[b, : len(s)].copy()
@@ -775,6 +794,13 @@ class WhisperMedusaModel:
                 s = list(gp.prompt) + [gp.eos_token_id]
                 row = np.zeros(len(s), dtype=np.float32)
             infos.append(dict(token_logprobs=row, avg_logprob=avg, compression_ratio=cr, no_speech_prob=ns, skipped=skip, needs_fallback=fb))
+            if k:
+                n = len(s)
+                if skip:    # a gated stream is prompt + EOS: nothing of it was scored
+                    alt = _scores.topk_fills(n, k)
+                else:
+                    alt = (np.array(tid[b, :n], dtype=np.int64), np.array(tlp[b, :n], dtype=np.float32), np.array(rk[b, :n], dtype=np.int64))
+                infos[-1].update(top_token_ids=alt[0], top_token_logprobs=alt[1], token_ranks=alt[2])
             out.append(s if skip else seqs[b])
         return out, infos, ms
 
@@ -790,6 +816,8 @@ class WhisperMedusaModel:
                   compression_ratio=torch.tensor([f["compression_ratio"] for f in infos], dtype=torch.float32, device=self.device),
                   # the streams' own ends (EOS included): with pad == eos a padded row alone cannot tell a stream's EOS from its padding
                   lengths=torch.tensor([len(self._own_end(s, gp)) for s in seqs], dtype=torch.long, device=self.device))
+        if req.get("top_k"):
+            sc.update(self._topk_stack([{k_: torch.from_numpy(np.asarray(f[k_])) for k_ in _scores.TOPK_FIELDS} for f in infos], T))
         if all(f["no_speech_prob"] is not None for f in infos):
             sc["no_speech_prob"] = torch.tensor([f["no_speech_prob"] for f in infos], dtype=torch.float32, device=self.device)
         if req["no_speech_threshold"] is not None:
@@ -798,6 +826,19 @@ class WhisperMedusaModel:
             sc["needs_fallback"] = torch.tensor([f["needs_fallback"] for f in infos], dtype=torch.bool, device=self.device)
         sc["_want"] = req["want"]
         return sc
+
+    def _topk_stack(self, rows, T: int) -> dict:
+        """Per-stream alternative fields (``top_token_ids [n, k]``, ``top_token_logprobs [n, k]``, ``token_ranks [n]``) -> tensors over T positions,
+        -1 / -inf / 0 behind every stream's end."""
+        k = int(rows[0]["top_token_ids"].shape[-1])
+        ids, lps, rks = _scores.topk_fills(T, k)
+        out = dict(top_token_ids=torch.from_numpy(ids).repeat(len(rows), 1, 1), top_token_logprobs=torch.from_numpy(lps).repeat(len(rows), 1, 1),
+                   token_ranks=torch.from_numpy(rks).repeat(len(rows), 1))
+        for i, f in enumerate(rows):
+            for name in _scores.TOPK_FIELDS:
+                v = f[name].cpu()
+                out[name][i, : v.shape[0]] = v.to(out[name].dtype)
+        return {name: v.to(self.device) for name, v in out.items()}
 
     # ---- token-level timestamps (HF _extract_token_timestamps; engine: csrc/wm_align.hip) ----------------------------------------------
     def _token_ts_request(self, alignment_heads, generation_config, num_frames, logits_processor, time_precision) -> dict:
@@ -978,6 +1019,9 @@ class WhisperMedusaModel:
                     for sg in out["segments"][i]:
                         n = int(sg["tokens"].numel())
                         sg["token_logprobs"] = fields["token_logprobs"][i, o: o + n]
+                        for name in _scores.TOPK_FIELDS:
+                            if name in fields:
+                                sg[name] = fields[name][i, o: o + n]
                         o += n
             out.update(fields)
             return out
@@ -1107,6 +1151,9 @@ class WhisperMedusaModel:
                     sc[k] = torch.zeros(len(rows), T, dtype=torch.float32, device=self.device)
                     for i, f in enumerate(scs):
                         sc[k][i, : f[k].numel()] = f[k]
+                elif k in _scores.TOPK_FIELDS:      # [T_group(, k)] per clip: -1 / -inf / 0 behind the group's own length
+                    if k == _scores.TOPK_FIELDS[0]:
+                        sc.update(self._topk_stack(scs, T))
                 else:
                     sc[k] = torch.stack([f[k] for f in scs])
             self.last_stats["ms_token_logprobs"] = ms_sc
@@ -1439,7 +1486,8 @@ class WhisperMedusaModel:
         local, local_sc = [], []
         gc = kw.get("generation_config")        # (the thresholds may come through a passed generation_config, as in generate())
         scoring = any(kw.get(k) is not None or getattr(gc, k, None) is not None
-                      for k in ("no_speech_threshold", "logprob_threshold", "compression_ratio_threshold")) or bool(kw.get("return_token_logprobs"))
+                      for k in ("no_speech_threshold", "logprob_threshold", "compression_ratio_threshold")) \
+            or bool(kw.get("return_token_logprobs")) or kw.get("top_logprobs") is not None
         if mine:
             out = self.generate(input_features[mine], **kw)
             rows = out["sequences"] if isinstance(out, dict) else out
@@ -1461,10 +1509,13 @@ class WhisperMedusaModel:
                 fields[k] = torch.zeros(B, T, dtype=torch.float32, device=self.device)
                 for i, f in enumerate(infos):
                     fields[k][i, : len(f[k])] = torch.tensor(f[k], dtype=torch.float32)
+            elif k in _scores.TOPK_FIELDS:
+                if k == _scores.TOPK_FIELDS[0]:
+                    fields.update(self._topk_stack([{n_: torch.tensor(f[n_]) for n_ in _scores.TOPK_FIELDS} for f in infos], T))
             else:
                 fields[k] = torch.tensor([f[k] for f in infos], device=self.device)
         self.last_scores = fields
-        if kw.get("return_token_logprobs") or kw.get("return_dict_in_generate") or getattr(gc, "return_dict_in_generate", None):
+        if kw.get("return_token_logprobs") or kw.get("top_logprobs") is not None or kw.get("return_dict_in_generate") or getattr(gc, "return_dict_in_generate", None):
             return GenerateEncoderDecoderOutput(t, **fields)
         return t
 

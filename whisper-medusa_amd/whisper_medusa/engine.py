@@ -73,7 +73,7 @@ EXPORTS = ["wm_create", "wm_destroy", "wm_last_error", "wm_abi_version", "wm_bui
            "wm_get_encoder_output", "wm_forward_logits", "wm_get_cross_kv", "wm_profile_kernel",
            "wm_decode_begin_ts", "wm_select_rows",
            "wm_token_timestamps", "wm_get_align_probs", "wm_get_align_matrix", "wm_dtw",
-           "wm_score_tokens", "wm_score_rows", "wm_set_repeat_rules",
+           "wm_score_tokens", "wm_score_rows", "wm_set_repeat_rules", "wm_score_tokens_topk", "wm_topk_rows",
            "wm_logmel_long", "wm_gather_windows"]
 
 _lib = {}
@@ -136,6 +136,9 @@ def load_library(path: Optional[str] = None, act_fp16: bool = False) -> C.CDLL:
     lib.wm_score_tokens.argtypes = [vp, C.POINTER(WmGenParams), C.POINTER(WmTimestampParams), C.POINTER(WmScoreParams), i32, i32p, i32, i32p, i32p,
                                     f32p, f32p, f32p]
     lib.wm_score_rows.argtypes = [vp, C.POINTER(WmGenParams), C.POINTER(WmTimestampParams), i32, f32p, i32p, i32, i32p, i32p, f32p]
+    lib.wm_score_tokens_topk.argtypes = [vp, C.POINTER(WmGenParams), C.POINTER(WmTimestampParams), C.POINTER(WmScoreParams), i32, i32p, i32, i32p, i32p,
+                                         i32, f32p, f32p, i32p, f32p, i32p, f32p]
+    lib.wm_topk_rows.argtypes = [vp, C.POINTER(WmGenParams), C.POINTER(WmTimestampParams), i32, f32p, i32p, i32, i32p, i32p, i32, i32p, f32p, i32p]
     for name in EXPORTS:
         if name not in ("wm_destroy", "wm_last_error", "wm_resample_len"):      # wm_resample_len returns int64 (set above)
             getattr(lib, name).restype = i32
@@ -475,6 +478,58 @@ class Engine:
                                            pre.ctypes.data_as(i32p), Tmax, lens.ctypes.data_as(i32p), tgt.ctypes.data_as(i32p),
                                            out.ctypes.data_as(f32p)), "wm_score_rows")
         return out
+
+    # ---- token alternatives (include/wm.h wm_score_tokens_topk) -------------------------
+    def score_tokens_topk(self, seqs: Sequence[Sequence[int]], n_prompt, gp: GenParams, top_k: int, no_speech_token_id: Optional[int] = None,
+                          sot_index: int = 0):
+        """``score_tokens`` plus the ``top_k`` (1..8) best tokens of every scored row — value descending, then id ascending — and the rank of the
+        emitted id in that order (0: masked).  Returns (log-probabilities, no-speech probabilities or None — both as ``score_tokens`` —,
+        numpy int32 [B, max len, top_k] ids, float32 [B, max len, top_k] log-probabilities, int32 [B, max len] ranks, ms); -1 / -inf / 0 inside
+        the prompt and after a stream's end.  Overwrites the decode state."""
+        B = len(seqs)
+        tok, lens, Tmax, npr = self._pack_ids(seqs, n_prompt)
+        k = int(top_k)
+        out = np.zeros((B, Tmax), dtype=np.float32)
+        tid = np.full((B, Tmax, max(k, 1)), -1, dtype=np.int32)
+        tlp = np.full((B, Tmax, max(k, 1)), -np.inf, dtype=np.float32)
+        rk = np.zeros((B, Tmax), dtype=np.int32)
+        want_ns = no_speech_token_id is not None and int(no_speech_token_id) >= 0
+        nsp = np.zeros(B, dtype=np.float32)
+        ms = C.c_float(0)
+        g, _keep = self._gen_struct(gp)
+        ts = self._ts_struct(gp) if gp.timestamps else None
+        sp = WmScoreParams(int(no_speech_token_id) if want_ns else -1, int(sot_index))
+        self._set_repeat_rules(gp)
+        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        self._kv_stamp = object()
+        self._check(self.lib.wm_score_tokens_topk(self.h, C.byref(g), C.byref(ts) if ts is not None else None, C.byref(sp), B, tok.ctypes.data_as(i32p),
+                                                  Tmax, lens.ctypes.data_as(i32p), npr.ctypes.data_as(i32p), k, out.ctypes.data_as(f32p),
+                                                  nsp.ctypes.data_as(f32p) if want_ns else None, tid.ctypes.data_as(i32p), tlp.ctypes.data_as(f32p),
+                                                  rk.ctypes.data_as(i32p), C.byref(ms)), "wm_score_tokens_topk")
+        return out, (nsp if want_ns else None), tid, tlp, rk, ms.value
+
+    def topk_rows(self, gp: GenParams, logits: np.ndarray, prefixes: Sequence[Sequence[int]], targets: Sequence[int], top_k: int):
+        """Alternatives parity tap (wm_topk_rows): the rows of ``score_rows`` through the scoring and the top-k kernels.  Returns numpy
+        (int32 [R, top_k] ids, float32 [R, top_k] log-probabilities, int32 [R] ranks)."""
+        x = np.ascontiguousarray(logits, dtype=np.float32)
+        R, V = x.shape
+        if V != self.cfg.vocab_size or len(prefixes) != R or len(targets) != R:
+            raise ValueError("topk_rows: logits must be [R, vocab] with one prefix and one target per row")
+        pre, lens, Tmax, _ = self._pack_ids(prefixes)
+        tgt = np.ascontiguousarray(targets, dtype=np.int32)
+        k = int(top_k)
+        tid = np.full((R, max(k, 1)), -1, dtype=np.int32)
+        tlp = np.full((R, max(k, 1)), -np.inf, dtype=np.float32)
+        rk = np.zeros(R, dtype=np.int32)
+        g, _keep = self._gen_struct(gp)
+        self._set_repeat_rules(gp)
+        ts = self._ts_struct(gp) if gp.timestamps else None
+        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        self._kv_stamp = object()
+        self._check(self.lib.wm_topk_rows(self.h, C.byref(g), C.byref(ts) if ts is not None else None, R, x.ctypes.data_as(f32p),
+                                          pre.ctypes.data_as(i32p), Tmax, lens.ctypes.data_as(i32p), tgt.ctypes.data_as(i32p), k,
+                                          tid.ctypes.data_as(i32p), tlp.ctypes.data_as(f32p), rk.ctypes.data_as(i32p)), "wm_topk_rows")
+        return tid, tlp, rk
 
     def tokens(self, stream: int) -> List[int]:
         cap = self.cfg.max_target_positions + 16

@@ -19,6 +19,15 @@ from typing import Optional, Sequence
 import numpy as np
 
 
+TOPK_MAX = 8            # include/wm.h WM_TOPK_MAX: alternatives per scored row (generate(top_logprobs=k))
+TOPK_FIELDS = ("top_token_ids", "top_token_logprobs", "token_ranks")
+
+
+def topk_fills(n: int, k: int):
+    """The alternative fields of ``n`` positions nothing was scored at: ids -1 [n, k], log-probabilities -inf [n, k], ranks 0 [n]."""
+    return np.full((n, k), -1, dtype=np.int64), np.full((n, k), -np.inf, dtype=np.float32), np.zeros(n, dtype=np.int64)
+
+
 def avg_logprob(token_logprobs: Sequence[float], n_prompt: int, length: int) -> float:
     """Mean of ``token_logprobs[n_prompt:length]`` (``length`` = the stream's own end, EOS included); 0.0 for an empty range.  The sum runs
     in the order and the precision HF's Python ``sum`` over float32 tensors takes, so the figure is HF's bit for bit."""
