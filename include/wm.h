@@ -219,6 +219,27 @@ typedef struct wm_timestamp_params {
 typedef struct wm_repeat_params { float repetition_penalty; int32_t no_repeat_ngram_size; } wm_repeat_params;
 int wm_set_repeat_rules(wm_ctx* ctx, const wm_repeat_params* rp /* NULL = off */);
 
+/* Seeded sampling on the plain decode path (additive to ABI v9; csrc/wm_sample.hip).  Stands in for HF generate(do_sample=True,
+ * temperature=T) as WhisperGenerationMixin.generate_with_fallback uses it for its retries (the reference copies that loop, model.py:1842-2013, and
+ * has no Medusa-with-sampling branch either): the processors run, then the temperature warper, then a draw from the softmax.  The engine draws by
+ * Gumbel-max over counter-based noise.  A token at sequence position t (the index it takes in ids; t = L[s] when it is chosen):
+ *   1. the processed row v: the repetition rules, then the processors of wm_gen_params, then the timestamp masks, each under the row's own prefix;
+ *   2. timestamp rules on: the log-softmax decision on v at temperature 1, BEFORE the temperature (HF: processors, then warpers): text is masked
+ *      when logsumexp(v[tb:]) > max(v[:tb]);
+ *   3. token = argmax_n (v_n * (1/T) + g_n) over what step 2 leaves (one fp32 fused multiply-add per token, 1/T rounded to fp32); ties: the lower id;
+ *   4. g_n = -logf(-logf(u_n)), u_n = (2 * (x_n >> 9) + 1) * 2^-24: every u is exact in fp32 and lies in [2^-24, 1 - 2^-24], so g is finite
+ *      (-2.81 .. 16.64); logf is the correctly-specified library function, not the fast intrinsic.
+ * x_n = word (n & 3) of Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85) with key (seed_lo, seed_hi)
+ * and counter (n >> 2, t, key_lo, key_hi), `key` the 64-bit stream key the caller gives each stream.  A token's noise therefore depends on
+ * (seed, stream key, position, token id) alone: not on the batch slot, the batch size, the slicing of the vocabulary or graph replay.
+ * This samples softmax(v / T) over the WHOLE distribution — openai-whisper's Categorical(logits / T); HF's default top_k = 50 warper is not applied
+ * (the deviation; an explicit top_k / top_p is refused by the Python layer).
+ * Sticky on the context until cleared (NULL); read by wm_decode_begin / wm_decode_begin_ts, which then return WM_ERR_ARG (wm_last_error says why)
+ * when n_keys != B, when wm_gen_params.vanilla == 0 (sampling runs on the plain decode path only) or on a candidate-tree context.  wm_set_sampling
+ * itself: WM_ERR_ARG for a temperature that is not finite or <= 0, n_keys < 0.  wm_gen_params.temperature keeps its meaning (typical acceptance). */
+typedef struct wm_sample_params { float temperature; uint64_t seed; const uint64_t* stream_keys /* HOST [n_keys]; NULL: 0..B-1 */; int32_t n_keys; } wm_sample_params;
+int wm_set_sampling(wm_ctx* ctx, const wm_sample_params* sp /* NULL = off */);
+
 /* ---- F3..F14 the Medusa decode loop (replaces _medusa_greedy_search, model.py:404-835) ---- */
 int wm_decode_begin(wm_ctx* ctx, const wm_gen_params* gp, int B);
 /* wm_decode_begin with the timestamp rules on (ts != NULL; NULL = wm_decode_begin).  WM_ERR_ARG (wm_last_error says why): a candidate tree
@@ -319,6 +340,15 @@ int wm_forward_logits(wm_ctx* ctx, int B, const int32_t* tokens /* HOST [B][T] *
 int wm_select_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* ts, int R, const float* logits, const int32_t* prefixes,
                    int Tmax, const int32_t* lens, const int32_t* probe_tokens, int32_t* out_argmax, float* out_p_probe, float* out_entropy,
                    int32_t* out_ts_forced);
+/* Sampling parity tap, the counterpart of wm_select_rows with the same row chunking: R caller-given logits rows (HOST float32 [R][vocab]) through
+ * k_sample1 / k_sample_fin, row r under prefix prefixes[r][0 .. lens[r]) (HOST int32 [R][Tmax]) at position lens[r] — its own length for the
+ * processors of gp, exponential decay included — with stream key keys[r] (HOST [R]); ts NULL: timestamp rules off (the repetition rules of the
+ * context apply either way).  sp: temperature and seed (stream_keys / n_keys are not read).  Outputs (HOST, [R] each): the drawn token, the winner's
+ * perturbed value v / T + g, and 1 where the log-softmax decision masked all text.  WM_ERR_ARG for lens outside [1, min(Tmax, n_tgt)] or a bad
+ * temperature.  Overwrites the processors' tables and the stream keys of the decode state (begin again afterwards).  Any R >= 1. */
+int wm_sample_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* ts /* may be NULL */, const wm_sample_params* sp, int R,
+                   const float* logits, const int32_t* prefixes, int Tmax, const int32_t* lens, const uint64_t* keys /* HOST [R] */,
+                   int32_t* out_token, float* out_value /* winner's perturbed value */, int32_t* out_forced);
 /* Scoring parity tap, the counterpart of wm_select_rows: R caller-given logits rows (HOST float32 [R][vocab]) through the scoring kernels of
  * wm_score_tokens only, row r under prefix prefixes[r][0 .. lens[r]) (HOST int32 [R][Tmax]) with cur_len = lens[r] — its own length, exponential
  * decay included — and target targets[r]; ts NULL: rules off.  out_logprob HOST [R]: what HF's log_softmax(processors(row))[target] gives, -inf for

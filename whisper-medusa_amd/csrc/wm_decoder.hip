@@ -1879,6 +1879,13 @@ int wm_dec_iteration(wm_ctx* ctx, int Mper_base)
             const int nb = min(chunk, B - b0);
             int rc = wm_dec_pass(ctx, b0, nb, Mper_base, 0, 0, 0);
             if (rc) return rc;
+            if (ctx->samp.on) {     // seeded sampling (wm_set_sampling): the token of row b0 + row is drawn at position L, not the arg-max
+                TsDev tsb = ts; tsb.st += b0; tsb.rp_ids += (size_t)b0 * ts.rp_stride;
+                SampDev sd = ctx->samp; sd.keys += b0;
+                rc = wm_sample_launch(ctx, gp, tsb, sd, ctx->L + b0, nb, b0, 0);
+                if (rc) return rc;
+                continue;
+            }
             if (wm_rules_on(ts)) {  // (committed-state records: ts.st of stream b0 + row; prefix ids of stream b0 + row)
                 TsDev tsb = ts; tsb.st += b0; tsb.rp_ids += (size_t)b0 * ts.rp_stride;
                 k_select1_ts<false><<<dim3(SEL_SP, nb), dim3(256), lds, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L + b0, 1,

@@ -37,7 +37,7 @@ extern "C" void wm_destroy(wm_ctx* ctx)
                     ctx->finished, ctx->cand, ctx->niter, ctx->hist, ctx->supmask, ctx->exppen, ctx->tap_tok, ctx->done,
                     ctx->hf_keep, ctx->hb_keep, ctx->carry, ctx->rowinfo, ctx->sinfo, ctx->steprows, ctx->rs_table, ctx->tree, ctx->sibtree, ctx->sibpart, ctx->sel_src, ctx->sel_n, ctx->sel_base, ctx->exn8, ctx->exs,
                     ctx->xn, ctx->lnstats, ctx->foldv, ctx->kx8, ctx->vx8, ctx->kxs, ctx->vxs,
-                    ctx->ts.st, ctx->ts.ver, ctx->ts.part1t, ctx->ts.forced};
+                    ctx->ts.st, ctx->ts.ver, ctx->ts.part1t, ctx->ts.forced, ctx->samp.part, ctx->samp.val, ctx->samp_keys};
     for (void* b : bufs) if (b) hipFree(b);
     wm_align_free(ctx);
     wm_score_free(ctx);
@@ -250,6 +250,10 @@ extern "C" int wm_create(const wm_config* cfg, const wm_weights* w, int device, 
     CREATE_HIP(dev_alloc(&ctx->ts.ver, std::max<size_t>(B, RW) * WM_CAND_STRIDE, st));
     CREATE_HIP(dev_alloc(&ctx->ts.part1t, RW * 16 * 4, st));
     CREATE_HIP(dev_alloc(&ctx->ts.forced, RW + B, st));
+    // seeded sampling (wm_set_sampling): slice partials, the winners' perturbed values, the rows' stream keys
+    CREATE_HIP(dev_alloc(&ctx->samp.part, RW * 16 * 8, st));
+    CREATE_HIP(dev_alloc(&ctx->samp.val, RW + B, st));
+    CREATE_HIP(dev_alloc(&ctx->samp_keys, std::max<size_t>(B, 16), st));
     const size_t Tids = ctx->Tal;
     CREATE_HIP(dev_alloc(&ctx->ids, B * Tids, st));
     CREATE_HIP(dev_alloc(&ctx->L, B, st));
@@ -380,6 +384,33 @@ extern "C" int wm_set_repeat_rules(wm_ctx* ctx, const wm_repeat_params* rp)
     return WM_OK;
 }
 
+// Seeded sampling on the plain decode path (include/wm.h): kept on the context, read by wm_decode_begin / wm_decode_begin_ts
+static int wm_sampling_check(wm_ctx* ctx, const char* who, const wm_sample_params* sp)
+{
+    if (!(sp->temperature > 0.f) || !std::isfinite(sp->temperature)) {
+        ctx->err = std::string(who) + ": the sampling temperature must be a finite number > 0"; return WM_ERR_ARG; }
+    if (sp->n_keys < 0) { ctx->err = std::string(who) + ": n_keys must not be negative"; return WM_ERR_ARG; }
+    return WM_OK;
+}
+extern "C" int wm_set_sampling(wm_ctx* ctx, const wm_sample_params* sp)
+{
+    if (!ctx) return WM_ERR_ARG;
+    if (!sp) { ctx->samp_set_on = false; ctx->samp_set_keys.clear(); return WM_OK; }
+    if (int rc = wm_sampling_check(ctx, "wm_set_sampling", sp)) return rc;
+    ctx->samp_set_on = true; ctx->samp_set_temp = sp->temperature; ctx->samp_set_seed = sp->seed;
+    ctx->samp_set_keys.clear();
+    if (sp->stream_keys) ctx->samp_set_keys.assign(sp->stream_keys, sp->stream_keys + sp->n_keys);
+    else for (int i = 0; i < sp->n_keys; ++i) ctx->samp_set_keys.push_back((uint64_t)i);       // NULL: 0 .. n_keys - 1 (n_keys is still checked against B)
+    return WM_OK;
+}
+// the device form of a sampling request: fl(1 / T), the seed's two words, the context's buffers
+static SampDev wm_sampling_dev(wm_ctx* ctx, float temperature, uint64_t seed)
+{
+    SampDev d = ctx->samp;
+    d.on = 1; d.inv_t = 1.0f / temperature; d.seed_lo = (unsigned)seed; d.seed_hi = (unsigned)(seed >> 32); d.keys = ctx->samp_keys;
+    return d;
+}
+
 extern "C" int wm_decode_begin(wm_ctx* ctx, const wm_gen_params* gp, int B) { return wm_decode_begin_ts(ctx, gp, nullptr, B); }
 
 extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* tsp, int B)
@@ -394,6 +425,14 @@ extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm
     if (!gp->vanilla && gp->accept_mode == WM_ACCEPT_TYPICAL && !(gp->temperature > 0.f)) {
         ctx->err = "wm_decode_begin: typical acceptance needs temperature > 0"; return WM_ERR_ARG; }
     hipStream_t st = ctx->stream;
+    SampDev sd = ctx->samp; sd.on = 0;
+    if (ctx->samp_set_on) {
+        if (!gp->vanilla) { ctx->err = "wm_decode_begin: sampling runs on the plain decode path only (wm_gen_params.vanilla = 1)"; return WM_ERR_ARG; }
+        if (ctx->tn) { ctx->err = "wm_decode_begin: sampling is not supported with a candidate tree (medusa_choices with top-k > 1)"; return WM_ERR_ARG; }
+        if ((int)ctx->samp_set_keys.size() != B) { ctx->err = "wm_decode_begin: wm_sample_params.n_keys must equal B"; return WM_ERR_ARG; }
+        sd = wm_sampling_dev(ctx, ctx->samp_set_temp, ctx->samp_set_seed);
+        WM_HIP(hipMemcpyAsync(ctx->samp_keys, ctx->samp_set_keys.data(), B * sizeof(uint64_t), hipMemcpyHostToDevice, st));    // (awaited below: wm_proc_setup ends idle)
+    }
     GenDev g{}; TsDev ts{};
     if (int rc = wm_proc_setup(ctx, "wm_decode_begin", gp, tsp, &g, &ts)) return rc;
     g.max_length = std::min(gp->max_length, ctx->Tmax);
@@ -411,10 +450,12 @@ extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm
     g.sib = (ctx->host_carry && ctx->tn == 0 && ctx->sib_cfg > 0 && std::getenv("WM_NO_SIBLINGS") == nullptr) ? ctx->sib_cfg : 0;
     const bool same = ctx->graph && ctx->graph_B == B && std::memcmp(&g, &ctx->gp, sizeof(GenDev)) == 0 && ts.on == ctx->ts.on &&
                       ts.tb == ctx->ts.tb && ts.nots == ctx->ts.nots && ts.mit == ctx->ts.mit && ts.rp == ctx->ts.rp &&
-                      ts.rp_pen == ctx->ts.rp_pen && ts.rp_g == ctx->ts.rp_g;
+                      ts.rp_pen == ctx->ts.rp_pen && ts.rp_g == ctx->ts.rp_g &&
+                      // the captured launches carry the sampling scalars by value (the stream keys live in device memory, rewritten above)
+                      sd.on == ctx->samp.on && (!sd.on || (sd.inv_t == ctx->samp.inv_t && sd.seed_lo == ctx->samp.seed_lo && sd.seed_hi == ctx->samp.seed_hi));
     if (!same && ctx->graph) { hipGraphExecDestroy(ctx->graph); ctx->graph = nullptr; }
     if (!same && ctx->graph_base) { hipGraphExecDestroy(ctx->graph_base); ctx->graph_base = nullptr; }
-    ctx->gp = g; ctx->Bdec = B; ctx->ts = ts;
+    ctx->gp = g; ctx->Bdec = B; ctx->ts = ts; ctx->samp = sd;
 
     std::vector<int> ids((size_t)B * Tids, gp->pad_token_id), L(B, P), zero(B, 0);
     for (int b = 0; b < B; ++b) for (int i = 0; i < P; ++i) ids[(size_t)b * Tids + i] = gp->prompt[i];
@@ -678,6 +719,61 @@ extern "C" int wm_select_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_tim
             for (int k = 0; k < SEL_SP; ++k) hs += h2[(size_t)r * SEL_SP + k];     // (k_accept's order)
             out_entropy[r0 + r] = -hs;
         }
+    }
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(buf);
+    return rc;
+}
+
+// Sampling parity tap: caller-given rows through k_sample1 / k_sample_fin (include/wm.h), row r at position lens[r] under its own prefix.
+extern "C" int wm_sample_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* tsp, const wm_sample_params* sp, int R,
+                              const float* logits, const int32_t* prefixes, int Tmax, const int32_t* lens, const uint64_t* keys,
+                              int32_t* out_token, float* out_value, int32_t* out_forced)
+{
+    if (!ctx) return WM_ERR_ARG;
+    if (!gp || !sp || R < 1 || !logits || !prefixes || Tmax < 1 || !lens || !keys || !out_token || !out_value || !out_forced) {
+        ctx->err = "wm_sample_rows: bad arguments"; return WM_ERR_ARG; }
+    if (int rc = wm_sampling_check(ctx, "wm_sample_rows", sp)) return rc;
+    for (int r = 0; r < R; ++r)
+        if (lens[r] < 1 || lens[r] > std::min(Tmax, ctx->Tmax)) { ctx->err = "wm_sample_rows: lens must be in [1, min(Tmax, n_tgt)]"; return WM_ERR_ARG; }
+    WM_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    GenDev g{}; TsDev ts{};
+    if (int rc = wm_proc_setup(ctx, "wm_sample_rows", gp, tsp, &g, &ts)) return rc;
+    g.max_length = g.hard_max_length = ctx->Tmax;
+    g.inv_temp = 1.0f; g.force_accept = -1;
+    g.accept_mode = WM_ACCEPT_GREEDY; g.vanilla = 1;
+    wm_decode_invalidate(ctx);
+    wm_scalars_swap swap(ctx, g, ts);
+    const SampDev sd = wm_sampling_dev(ctx, sp->temperature, sp->seed);
+    int* buf = nullptr;
+    WM_HIP(hipMalloc(reinterpret_cast<void**>(&buf), ((size_t)15 * Tmax + 15) * sizeof(int)));
+    ts.rp_ids = buf; ts.rp_stride = Tmax; ts.rp_len = buf + (size_t)15 * Tmax;      // repetition rules: the rows' own prefixes
+    int rc = WM_OK;
+    std::vector<int4> recs(15);
+    for (int r0 = 0; r0 < R && rc == WM_OK; r0 += 15) {
+        const int n = std::min(15, R - r0);
+        for (int r = 0; r < n && ts.on; ++r) {          // the row's record at its prefix length, where k_cand_fin puts stream 0's verify rows
+            int4 s0 = make_int4(0, 0, -1, 0);
+            const int32_t* pre = prefixes + (size_t)(r0 + r) * Tmax;
+            for (int t = std::max(g.begin, 0); t < lens[r0 + r]; ++t) s0 = ts_fold(s0, pre[t], ts.tb);
+            recs[r] = ts_record(s0, lens[r0 + r], g.begin, ts.tb, g.V, ts.mit);
+        }
+        hipError_t e = hipMemcpyAsync(buf, prefixes + (size_t)r0 * Tmax, (size_t)n * Tmax * sizeof(int), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(buf + (size_t)15 * Tmax, lens + r0, n * sizeof(int), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(ctx->samp_keys, keys + r0, n * sizeof(uint64_t), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && ts.on) e = hipMemcpyAsync(ts.ver, recs.data(), n * sizeof(int4), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpy2DAsync(ctx->logits, (size_t)ctx->Vpad * sizeof(float), logits + (size_t)r0 * ctx->V,
+                                                  (size_t)ctx->V * sizeof(float), (size_t)ctx->V * sizeof(float), n, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) { ctx->err = std::string("wm_sample_rows: ") + hipGetErrorString(e); rc = WM_ERR_HIP; break; }
+        rc = wm_sample_launch(ctx, g, ts, sd, buf + (size_t)15 * Tmax, n, 0, 1);
+        if (rc) break;
+        e = hipMemcpyAsync(out_token + r0, ctx->amax, n * sizeof(int), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(out_value + r0, sd.val, n * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && wm_rules_on(ts)) e = hipMemcpyAsync(out_forced + r0, ts.forced, n * sizeof(int), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);          // (the host staging of this chunk is reused by the next)
+        if (e != hipSuccess) { ctx->err = std::string("wm_sample_rows: ") + hipGetErrorString(e); rc = WM_ERR_HIP; break; }
+        if (!wm_rules_on(ts)) std::fill(out_forced + r0, out_forced + r0 + n, 0);
     }
     (void)hipStreamSynchronize(st);
     (void)hipFree(buf);

@@ -63,6 +63,16 @@ struct TsDev {
 // the rules kernel family (*_ts) runs when the timestamp rules or the repetition rules are on
 static inline bool wm_rules_on(const TsDev& t) { return t.on || t.rp; }
 
+// Seeded sampling on the plain decode path (wm_set_sampling).  Passed by value to k_sample1 / k_sample_fin, which stand in for
+// k_select1* / k_select_argmax* in the vanilla branch of wm_dec_iteration while sampling is on; nothing else reads it.
+struct SampDev {
+    int on; float inv_t;                // fl(1 / temperature): the sampling temperature (GenDev.inv_temp stays typical acceptance's)
+    unsigned seed_lo, seed_hi;          // Philox key
+    const unsigned long long* keys;     // DEV [rows] the 64-bit stream key of every row (counter words 2 and 3)
+    float* part;                        // [Rcap][SEL_SP][8] slice partials {max text, perturbed max text, its id, max ts, sum exp ts at 1, perturbed max ts, its id, 0}
+    float* val;                         // [Rcap] the winner's perturbed value (wm_sample_rows reads it)
+};
+
 // state after one more sampled token / the record of a row whose sampled prefix has state `st` (host: wm_decode_begin_ts, device: the select kernels)
 __host__ __device__ __forceinline__ int4 ts_fold(int4 st, int tok, int tb)
 {
@@ -225,6 +235,11 @@ struct wm_ctx {
     GenDev gp{};
     TsDev ts{};                            // timestamp rules of the current decode (ts.on = 0: off); buffers allocated in wm_create
     wm_repeat_params rep{1.0f, 0};         // wm_set_repeat_rules: sticky until cleared (neutral = off)
+    // wm_set_sampling: sticky until cleared.  samp_set = what the caller gave (keys copied to the host vector; empty: 0 .. B - 1), samp = the
+    // current decode's (on = 0: off); its buffers (part, val, samp_keys) are allocated in wm_create
+    bool samp_set_on = false; float samp_set_temp = 1.0f; uint64_t samp_set_seed = 0; std::vector<uint64_t> samp_set_keys;
+    SampDev samp{};
+    unsigned long long* samp_keys = nullptr;    // [max(maxB, 16)]
     int Bdec = 0;
     bool began = false, first_done = false;
     long long iters = 0;
@@ -276,6 +291,10 @@ struct wm_replay_hooks {
 int wm_dec_replay(wm_ctx* ctx, int b0, int nb, const int32_t* tokens, int Tmax, const int32_t* lens, int npos, int n_layers, const wm_replay_hooks& hooks);
 // a replay call's streams against the last encode: B <= Benc, lens in [1, min(Tmax, n_tgt)], n_prompt in [min_prompt, lens]; errors under `who`
 int wm_replay_check(wm_ctx* ctx, const char* who, int B, int Tmax, const int32_t* lens, const int32_t* n_prompt, int min_prompt);
+// implemented in wm_sample.hip: k_sample1 + k_sample_fin over `nrows` rows of ctx->logits, row r at position pos[r] (DEV), keys sd.keys[r]; the token goes
+// to ctx->amax[out_row0 + r], the decision to ts.forced[out_row0 + r] (rules on), the winner's perturbed value to sd.val[out_row0 + r].  tap = 0: row r
+// is stream r of the decode (record from ts.st[r], prefix ids of stream r); 1: a tap row (record ts.ver[r], prefix ts.rp_ids + r * ts.rp_stride)
+int wm_sample_launch(wm_ctx* ctx, const GenDev& gp, const TsDev& ts, const SampDev& sd, const int* pos, int nrows, int out_row0, int tap);
 // implemented in wm_align.hip
 void wm_align_free(wm_ctx* ctx);
 // implemented in wm_score.hip

@@ -478,7 +478,8 @@ class WhisperMedusaModel:
         mlen = min(mlen, cfg.max_target_positions)
         if temperature is not None and float(temperature) > 0.0:
             # reference: do_sample path falls through with `result` unbound (model.py:1128-1156)
-            raise NotImplementedError("sampling (temperature > 0) is not supported with medusa")
+            raise NotImplementedError("sampling (temperature > 0) is not supported with medusa; pass sampling_seed= for the engine's seeded "
+                                      "sampling on the plain decode path")
         # G4: generate() forces generation_config.temperature = 1.0 when not sampling (model.py:1877-1881),
         # so the typical-acceptance branch of evaluate_posterior runs.  temperature=0.0 selects exact-match.
         mode = ACCEPT_GREEDY if (temperature is not None and float(temperature) == 0.0) else ACCEPT_TYPICAL
@@ -496,6 +497,94 @@ class WhisperMedusaModel:
                          max_initial_timestamp_index=cfg.max_initial_timestamp_index if timestamps else None,
                          repetition_penalty=1.0 if repetition_penalty is None else float(repetition_penalty),
                          no_repeat_ngram_size=0 if no_repeat_ngram_size is None else int(no_repeat_ngram_size))
+
+    # ---- seeded sampling and HF's temperature fallback (engine: csrc/wm_sample.hip) -------------------------------------------
+    def _sampling_request(self, temperature, kwargs, logits_processor) -> Optional[dict]:
+        """The sampling side of a generate() call: None unless ``sampling_seed`` is given AND the call asks for sampling (a positive scalar
+        temperature, ``do_sample=True``, or a tuple / list temperature: HF's fallback schedule) — then {seed, ids, seeks, temps, fallback},
+        after refusing, each by name, what sampling does not run with."""
+        seed = kwargs.get("sampling_seed")
+        if seed is None:
+            return None
+        ladder = isinstance(temperature, (tuple, list))
+        if ladder:
+            temps = [float(t) for t in temperature]
+        elif temperature is not None and float(temperature) > 0.0:
+            temps = [float(temperature)]
+        elif kwargs.get("do_sample"):
+            temps = [1.0]
+        else:
+            return None
+        if not temps or any(not np.isfinite(t) or t < 0.0 for t in temps):
+            raise ValueError(f"`temperature` has to hold finite values >= 0, but is {temperature!r}")
+        if kwargs.get("top_k") is not None or kwargs.get("top_p") is not None:
+            raise NotImplementedError("top_k / top_p are not supported with sampling_seed: the engine samples softmax(logits / T) over the whole "
+                                      "vocabulary (openai-whisper's Categorical; HF's default top_k=50 warper is not applied)")
+        if self.config.is_tree:
+            raise NotImplementedError("sampling (sampling_seed) is not supported with a candidate tree (medusa_choices with top-k > 1)")
+        if logits_processor and any(type(p_).__name__ not in _LOWERABLE_PROCESSORS for p_ in logits_processor):
+            raise NotImplementedError("sampling (sampling_seed) is not supported on the host processor path (logits_processor=)")
+        if kwargs.get("streamer") is not None:
+            raise NotImplementedError("streamer= is not supported with sampling (sampling_seed): a fallback attempt would take streamed tokens back")
+        if kwargs.get("chunk_longform"):
+            raise NotImplementedError("chunk_longform is not supported with sampling (sampling_seed); use sequential_longform")
+        ids = kwargs.get("sampling_stream_ids")
+        return dict(seed=int(seed), ids=None if ids is None else [int(v) for v in ids], seeks=kwargs.get("_sampling_seeks"), temps=temps,
+                    fallback=ladder)
+
+    @staticmethod
+    def sampling_stream_key(stream_id: int, seek_frames: int, attempt: int) -> int:
+        """The 64-bit stream key of one decode attempt: key_lo = the stream id, key_hi = 16 * the window's seek (mel frames) + the attempt index."""
+        return (int(stream_id) & 0xFFFFFFFF) | (((16 * int(seek_frames) + int(attempt)) & 0xFFFFFFFF) << 32)
+
+    @staticmethod
+    def _sampled_gp(gp: GenParams, T: float, seed: int, keys: List[int]) -> GenParams:
+        """``gp`` for one sampled attempt: the engine's plain decode path with the draw in place of the arg-max."""
+        import dataclasses
+        g = dataclasses.replace(gp, vanilla=True, accept_mode=ACCEPT_GREEDY, temperature=0.0, sampling_temperature=float(T),
+                                sampling_seed=int(seed), sampling_keys=list(keys))
+        for k, v in vars(gp).items():           # (what generate() hangs on the object: _time_precision)
+            if k.startswith("_"):
+                setattr(g, k, v)
+        return g
+
+    def _decode_with_fallback(self, eng, feats, gp: GenParams, samp: dict, sc_req: Optional[dict], encoded: bool):
+        """HF ``generate_with_fallback``: attempt i decodes the streams still flagged at temps[i] — 0: the configured path, > 0: the sampled plain
+        decode —, scores them (the existing scoring pass, at temperature 1 on the processed rows, as HF's _retrieve_avg_logprobs undoes the
+        temperature) and gates them.  A stream is final when it needs no fallback, was skipped by the no-speech gate, or the temperatures are
+        exhausted (the last attempt is kept).  Flagged streams are re-encoded as a sub-batch.  Without thresholds nothing is ever flagged.
+        Returns (seqs, infos or None, kept temperature, attempts per stream, ms of the scoring passes)."""
+        B = feats.shape[0]
+        ids = samp["ids"] if samp["ids"] is not None else list(range(B))
+        seeks = samp["seeks"] if samp["seeks"] is not None else [0] * B
+        if len(ids) != B or len(seeks) != B:
+            raise ValueError(f"sampling_stream_ids needs one id per stream ({B}), got {len(ids)}")
+        seqs, infos, kept, att = [None] * B, [None] * B, [0.0] * B, [0] * B
+        todo, stats, ms_sc, n_dec = list(range(B)), None, 0.0, 0
+        for i, T in enumerate(samp["temps"]):
+            if len(todo) != B or not (encoded or i > 0):
+                eng.encode(feats if len(todo) == B else feats[todo])        # (a rare path: one encoder pass over the flagged streams)
+            gp_i = gp if T == 0.0 else self._sampled_gp(gp, T, samp["seed"], [self.sampling_stream_key(ids[b], seeks[b], i) for b in todo])
+            out = eng.decode(gp_i, len(todo))
+            n_dec += 1
+            st = eng.stats()
+            if stats is None:
+                stats = st
+            else:
+                stats["ms_decode"] += st["ms_decode"]; stats["ms_encode"] += st["ms_encode"]
+            inf = None
+            if sc_req is not None:
+                out, inf, ms = self._score_run(eng, out, gp_i, sc_req)
+                ms_sc += ms
+            for j, b in enumerate(todo):
+                seqs[b], kept[b], att[b] = out[j], float(T), i + 1
+                infos[b] = None if inf is None else inf[j]
+            todo = [b for j, b in enumerate(todo) if inf is not None and inf[j]["needs_fallback"] and not inf[j]["skipped"]]
+            if not todo:
+                break
+        stats["fallback_decodes"] = n_dec - 1
+        self.last_stats = stats
+        return seqs, (infos if sc_req is not None else None), kept, att, ms_sc
 
     @torch.no_grad()
     def generate(self, input_features: Optional[torch.Tensor] = None, generation_config=None, logits_processor=None,
@@ -562,8 +651,12 @@ class WhisperMedusaModel:
                 warnings.warn("generate(generation_config=...): the Medusa path does not honour " + ", ".join(ignored) +
                               " from a passed config (see INTEGRATION.md, 'generation_config fields'); pass processors / criteria explicitly",
                               UserWarning, stacklevel=2)
-        if kwargs.get("do_sample"):
-            raise NotImplementedError("sampling (do_sample=True) is not supported with medusa")      # model.py:1128-1156: no Medusa branch
+        # Seeded sampling / temperature fallback: opt-in through `sampling_seed=` — the random stream is the engine's own
+        # counter-based one, not torch's generator; without it every refusal below stands as it always has
+        samp = self._sampling_request(temperature, kwargs, logits_processor)
+        if samp is None and kwargs.get("do_sample"):
+            raise NotImplementedError("sampling (do_sample=True) is not supported with medusa; pass sampling_seed= for the engine's seeded "
+                                      "sampling on the plain decode path")      # model.py:1128-1156: no Medusa branch
         if top_logprobs is not None:
             if isinstance(top_logprobs, bool) or not isinstance(top_logprobs, (int, np.integer)) or not 1 <= int(top_logprobs) <= _scores.TOPK_MAX:
                 raise ValueError(f"`top_logprobs` has to be an integer in 1..{_scores.TOPK_MAX}, but is {top_logprobs!r}")
@@ -571,8 +664,9 @@ class WhisperMedusaModel:
                 raise NotImplementedError("top_logprobs is not supported with chunk_longform / sequential_longform (short-form only)")
             top_logprobs = int(top_logprobs)
         if kwargs.get("sequential_longform"):
-            self._check_sequential(return_timestamps, condition_on_prev_tokens, temperature, return_token_timestamps, logits_processor,
-                                   stopping_criteria, kwargs.get("streamer"), prompt_ids, prompt_condition_type)
+            self._check_sequential(return_timestamps, condition_on_prev_tokens, None if samp is not None else temperature,
+                                   return_token_timestamps, logits_processor, stopping_criteria, kwargs.get("streamer"), prompt_ids,
+                                   prompt_condition_type)
         # HF RepetitionPenaltyLogitsProcessor / NoRepeatNGramLogitsProcessor (GenerationMixin._get_logits_processor builds them from these two
         # fields; the reference's generate() drops both): inside the engine's select kernels, every row under its own prefix
         rep_pen, rep_g = kwargs.get("repetition_penalty"), kwargs.get("no_repeat_ngram_size")
@@ -667,6 +761,9 @@ class WhisperMedusaModel:
             self.set_max_batch(B)
         gp = self._gen_params(language, task, kwargs.get("exponential_decay_length_penalty"),
                               kwargs.get("max_new_tokens"), kwargs.get("max_length"),
+                              # (sampling: attempt 0 of a fallback schedule at temperature 0 is today's call with that tuple — exact-match
+                              # acceptance —, every sampled attempt derives its own parameters from these: _sampled_gp)
+                              (0.0 if samp["temps"][0] == 0.0 else None) if samp is not None else
                               temperature if not isinstance(temperature, (tuple, list)) else temperature[0],
                               kwargs.get("vanilla", False), kwargs.get("posterior_threshold"),
                               kwargs.get("posterior_alpha"), kwargs.get("suppress_tokens"),
@@ -683,6 +780,11 @@ class WhisperMedusaModel:
         # encoder pass over the same clips (the automatic policy's gain at 2-3 clips is smaller than an encoder pass)
         if self._micro_batches is None and kwargs.get("_encoded_batch") == B and getattr(self._engine, "_B", None) == B:
             n_ctx = 1
+        if samp is not None:
+            if getattr(gp, "_host_criteria", None) or getattr(gp, "_host_processors", None):
+                raise NotImplementedError("sampling (sampling_seed) is not supported on the host processor path (logits_processor= / "
+                                          "stopping_criteria= that the engine cannot lower)")
+            n_ctx = 1           # the model's own engine: the micro-batch pool is not taught sampling
         if n_ctx > 1 and B >= 2:
             pool = self._get_pool(n_ctx)
             tsf = None
@@ -714,8 +816,29 @@ class WhisperMedusaModel:
             return self._outputs(seqs, gp, return_dict_in_generate, return_segments)
         # language detection just encoded exactly these clips on this engine (one language group, same order): its encoder output and
         # cross-K/V are still resident — decode from them instead of running the encoder a second time
-        if not (kwargs.get("_encoded_batch") == B and getattr(eng, "_B", None) == B):
+        if samp is None and not (kwargs.get("_encoded_batch") == B and getattr(eng, "_B", None) == B):
             eng.encode(feats)                                               # F1 + F2
+        if samp is not None:
+            seqs, infos, kept, att, ms = self._decode_with_fallback(eng, feats, gp, samp, sc_req, kwargs.get("_encoded_batch") == B and
+                                                                    getattr(eng, "_B", None) == B)
+            fb = dict(fallback_temperature=torch.tensor(kept, dtype=torch.float32, device=self.device),
+                      fallback_attempts=torch.tensor(att, dtype=torch.long, device=self.device))
+            self.last_fallback = fb
+            sc = None
+            if sc_req is not None:
+                self.last_stats["ms_token_logprobs"] = ms
+                sc = dict(self._score_pack(infos, seqs, gp, sc_req), **fb)
+            tt = None
+            if tt_req is not None:
+                if getattr(eng, "_B", None) != B:       # the last attempt left a sub-batch resident
+                    eng.encode(feats)
+                rows, ms = self._token_ts_run(eng, seqs, gp, tt_req, 0)
+                self.last_stats["ms_token_timestamps"] = ms
+                tt = self._token_ts_tensor(rows, seqs, gp)
+            out = self._outputs(seqs, gp, return_dict_in_generate, return_segments, tt, tt_side, sc, sc_side)
+            if sc is None and isinstance(out, dict):
+                out.update(fb)
+            return out
         if streamer is not None or host_crit:
             # one iteration per engine call: the streamer gets the tokens of every iteration (model.py:1034-1035 prompt, :758-759
             # tokens, :795-796 end); stopping criteria that are not static length / EOS rules are asked after every iteration with
@@ -1104,6 +1227,7 @@ class WhisperMedusaModel:
         plens = [0] * len(langs)
         req, outer = kw.pop("_tt_req", None), kw.pop("_tt_outer", False)
         sreq, souter = kw.pop("_sc_req", None), kw.pop("_sc_outer", False)
+        sids, sseeks = kw.pop("sampling_stream_ids", None), kw.pop("_sampling_seeks", None)      # (seeded sampling: they follow their clips into the groups)
         tts: List[Optional[torch.Tensor]] = [None] * len(langs)
         scs: List[Optional[dict]] = [None] * len(langs)
         ms_tt = ms_sc = 0.0
@@ -1115,6 +1239,9 @@ class WhisperMedusaModel:
                 reuse["_tt_req"] = dict(req, num_frames=[nf[i] for i in idx] if isinstance(nf, list) else nf)
             if sreq is not None:
                 reuse["_sc_req"] = sreq
+            if kw.get("sampling_seed") is not None:
+                reuse["sampling_stream_ids"] = [i if sids is None else int(sids[i]) for i in idx]
+                reuse["_sampling_seeks"] = None if sseeks is None else [sseeks[i] for i in idx]
             out = self.generate(input_features[idx], language=l, _language_resolved=True, **reuse, **kw)
             if req is not None:
                 ms_tt += self.last_stats.get("ms_token_timestamps", 0.0)
@@ -1318,7 +1445,8 @@ class WhisperMedusaModel:
             raise NotImplementedError("condition_on_prev_tokens=True is not supported with sequential_longform: every window of a clip is "
                                       "decoded under the same prompt (conditioning needs one prompt per stream)")
         if isinstance(temperature, (tuple, list)):
-            raise NotImplementedError("a tuple `temperature` (temperature fallback) is not supported with sequential_longform")
+            raise NotImplementedError("a tuple `temperature` (temperature fallback) is not supported with sequential_longform without "
+                                      "sampling_seed= (the engine's seeded sampling, DESIGN.md §2h)")
         if return_token_timestamps:
             raise NotImplementedError("return_token_timestamps is not supported together with sequential_longform")
         if not self.config.supports_timestamps:
@@ -1374,6 +1502,11 @@ class WhisperMedusaModel:
         kw.pop("detect_language", None)
         prompts: List[Optional[List[int]]] = [None] * B
         ms_sc = [0.0]
+        # seeded sampling / temperature fallback: a window's stream key comes from its clip's id and its seek, not from the round
+        sampling = kw.get("sampling_seed") is not None
+        sids, n_fb = kw.pop("sampling_stream_ids", None), [0]
+        if sids is not None and len(sids) != B:
+            raise ValueError(f"sampling_stream_ids needs one id per clip ({B}), got {len(sids)}")
 
         def decode_round(clips, seeks, snf):
             win = self.engine.gather_windows(feats, clips, seeks, snf)
@@ -1386,10 +1519,14 @@ class WhisperMedusaModel:
             for l in groups:
                 widx = [q for q, b in enumerate(clips) if langs[b] == l]
                 reuse = {"_encoded_batch": len(clips)} if len(groups) == 1 and len(new) == len(clips) else {}
+                if sampling:
+                    reuse["sampling_stream_ids"] = [clips[q] if sids is None else int(sids[clips[q]]) for q in widx]
+                    reuse["_sampling_seeks"] = [int(seeks[q]) for q in widx]
                 o = self.generate(win[widx], language=l, _language_resolved=True, return_timestamps=True, time_precision=tprec,
                                   **reuse, **kw, **({"_sc_req": sreq} if sreq is not None else {}))
                 P = len(self._last_prompt)
                 rows = o.cpu()
+                n_fb[0] += self.last_stats.get("fallback_decodes", 0)
                 if sreq is not None:
                     ms_sc[0] += self.last_stats.get("ms_token_logprobs", 0.0)
                     sc = {k: v.cpu() for k, v in self._last_sc.items() if not k.startswith("_")}
@@ -1418,6 +1555,8 @@ class WhisperMedusaModel:
             self.detected_languages = list(langs)
         stats = dict(getattr(self, "last_stats", None) or {})
         stats["longform_windows"] = [len(w) for w in windows]
+        if sampling:
+            stats["fallback_decodes"] = n_fb[0]
         self.last_stats = stats
         fields = None
         if sreq is not None:
@@ -1457,6 +1596,10 @@ class WhisperMedusaModel:
                     fields[k] = [torch.stack([w["scores"][k] for w in ws]) if ws else torch.zeros(0) for ws in windows]
             fields["window_avg_logprob"] = [torch.stack([w["scores"]["avg_logprob"] for w in ws]) if ws else torch.zeros(0) for ws in windows]
             fields["window_seek"] = [torch.tensor([w["seek"] for w in ws], dtype=torch.long) for ws in windows]
+            if any_w is not None and "fallback_temperature" in any_w["scores"]:
+                fields["window_temperature"] = [torch.stack([w["scores"]["fallback_temperature"] for w in ws]) if ws else torch.zeros(0) for ws in windows]
+                fields["window_attempts"] = [torch.stack([w["scores"]["fallback_attempts"] for w in ws]) if ws else torch.zeros(0, dtype=torch.long)
+                                             for ws in windows]
             self.last_scores = fields
             self.last_stats["ms_token_logprobs"] = ms_sc[0]
         if fields is not None and (sreq["want"] or rdg):
@@ -1488,6 +1631,10 @@ class WhisperMedusaModel:
         scoring = any(kw.get(k) is not None or getattr(gc, k, None) is not None
                       for k in ("no_speech_threshold", "logprob_threshold", "compression_ratio_threshold")) \
             or bool(kw.get("return_token_logprobs")) or kw.get("top_logprobs") is not None
+        if mine and kw.get("sampling_seed") is not None:
+            # seeded sampling: a stream keeps the key of its GLOBAL index (or of its caller-given id) on whichever rank it lands
+            gids = kw.get("sampling_stream_ids")
+            kw = dict(kw, sampling_stream_ids=[s_ if gids is None else int(gids[s_]) for s_ in mine])
         if mine:
             out = self.generate(input_features[mine], **kw)
             rows = out["sequences"] if isinstance(out, dict) else out

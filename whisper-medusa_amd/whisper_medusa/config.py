@@ -347,6 +347,12 @@ class GenParams:
     repetition_penalty: float = 1.0
     no_repeat_ngram_size: int = 0
 
+    # Seeded sampling on the plain decode path (wm_set_sampling): sampling_temperature > 0 with vanilla=True draws every token
+    # from softmax(processed row / T) under the engine's counter-based noise; `temperature` above stays typical acceptance's.  0 = off
+    sampling_temperature: float = 0.0
+    sampling_seed: int = 0
+    sampling_keys: Optional[List[int]] = None        # one 64-bit stream key per stream; None: 0 .. B - 1
+
     @property
     def repeat_rules(self) -> bool:
         return float(self.repetition_penalty) != 1.0 or int(self.no_repeat_ngram_size) != 0

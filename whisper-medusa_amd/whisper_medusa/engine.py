@@ -53,6 +53,10 @@ class WmRepeatParams(C.Structure):
     _fields_ = [("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int32)]
 
 
+class WmSampleParams(C.Structure):
+    _fields_ = [("temperature", C.c_float), ("seed", C.c_uint64), ("stream_keys", C.POINTER(C.c_uint64)), ("n_keys", C.c_int32)]
+
+
 class WmAlignParams(C.Structure):
     _fields_ = [("heads", C.POINTER(C.c_int32)), ("n_heads", C.c_int32), ("median_filter_width", C.c_int32), ("time_precision", C.c_float)]
 
@@ -74,7 +78,7 @@ EXPORTS = ["wm_create", "wm_destroy", "wm_last_error", "wm_abi_version", "wm_bui
            "wm_decode_begin_ts", "wm_select_rows",
            "wm_token_timestamps", "wm_get_align_probs", "wm_get_align_matrix", "wm_dtw",
            "wm_score_tokens", "wm_score_rows", "wm_set_repeat_rules", "wm_score_tokens_topk", "wm_topk_rows",
-           "wm_logmel_long", "wm_gather_windows"]
+           "wm_logmel_long", "wm_gather_windows", "wm_set_sampling", "wm_sample_rows"]
 
 _lib = {}
 
@@ -121,6 +125,9 @@ def load_library(path: Optional[str] = None, act_fp16: bool = False) -> C.CDLL:
     lib.wm_select_rows.argtypes = [vp, C.POINTER(WmGenParams), C.POINTER(WmTimestampParams), i32, f32p, i32p, i32, i32p, i32p,
                                    i32p, f32p, f32p, i32p]
     lib.wm_set_repeat_rules.argtypes = [vp, C.POINTER(WmRepeatParams)]
+    lib.wm_set_sampling.argtypes = [vp, C.POINTER(WmSampleParams)]
+    lib.wm_sample_rows.argtypes = [vp, C.POINTER(WmGenParams), C.POINTER(WmTimestampParams), C.POINTER(WmSampleParams), i32, f32p, i32p, i32, i32p,
+                                   C.POINTER(C.c_uint64), i32p, f32p, i32p]
     lib.wm_decode_run.argtypes = [vp, i32, i32p]
     lib.wm_get_tokens.argtypes = [vp, i32, i32p, i32, i32p]
     lib.wm_get_stats.argtypes = [vp, C.POINTER(WmStats)]
@@ -323,9 +330,31 @@ class Engine:
             rp = WmRepeatParams(pen, g)
             self._check(self.lib.wm_set_repeat_rules(self.h, C.byref(rp)), "wm_set_repeat_rules")
 
+    def set_sampling(self, temperature: Optional[float], seed: int = 0, stream_keys: Optional[Sequence[int]] = None, n_keys: Optional[int] = None) -> None:
+        """wm_set_sampling: seeded sampling for the following plain decodes (``gp.vanilla``), sticky until cleared (``temperature=None``).
+        ``stream_keys``: one 64-bit key per stream (None: 0 .. n_keys - 1); their number must equal the decode's B."""
+        if temperature is None:
+            self._check(self.lib.wm_set_sampling(self.h, None), "wm_set_sampling")
+            return
+        if stream_keys is None:
+            sp = WmSampleParams(float(temperature), int(seed) & (2 ** 64 - 1), None, int(n_keys or 0))
+        else:
+            keys = np.ascontiguousarray([int(k) & (2 ** 64 - 1) for k in stream_keys], dtype=np.uint64)
+            sp = WmSampleParams(float(temperature), int(seed) & (2 ** 64 - 1), keys.ctypes.data_as(C.POINTER(C.c_uint64)), len(keys))
+        self._check(self.lib.wm_set_sampling(self.h, C.byref(sp)), "wm_set_sampling")
+
+    def _set_sampling(self, gp: GenParams, B: int) -> None:
+        """The context's sampling request follows ``gp`` before every decode (wm_set_sampling is sticky), like the repetition rules."""
+        T = float(getattr(gp, "sampling_temperature", 0.0) or 0.0)
+        if T == 0.0:
+            self.set_sampling(None)
+        else:
+            self.set_sampling(T, int(gp.sampling_seed), gp.sampling_keys, B)
+
     def decode(self, gp: GenParams, B: int, max_iters: int = 1 << 30, on_iteration=None) -> List[List[int]]:
         g, _keep = self._gen_struct(gp)
         self._set_repeat_rules(gp)
+        self._set_sampling(gp, B)
         self._kv_stamp = object()             # the decode loop rewrites the self-attention cache: forward()'s cache handles go stale
         if gp.timestamps:                     # WhisperTimeStampLogitsProcessor in the loop (include/wm.h wm_decode_begin_ts)
             ts = self._ts_struct(gp)
@@ -382,6 +411,28 @@ class Engine:
                                             lens.ctypes.data_as(i32p), probe.ctypes.data_as(i32p), am.ctypes.data_as(i32p),
                                             pp.ctypes.data_as(f32p), H.ctypes.data_as(f32p), fo.ctypes.data_as(i32p)), "wm_select_rows")
         return dict(argmax=am, p_probe=pp, entropy=H, ts_forced=fo)
+
+    def sample_rows(self, gp: GenParams, logits: np.ndarray, prefixes: Sequence[Sequence[int]], keys: Sequence[int], temperature: float,
+                    seed: int) -> dict:
+        """Sampling parity tap (wm_sample_rows): rows ``logits [R, V]``, row r under its own prefix at position ``len(prefixes[r])`` with stream
+        key ``keys[r]``, through k_sample1 / k_sample_fin.  Returns numpy arrays token, value (the winner's v / T + g), ts_forced."""
+        x = np.ascontiguousarray(logits, dtype=np.float32)
+        R, V = x.shape
+        if V != self.cfg.vocab_size or len(prefixes) != R or len(keys) != R:
+            raise ValueError("sample_rows: logits must be [R, vocab] with one prefix and one stream key per row")
+        pre, lens, Tmax, _ = self._pack_ids(prefixes)
+        k64 = np.ascontiguousarray([int(k) & (2 ** 64 - 1) for k in keys], dtype=np.uint64)
+        tok = np.zeros(R, np.int32); val = np.zeros(R, np.float32); fo = np.zeros(R, np.int32)
+        g, _keep = self._gen_struct(gp)
+        self._set_repeat_rules(gp)
+        ts = self._ts_struct(gp) if gp.timestamps else None
+        sp = WmSampleParams(float(temperature), int(seed) & (2 ** 64 - 1), None, 0)
+        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        self._kv_stamp = object()
+        self._check(self.lib.wm_sample_rows(self.h, C.byref(g), C.byref(ts) if ts is not None else None, C.byref(sp), R, x.ctypes.data_as(f32p),
+                                            pre.ctypes.data_as(i32p), Tmax, lens.ctypes.data_as(i32p), k64.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                            tok.ctypes.data_as(i32p), val.ctypes.data_as(f32p), fo.ctypes.data_as(i32p)), "wm_sample_rows")
+        return dict(token=tok, value=val, ts_forced=fo)
 
     # ---- token-level timestamps (include/wm.h wm_token_timestamps) ---------------------------------
     def token_timestamps(self, seqs: Sequence[Sequence[int]], n_prompt, alignment_heads: Sequence[Sequence[int]], median_filter_width: int = 7,
