@@ -240,6 +240,44 @@ int wm_set_repeat_rules(wm_ctx* ctx, const wm_repeat_params* rp /* NULL = off */
 typedef struct wm_sample_params { float temperature; uint64_t seed; const uint64_t* stream_keys /* HOST [n_keys]; NULL: 0..B-1 */; int32_t n_keys; } wm_sample_params;
 int wm_set_sampling(wm_ctx* ctx, const wm_sample_params* sp /* NULL = off */);
 
+/* Beam search on the plain decode path (additive to ABI v9; csrc/wm_beam.hip).  Stands in for HF generate(num_beams=n) with
+ * do_sample off — GenerationMixin._beam_search (transformers generation/utils.py) and its helpers _get_top_k_continuations,
+ * _get_running_beams_for_next_iteration, _update_finished_beams, _check_early_stop_heuristic, _beam_search_has_unfinished_sequences — which the
+ * reference refuses (model.py:1153-1156).  Beam j of clip b is stream b * n + j of a plain decode of B * n streams, all at one length L; the model
+ * runs as the ordinary base pass.  One step, everything on the device (P = the whole decoder prompt length, V = vocab):
+ *   1. The row of stream s is w = log_softmax(raw logits) FIRST (fp32: x - (m + logf(sum exp(x - m))), the sum in 16 slice partials); the
+ *      processors then run ON THE LOG-PROBABILITIES with no renormalisation afterwards (HF: `log_probs = logits_processor(ids, log_probs)`): the
+ *      repetition rules, then the processors of wm_gen_params — the exponential decay reads abs(w[eos]) —, then the timestamp rules (their own
+ *      decision compares logsumexp(w[tb:]) with max(w[:tb]) of the processed row) — each row under its OWN beam's prefix, at the common length L.
+ *   2. Each clip keeps the best 2n of the n * V accumulated values a = running_score[j] + w[j][token] (one fp32 add).  A candidate HITS when its
+ *      token is EOS or L + 1 >= max_length.  The next running beams are the best n of a + (hit ? -1e9f : 0) (HF's fp32 -1e9 arithmetic, the
+ *      running score keeps that sum).  Only hits among the first n ranks can enter the finished table (n entries, initially -1e9 / not set), scored
+ *      a / fl((L + 1 - P) ** length_penalty) (the power in double, rounded to fp32, a true fp32 division), then + -1e9f when early_stopping is
+ *      True and the table is full, + -1e9f when the heuristic flag is off, + -1e9f for every candidate that may not enter, in that order.
+ *      The initial running scores are [0, -1e9, ...].
+ *   3. torch.topk leaves ties open; the engine orders by value descending, then by (beam, token) ascending, and in the finished-table merge an
+ *      older entry comes before a new one (old entries by their table index).
+ *   4. After L += 1 the heuristic flag is and-ed with any_j(running_score[0] / fl(len ** length_penalty) > (set[j] ? min(finished scores) : -1e9)),
+ *      len = max_length - P for early_stopping "never" with length_penalty > 0, else L - P.  A clip is done when the flag is off, or
+ *      early_stopping is True and every table entry is set, or all 2n candidates hit (HF's three-way condition, taken per clip: a clip's result does
+ *      not depend on its batch).  A done clip's streams keep stepping as no-ops.  The output is the finished table, never the running beams.
+ * Then stream s takes over the self K/V rows [0, L), the ids row and the committed timestamp state of stream beam_idx[s] (through a shadow buffer:
+ * gather, then write back) and appends its token.  The encoder ran once per clip: wm_decode_begin replicates the cross K/V of clip b (slot b) to
+ * slots b * n .. b * n + n - 1 (the fp8 copy and its scales included) and wm_decode_run moves it back (slot b * n -> b) when the last clip is
+ * done, so that the context is in the state wm_encode left and the replay entry points (wm_score_tokens, wm_token_timestamps) work unchanged.
+ * length_penalty is read as fp32.  Sticky on the context until cleared (NULL), like wm_set_sampling; read by wm_decode_begin / wm_decode_begin_ts,
+ * whose B is then the number of CLIPS.  WM_ERR_ARG (wm_last_error says why) from wm_set_beam: num_beams outside [2, WM_BEAM_MAX], a penalty that
+ * is not finite, early_stopping outside 0..2; from wm_decode_begin*: wm_gen_params.vanilla == 0, a candidate-tree context, sampling set at the same
+ * time, B * num_beams > max_batch. */
+#define WM_BEAM_MAX 8
+typedef struct wm_beam_params { int32_t num_beams; float length_penalty; int32_t early_stopping /* 0 False, 1 True, 2 "never" */; } wm_beam_params;
+int wm_set_beam(wm_ctx* ctx, const wm_beam_params* bp /* NULL = off */);
+/* The finished hypothesis `rank` (0 = best) of clip `clip` of the last beam decode (HF: `sequences` / `sequences_scores` of _beam_search, row
+ * clip * num_return_sequences + rank): ids (prompt + generated, EOS included) to out_ids (HOST, cap entries of room), their number to *n, the
+ * length-penalised score to *score.  An entry that was never set has the prompt alone and the score -1e9.  WM_ERR_STATE when the last decode was
+ * no beam decode or is not finished. */
+int wm_get_beam_result(wm_ctx* ctx, int clip, int rank, int32_t* out_ids /* HOST */, int cap, int* n, float* score);
+
 /* ---- F3..F14 the Medusa decode loop (replaces _medusa_greedy_search, model.py:404-835) ---- */
 int wm_decode_begin(wm_ctx* ctx, const wm_gen_params* gp, int B);
 /* wm_decode_begin with the timestamp rules on (ts != NULL; NULL = wm_decode_begin).  WM_ERR_ARG (wm_last_error says why): a candidate tree
@@ -253,7 +291,8 @@ int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_
  * tokens, accept histogram and per-stream iteration counts are those of the lock-step schedule).
  * Environment: WM_NO_STEP=1 lock-step schedule, WM_NO_CARRY=1 no hidden-state carry, WM_NO_GRAPH=1 eager launches. */
 int wm_decode_run(wm_ctx* ctx, int max_iters, int* n_unfinished);
-/* ids (prompt + generated, post-EOS overwrite of model.py:798-810 applied) of one stream. */
+/* ids (prompt + generated, post-EOS overwrite of model.py:798-810 applied) of one stream.  After a beam decode (wm_set_beam): `stream` is the
+ * clip and the ids are its finished hypothesis of rank 0 (wm_get_beam_result). */
 int wm_get_tokens(wm_ctx* ctx, int stream, int32_t* out /* HOST */, int cap, int* n);
 int wm_get_stats(wm_ctx* ctx, wm_stats* out /* HOST */);
 int wm_sync(wm_ctx* ctx);
@@ -349,6 +388,25 @@ int wm_select_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_para
 int wm_sample_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* ts /* may be NULL */, const wm_sample_params* sp, int R,
                    const float* logits, const int32_t* prefixes, int Tmax, const int32_t* lens, const uint64_t* keys /* HOST [R] */,
                    int32_t* out_token, float* out_value /* winner's perturbed value */, int32_t* out_forced);
+/* Beam-search parity tap (HF GenerationMixin._beam_search steps b to g on caller-given rows): S steps of logits (HOST float32 [S][G][n][vocab],
+ * n = bp->num_beams, G clips) through the select, bookkeeping and ids-reorder kernels of the beam decode — no model, no K/V.  Stream s = g * n + j
+ * starts from prefixes[s][0 .. prefix_len) (HOST int32 [G * n][Tmax]; one common length, >= gp->prompt_len = P of the length penalty) with running
+ * score init_scores[s] (HOST [G * n]; NULL: HF's first-step [0, -1e9, ..] per clip); ts NULL: timestamp rules off (the repetition rules of the
+ * context apply either way).  A clip that is done stops changing; the steps it took go to out_steps[g] (S when it never finished).
+ * Outputs (HOST): per step the ordered 2n candidates of every clip — cand_val / cand_beam / cand_tok [S][G][2n] (entries of a clip's steps past its
+ * end are not defined) — and beam_idx [S][G * n] (the source stream of every stream, s itself for a clip that is done); at the end the finished
+ * table — fin_ids [G][n][Tmax], fin_len / fin_score / fin_set [G][n] — and the running beams: run_ids [G * n][Tmax], run_len [G * n], run_score
+ * [G * n].  WM_ERR_ARG (wm_last_error says why): G * n > max_batch, prefix_len outside [max(P, 1), Tmax], prefix_len + S > min(Tmax, n_tgt), a bad
+ * bp.  Overwrites the decode state like wm_forward_logits (begin again afterwards). */
+int wm_beam_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* ts /* may be NULL */, const wm_beam_params* bp, int G, int S,
+                 const float* logits, const int32_t* prefixes, int Tmax, int prefix_len, const float* init_scores /* may be NULL */,
+                 float* cand_val, int32_t* cand_beam, int32_t* cand_tok, int32_t* beam_idx, int32_t* out_steps,
+                 int32_t* fin_ids, int32_t* fin_len, float* fin_score, int32_t* fin_set, int32_t* run_ids, int32_t* run_len, float* run_score);
+/* The K/V reorder of a beam step alone (HF: Cache.reorder_cache(beam_idx) behind _beam_search step g): stream s < B_streams takes over the self
+ * K/V rows [0, len) of every kv layer from stream beam_idx[s] (HOST int32 [B_streams], each in [0, B_streams)), through the shadow buffer;
+ * beam_idx[s] == s moves nothing.  WM_ERR_ARG for B_streams outside [1, max_batch], len outside [1, n_tgt], an index out of range.  Overwrites
+ * kvlen of the decode state (begin again afterwards). */
+int wm_beam_reorder_kv(wm_ctx* ctx, int B_streams, const int32_t* beam_idx /* HOST */, int len);
 /* Scoring parity tap, the counterpart of wm_select_rows: R caller-given logits rows (HOST float32 [R][vocab]) through the scoring kernels of
  * wm_score_tokens only, row r under prefix prefixes[r][0 .. lens[r]) (HOST int32 [R][Tmax]) with cur_len = lens[r] — its own length, exponential
  * decay included — and target targets[r]; ts NULL: rules off.  out_logprob HOST [R]: what HF's log_softmax(processors(row))[target] gives, -inf for

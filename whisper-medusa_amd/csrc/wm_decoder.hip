@@ -1879,6 +1879,9 @@ int wm_dec_iteration(wm_ctx* ctx, int Mper_base)
             const int nb = min(chunk, B - b0);
             int rc = wm_dec_pass(ctx, b0, nb, Mper_base, 0, 0, 0);
             if (rc) return rc;
+            if (ctx->beam.on) {     // beam search (wm_set_beam; wm_beam.hip): select, bookkeeping and reorder stand in for the arg-max and the accept below
+                return wm_beam_step(ctx, gp, ts, ctx->beam, true);
+            }
             if (ctx->samp.on) {     // seeded sampling (wm_set_sampling): the token of row b0 + row is drawn at position L, not the arg-max
                 TsDev tsb = ts; tsb.st += b0; tsb.rp_ids += (size_t)b0 * ts.rp_stride;
                 SampDev sd = ctx->samp; sd.keys += b0;

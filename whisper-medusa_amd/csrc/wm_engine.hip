@@ -41,6 +41,7 @@ extern "C" void wm_destroy(wm_ctx* ctx)
     for (void* b : bufs) if (b) hipFree(b);
     wm_align_free(ctx);
     wm_score_free(ctx);
+    wm_beam_free(ctx);
     if (ctx->ev0) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) hipEventDestroy(ctx->ev1);
     if (ctx->own_stream && ctx->stream) hipStreamDestroy(ctx->stream);
@@ -299,6 +300,7 @@ extern "C" int wm_encode(wm_ctx* ctx, const float* feats, int B)
     if (!ctx || !feats) return WM_ERR_ARG;
     WM_HIP(hipSetDevice(ctx->device));
     ctx->began = false;
+    ctx->beam_expanded = false;         // (the encoder pass rewrites the cross K/V slots)
     return wm_enc_encode(ctx, feats, B);
 }
 
@@ -307,6 +309,7 @@ extern "C" int wm_set_encoder_output(wm_ctx* ctx, const float* hidden, int B)
     if (!ctx || !hidden) return WM_ERR_ARG;
     WM_HIP(hipSetDevice(ctx->device));
     ctx->began = false;
+    ctx->beam_expanded = false;
     return wm_enc_set_output(ctx, hidden, B);
 }
 
@@ -367,6 +370,9 @@ int wm_proc_setup(wm_ctx* ctx, const char* who, const wm_gen_params* gp, const w
 void wm_decode_invalidate(wm_ctx* ctx, bool drop_graphs)
 {
     ctx->began = false; ctx->use_done = false; ctx->host_carry = false; ctx->dev_carry = false; ctx->step_flow = false;
+    if (ctx->beam_expanded) (void)wm_beam_compact(ctx);         // a beam decode that was left unfinished: the cross K/V goes back to its clips' slots
+    if (drop_graphs && ctx->graph_beam) { (void)hipGraphExecDestroy(ctx->graph_beam); ctx->graph_beam = nullptr; }
+    if (drop_graphs) ctx->beam_keep_valid = false;
     if (drop_graphs && ctx->graph) { (void)hipGraphExecDestroy(ctx->graph); ctx->graph = nullptr; }
     if (drop_graphs && ctx->graph_base) { (void)hipGraphExecDestroy(ctx->graph_base); ctx->graph_base = nullptr; }
 }
@@ -417,8 +423,20 @@ extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm
 {
     if (!ctx || !gp) return WM_ERR_ARG;
     WM_HIP(hipSetDevice(ctx->device));
+    if (ctx->beam_expanded) { if (int rc = wm_beam_compact(ctx)) return rc; }      // (a beam decode that was never run to its end)
     if (ctx->Benc < 1 || B != ctx->Benc) { ctx->err = "wm_decode_begin: call wm_encode with the same B first"; return WM_ERR_STATE; }
     const int P = gp->prompt_len, Tids = ctx->Tal;
+    // beam search (wm_set_beam; HF _beam_search): B clips become B * n streams of the plain decode
+    const bool beam = ctx->beam_set_on;
+    const int nbeam = beam ? ctx->beam_set.num_beams : 1, G = B;
+    if (beam) {
+        if (!gp->vanilla) { ctx->err = "wm_decode_begin: beam search runs on the plain decode path only (wm_gen_params.vanilla = 1)"; return WM_ERR_ARG; }
+        if (ctx->tn) { ctx->err = "wm_decode_begin: beam search is not supported with a candidate tree (medusa_choices with top-k > 1)"; return WM_ERR_ARG; }
+        if (ctx->samp_set_on) { ctx->err = "wm_decode_begin: beam search and sampling (wm_set_sampling) cannot be on together"; return WM_ERR_ARG; }
+        if (B * nbeam > ctx->maxB) { ctx->err = "wm_decode_begin: B * num_beams exceeds max_batch"; return WM_ERR_ARG; }
+        B *= nbeam;
+    }
+    ctx->beam_done = false;
     if (P < 1 || P >= ctx->Tmax - ctx->K - 1) {
         // same condition class as the reference's over-long prompt ValueError (model.py:1526-1529)
         ctx->err = "wm_decode_begin: prompt length must be in [1, n_tgt - K - 2]"; return WM_ERR_ARG; }
@@ -448,14 +466,28 @@ extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm
     ctx->step_flow = ctx->dev_carry && ctx->tn == 0 && std::getenv("WM_NO_STEP") == nullptr;
     g.fuse = ctx->host_carry ? 1 : (ctx->dev_carry ? (ctx->step_flow ? 3 : 2) : 0);
     g.sib = (ctx->host_carry && ctx->tn == 0 && ctx->sib_cfg > 0 && std::getenv("WM_NO_SIBLINGS") == nullptr) ? ctx->sib_cfg : 0;
+    BeamDev bd{};
+    if (beam) {
+        if (int rc = wm_beam_begin(ctx, ctx->beam_set, G, g, true, nullptr, P, &bd)) return rc;
+        // the other decodes' graphs stay: what they were compared against waits in beam_keep until the next decode without beams
+        if (!ctx->beam_keep_valid) { ctx->beam_keep_gp = ctx->gp; ctx->beam_keep_ts = ctx->ts; ctx->beam_keep_samp = ctx->samp; ctx->beam_keep_B = ctx->graph_B; ctx->beam_keep_valid = true; }
+        const BeamDev& o = ctx->beam_graph_bd; const TsDev& t = ctx->beam_graph_ts;
+        const bool same_b = ctx->graph_beam && std::memcmp(&g, &ctx->beam_graph_gp, sizeof(GenDev)) == 0 && ts.on == t.on && ts.tb == t.tb && ts.nots == t.nots &&
+                            ts.mit == t.mit && ts.rp == t.rp && ts.rp_pen == t.rp_pen && ts.rp_g == t.rp_g && bd.n == o.n && bd.G == o.G && bd.es == o.es &&
+                            bd.lp_pos == o.lp_pos && bd.rows_cap == o.rows_cap && bd.sh_kv == o.sh_kv;
+        if (!same_b && ctx->graph_beam) { hipGraphExecDestroy(ctx->graph_beam); ctx->graph_beam = nullptr; }
+        ctx->beam_graph_gp = g; ctx->beam_graph_ts = ts; ctx->beam_graph_bd = bd;
+    } else if (ctx->beam_keep_valid) {
+        ctx->gp = ctx->beam_keep_gp; ctx->ts = ctx->beam_keep_ts; ctx->samp = ctx->beam_keep_samp; ctx->graph_B = ctx->beam_keep_B; ctx->beam_keep_valid = false;
+    }
     const bool same = ctx->graph && ctx->graph_B == B && std::memcmp(&g, &ctx->gp, sizeof(GenDev)) == 0 && ts.on == ctx->ts.on &&
                       ts.tb == ctx->ts.tb && ts.nots == ctx->ts.nots && ts.mit == ctx->ts.mit && ts.rp == ctx->ts.rp &&
                       ts.rp_pen == ctx->ts.rp_pen && ts.rp_g == ctx->ts.rp_g &&
                       // the captured launches carry the sampling scalars by value (the stream keys live in device memory, rewritten above)
                       sd.on == ctx->samp.on && (!sd.on || (sd.inv_t == ctx->samp.inv_t && sd.seed_lo == ctx->samp.seed_lo && sd.seed_hi == ctx->samp.seed_hi));
-    if (!same && ctx->graph) { hipGraphExecDestroy(ctx->graph); ctx->graph = nullptr; }
-    if (!same && ctx->graph_base) { hipGraphExecDestroy(ctx->graph_base); ctx->graph_base = nullptr; }
-    ctx->gp = g; ctx->Bdec = B; ctx->ts = ts; ctx->samp = sd;
+    if (!beam && !same && ctx->graph) { hipGraphExecDestroy(ctx->graph); ctx->graph = nullptr; }
+    if (!beam && !same && ctx->graph_base) { hipGraphExecDestroy(ctx->graph_base); ctx->graph_base = nullptr; }
+    ctx->gp = g; ctx->Bdec = B; ctx->ts = ts; ctx->samp = sd; ctx->beam = bd; ctx->beam_clips = beam ? G : 0;
 
     std::vector<int> ids((size_t)B * Tids, gp->pad_token_id), L(B, P), zero(B, 0);
     for (int b = 0; b < B; ++b) for (int i = 0; i < P; ++i) ids[(size_t)b * Tids + i] = gp->prompt[i];
@@ -475,6 +507,10 @@ extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm
         for (int i = std::max(g.begin, 0); i < P; ++i) s0 = ts_fold(s0, gp->prompt[i], ts.tb);
         std::fill(tst.begin(), tst.end(), s0);
         WM_HIP(hipMemcpyAsync(ctx->ts.st, tst.data(), B * sizeof(int4), hipMemcpyHostToDevice, st));
+    }
+    if (beam) {
+        if (int rc = wm_beam_seed_table(ctx, bd)) return rc;
+        if (int rc = wm_beam_expand(ctx, G, nbeam)) return rc;
     }
     WM_HIP(hipStreamSynchronize(st));      // host vectors go out of scope
     ctx->hostflags[0] = 0; ctx->hostflags[1] = 0;
@@ -560,12 +596,13 @@ extern "C" int wm_decode_run(wm_ctx* ctx, int max_iters, int* n_unfinished)
                     ctx->first_done = true;
                 } else {
                     int (*body)(wm_ctx*, int) = ctx->step_flow ? wm_dec_step : wm_dec_iteration;
-                    if (use_graph && ctx->iters >= 2 && !ctx->graph) {   // shapes are warm: capture one steady-state iteration / step
-                        rc = capture_graph(ctx, &ctx->graph, body);
+                    hipGraphExec_t& gx = ctx->beam.on ? ctx->graph_beam : ctx->graph;      // (a beam step has a graph of its own: the others survive it)
+                    if (use_graph && ctx->iters >= 2 && !gx) {   // shapes are warm: capture one steady-state iteration / step
+                        rc = capture_graph(ctx, &gx, body);
                         if (rc) return rc;
-                        ctx->graph_B = ctx->Bdec;
+                        if (!ctx->beam.on) ctx->graph_B = ctx->Bdec;
                     }
-                    if (use_graph && ctx->graph) { WM_HIP(hipGraphLaunch(ctx->graph, st)); ctx->graph_replays++; }
+                    if (use_graph && gx) { WM_HIP(hipGraphLaunch(gx, st)); ctx->graph_replays++; }
                     else { rc = body(ctx, 1); if (rc) return rc; }
                 }
                 ctx->iters++; done++;
@@ -579,7 +616,12 @@ extern "C" int wm_decode_run(wm_ctx* ctx, int max_iters, int* n_unfinished)
     float ms = 0.f;
     WM_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
     ctx->ms_decode += ms;
-    if (n_unfinished) *n_unfinished = left;
+    if (ctx->beam.on && left == 0) {        // every clip is done: the cross K/V goes back to the clips' slots (the state wm_encode left)
+        if (int rc2 = wm_beam_compact(ctx)) return rc2;
+        ctx->beam_done = true;
+        left = 0;
+    }
+    if (n_unfinished) *n_unfinished = ctx->beam.on ? (left + ctx->beam.n - 1) / ctx->beam.n : left;
     return WM_OK;
 }
 
@@ -587,6 +629,11 @@ extern "C" int wm_get_tokens(wm_ctx* ctx, int stream, int32_t* out, int cap, int
 {
     if (!ctx || !out || !n || stream < 0 || stream >= ctx->Bdec) return WM_ERR_ARG;
     WM_HIP(hipSetDevice(ctx->device));
+    if (ctx->beam.on) {                     // a beam decode: the clip's finished hypothesis of rank 0
+        float score = 0.f;
+        if (!ctx->beam_done) { ctx->err = "wm_get_tokens: the beam decode is not finished"; return WM_ERR_STATE; }
+        return wm_get_beam_result(ctx, stream, 0, out, cap, n, &score);
+    }
     int L = 0;
     WM_HIP(hipMemcpyAsync(&L, ctx->L + stream, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     WM_HIP(hipStreamSynchronize(ctx->stream));

@@ -73,6 +73,26 @@ struct SampDev {
     float* val;                         // [Rcap] the winner's perturbed value (wm_sample_rows reads it)
 };
 
+// Beam search on the plain decode path (wm_set_beam; csrc/wm_beam.hip).  Passed by value to the k_beam_* kernels, which stand in for
+// k_select1* / k_select_argmax* / k_accept_vanilla1* in the vanilla branch of wm_dec_iteration while beams are on; nothing else reads it.  Stream
+// s = g * n + j is beam j of clip g.  The buffers belong to wm_beam_state (allocated on first use, sized for max_batch streams).
+struct BeamDev {
+    int on, n, G, es;               // beams per clip, clips, early_stopping (0 False, 1 True, 2 "never")
+    int lp_pos;                     // length_penalty > 0 ("never": the best length is max_length - P)
+    int rows_cap;                   // K/V rows per (kv layer, stream, head) of the shadow buffer (a multiple of 32)
+    float* run;                     // [G * n] running scores
+    float* cval; int* cbeam; int* ctok;                             // [G][2n] the step's ordered candidates
+    float* fscore; int* fset; int* flen; int* fids;                 // finished table: [G][n] score, set, length; [G][n][Tids] ids
+    int* heur; int* cdone;          // [G] early-stop heuristic flag (1 = improvement possible), clip done
+    int* bidx; int* ntok;           // [G * n] source stream / next token of every stream (ntok < 0: the stream does not step)
+    float* lse;                     // [rows][SEL_SP][2] slice partials {max, sum exp} of the raw row
+    float* reg;                     // [rows][SEL_SP][4] slice partials of the processed row {max text, max timestamps, their sum exp, 0}
+    float* sval; int* stok;         // [rows][SEL_SP][2 * WM_BEAM_MAX] slice candidates (accumulated value, token; token -1: none)
+    const float* den;               // [Tids + 2] fl(t ** length_penalty)
+    int* sh_ids; int4* sh_st;       // shadow of the ids rows [G * n][Tids] and of the committed timestamp states
+    bf16_t* sh_kv;                  // shadow of the self K/V: K [nkv][G * n][H][rows_cap][64], then V the same
+};
+
 // state after one more sampled token / the record of a row whose sampled prefix has state `st` (host: wm_decode_begin_ts, device: the select kernels)
 __host__ __device__ __forceinline__ int4 ts_fold(int4 st, int tok, int tb)
 {
@@ -240,6 +260,18 @@ struct wm_ctx {
     bool samp_set_on = false; float samp_set_temp = 1.0f; uint64_t samp_set_seed = 0; std::vector<uint64_t> samp_set_keys;
     SampDev samp{};
     unsigned long long* samp_keys = nullptr;    // [max(maxB, 16)]
+    // wm_set_beam: sticky until cleared.  beam = the current decode's (on = 0: off); its buffers live in beam_state.  While a beam decode owns
+    // ctx->gp / ts / samp, the scalars the other captured graphs (graph, graph_base) were compared against wait in beam_keep: the next decode
+    // without beams takes them back, so those graphs survive a beam call
+    bool beam_set_on = false; wm_beam_params beam_set{};
+    BeamDev beam{};
+    struct wm_beam_state* beam_state = nullptr;
+    int beam_clips = 0;                         // G of the current beam decode
+    bool beam_expanded = false;                 // the cross K/V sits replicated (slot g * n + j); wm_decode_run / wm_decode_invalidate move it back
+    bool beam_done = false;                     // the last decode was a beam decode and all its clips are done (wm_get_beam_result)
+    bool beam_keep_valid = false; GenDev beam_keep_gp{}; TsDev beam_keep_ts{}; SampDev beam_keep_samp{}; int beam_keep_B = 0;
+    hipGraphExec_t graph_beam = nullptr;        // one steady-state beam step; beam_graph_gp / _ts / _bd: what it was captured with
+    GenDev beam_graph_gp{}; TsDev beam_graph_ts{}; BeamDev beam_graph_bd{};
     int Bdec = 0;
     bool began = false, first_done = false;
     long long iters = 0;
@@ -295,6 +327,18 @@ int wm_replay_check(wm_ctx* ctx, const char* who, int B, int Tmax, const int32_t
 // to ctx->amax[out_row0 + r], the decision to ts.forced[out_row0 + r] (rules on), the winner's perturbed value to sd.val[out_row0 + r].  tap = 0: row r
 // is stream r of the decode (record from ts.st[r], prefix ids of stream r); 1: a tap row (record ts.ver[r], prefix ts.rp_ids + r * ts.rp_stride)
 int wm_sample_launch(wm_ctx* ctx, const GenDev& gp, const TsDev& ts, const SampDev& sd, const int* pos, int nrows, int out_row0, int tap);
+// implemented in wm_beam.hip (beam search on the plain decode path; include/wm.h wm_set_beam)
+int wm_beam_check(wm_ctx* ctx, const char* who, const wm_beam_params* bp);      // the parameter checks of wm_set_beam
+// the device form of a beam request over G clips: allocates / grows the state (shadow K/V only with `kv`), uploads the length-penalty table and
+// resets the running scores (init_scores HOST [G * n] or NULL: [0, -1e9, ..] per clip), the finished table (entries of len0 ids, not set) and the
+// flags.  Ends with the stream idle.  wm_beam_seed_table: the table's ids rows start as the streams' ids rows (after the caller has uploaded ctx->ids).
+int wm_beam_begin(wm_ctx* ctx, const wm_beam_params& bp, int G, const GenDev& g, bool kv, const float* init_scores, int len0, BeamDev* out);
+int wm_beam_seed_table(wm_ctx* ctx, const BeamDev& bd);
+// one beam step behind the base pass: select (rows = streams of ctx->logits, lengths ctx->L), bookkeeping, reorder (self K/V only with `kv`)
+int wm_beam_step(wm_ctx* ctx, const GenDev& gp, const TsDev& ts, const BeamDev& bd, bool kv);
+int wm_beam_expand(wm_ctx* ctx, int G, int n);      // cross K/V of clip g: slot g -> slots g * n .. g * n + n - 1; Benc becomes G * n
+int wm_beam_compact(wm_ctx* ctx);                   // and back (slot g * n -> g) when it sits expanded; Benc becomes G again
+void wm_beam_free(wm_ctx* ctx);
 // implemented in wm_align.hip
 void wm_align_free(wm_ctx* ctx);
 // implemented in wm_score.hip

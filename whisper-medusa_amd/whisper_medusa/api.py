@@ -542,11 +542,87 @@ class WhisperMedusaModel:
         """``gp`` for one sampled attempt: the engine's plain decode path with the draw in place of the arg-max."""
         import dataclasses
         g = dataclasses.replace(gp, vanilla=True, accept_mode=ACCEPT_GREEDY, temperature=0.0, sampling_temperature=float(T),
-                                sampling_seed=int(seed), sampling_keys=list(keys))
+                                sampling_seed=int(seed), sampling_keys=list(keys), num_beams=1)     # (HF: a sampled retry runs with one beam)
         for k, v in vars(gp).items():           # (what generate() hangs on the object: _time_precision)
             if k.startswith("_"):
                 setattr(g, k, v)
         return g
+
+    # ---- beam search on the plain decode path (engine: csrc/wm_beam.hip; DESIGN.md §2i) ------------------------------------------------------
+    BEAM_MAX = 8
+
+    def _beam_request(self, kwargs, temperature, logits_processor, stopping_criteria, side: bool) -> Optional[dict]:
+        """The beam side of a generate() call: None for ``num_beams`` 1 / None; without ``vanilla=True`` the reference's exception (model.py:1153-1156);
+        else {n, length_penalty, early_stopping, num_return_sequences} after refusing, each by name, what beam search does not run with."""
+        nb = kwargs.get("num_beams", 1)
+        if nb in (None, 1):
+            return None
+        if not kwargs.get("vanilla"):
+            raise Exception("Beam search is not supported with medusa for now (vanilla=True selects the engine's beam search on the plain "
+                            "decode path)")                                                 # model.py:1153-1156
+        if isinstance(nb, bool) or not isinstance(nb, (int, np.integer)) or int(nb) < 1:
+            raise ValueError(f"`num_beams` has to be an integer strictly greater than 0, but is {nb!r}")        # HF's own check
+        n = int(nb)
+        if n > self.BEAM_MAX:
+            raise NotImplementedError(f"num_beams > {self.BEAM_MAX} is not supported by the engine's beam search (num_beams={n})")
+        if kwargs.get("do_sample") or (not isinstance(temperature, (tuple, list)) and temperature is not None and float(temperature) > 0.0):
+            raise NotImplementedError("do_sample with beams (beam-search multinomial sampling) is not supported; a tuple `temperature` with "
+                                      "sampling_seed= runs the beam search at temperature 0 and the sampled retries with one beam")
+        if self.config.is_tree:
+            raise NotImplementedError("beam search is not supported with a candidate tree (medusa_choices with top-k > 1)")
+        if logits_processor or stopping_criteria:
+            raise NotImplementedError("beam search is not supported on the host processor path (logits_processor= / stopping_criteria=)")
+        if kwargs.get("streamer") is not None:
+            raise NotImplementedError("streamer= is not supported with beam search: a beam's tokens are not final until the search ends")
+        if kwargs.get("chunk_longform") or kwargs.get("sequential_longform"):
+            raise NotImplementedError("chunk_longform / sequential_longform are not supported with beam search (short-form only)")
+        if self._micro_batches not in (None, 1):
+            raise NotImplementedError("the micro-batch pool (set_micro_batches) is not supported with beam search: the beams of a clip share one context")
+        lp = kwargs.get("length_penalty")
+        lp = 1.0 if lp is None else float(lp)
+        if not np.isfinite(lp):
+            raise ValueError(f"`length_penalty` has to be a finite float, but is {lp}")
+        es = kwargs.get("early_stopping")
+        es = False if es is None else es
+        if not (isinstance(es, bool) or es == "never"):
+            raise ValueError(f"`early_stopping` must be a boolean or 'never', but is {es!r}")                  # HF's own check
+        r = kwargs.get("num_return_sequences")
+        r = 1 if r is None else int(r)
+        if not 1 <= r <= n:
+            raise ValueError(f"`num_return_sequences` ({r}) has to be in 1..`num_beams` ({n})")                 # HF's own check
+        if r > 1 and side:
+            raise NotImplementedError("num_return_sequences > 1 is not supported together with the requests that replay the final ids "
+                                      "(token log-probabilities, thresholds, top_logprobs, return_token_timestamps): they score one row per clip")
+        if n > self._max_batch:
+            raise ValueError(f"num_beams={n} needs {n} streams per clip and the context holds max_batch={self._max_batch}: call set_max_batch({n}) "
+                             "or more first")
+        return dict(n=n, length_penalty=lp, early_stopping=es, num_return_sequences=r)
+
+    def _beam_decode(self, eng, feats, gp: GenParams, encoded: bool):
+        """Beam search over the clips ``feats`` in groups of max_batch // num_beams, each group encoded and decoded in turn (B clips need
+        B * num_beams streams).  Returns every clip's best finished hypothesis; all of them — [(ids, score)] * num_beams per clip, best first —
+        stay in ``self._last_beam``.  Ends with ALL clips resident (one more encoder pass when there was more than one group), so that the
+        requests that replay the final ids find the state an ordinary decode leaves."""
+        B, n = feats.shape[0], int(gp.num_beams)
+        per = max(eng.max_batch // n, 1)
+        hyps, stats = [], None
+        for lo in range(0, B, per):
+            hi = min(B, lo + per)
+            if not (encoded and lo == 0 and hi == B):
+                eng.encode(feats if (lo == 0 and hi == B) else feats[lo:hi])
+            eng.decode(gp, hi - lo)
+            hyps += [[eng.beam_result(c, k) for k in range(n)] for c in range(hi - lo)]
+            st = eng.stats()
+            if stats is None:
+                stats = st
+            else:
+                for k in ("ms_decode", "ms_encode", "iterations", "iterations_launched", "tokens_emitted", "graph_replays"):
+                    stats[k] += st[k]
+        if per < B:
+            eng.encode(feats)
+        stats["beam_groups"] = -(-B // per)
+        self._last_beam, self._last_beam_stats = hyps, stats
+        return [h[0][0] for h in hyps]
 
     def _decode_with_fallback(self, eng, feats, gp: GenParams, samp: dict, sc_req: Optional[dict], encoded: bool):
         """HF ``generate_with_fallback``: attempt i decodes the streams still flagged at temps[i] — 0: the configured path, > 0: the sampled plain
@@ -561,11 +637,17 @@ class WhisperMedusaModel:
             raise ValueError(f"sampling_stream_ids needs one id per stream ({B}), got {len(ids)}")
         seqs, infos, kept, att = [None] * B, [None] * B, [0.0] * B, [0] * B
         todo, stats, ms_sc, n_dec = list(range(B)), None, 0.0, 0
+        beams: Dict[int, list] = {}             # clip -> the hypotheses of its beam-search attempt (the temperature-0 attempt of a beam call)
         for i, T in enumerate(samp["temps"]):
             if len(todo) != B or not (encoded or i > 0):
                 eng.encode(feats if len(todo) == B else feats[todo])        # (a rare path: one encoder pass over the flagged streams)
             gp_i = gp if T == 0.0 else self._sampled_gp(gp, T, samp["seed"], [self.sampling_stream_key(ids[b], seeks[b], i) for b in todo])
-            out = eng.decode(gp_i, len(todo))
+            if int(getattr(gp_i, "num_beams", 1) or 1) > 1:      # HF generate_with_fallback: num_beams stays exactly when the attempt does not sample
+                out = self._beam_decode(eng, feats if len(todo) == B else feats[todo], gp_i, True)
+                for j, b in enumerate(todo):
+                    beams[b] = self._last_beam[j]
+            else:
+                out = eng.decode(gp_i, len(todo))
             n_dec += 1
             st = eng.stats()
             if stats is None:
@@ -584,6 +666,7 @@ class WhisperMedusaModel:
                 break
         stats["fallback_decodes"] = n_dec - 1
         self.last_stats = stats
+        self._fallback_beams = beams
         return seqs, (infos if sc_req is not None else None), kept, att, ms_sc
 
     @torch.no_grad()
@@ -630,7 +713,7 @@ class WhisperMedusaModel:
             return_dict_in_generate = pick("return_dict_in_generate", return_dict_in_generate)
             for name in ("max_new_tokens", "max_length", "num_beams", "suppress_tokens", "begin_suppress_tokens",
                          "exponential_decay_length_penalty", "posterior_threshold", "posterior_alpha",
-                         "repetition_penalty", "no_repeat_ngram_size"):
+                         "repetition_penalty", "no_repeat_ngram_size", "num_return_sequences", "early_stopping"):
                 if kwargs.get(name) is None and getattr(gc, name, None) is not None:
                     kwargs[name] = getattr(gc, name)
             if kwargs.get("do_sample") is None and getattr(gc, "do_sample", False):
@@ -639,11 +722,14 @@ class WhisperMedusaModel:
             # (a value equal to the model's own generation config, or to HF's default, is not a request)
             own = getattr(self, "generation_config", None)
             ignored = []
+            beam_call = bool(kwargs.get("vanilla")) and kwargs.get("num_beams") not in (None, 1)
+            if beam_call and kwargs.get("length_penalty") is None and getattr(gc, "length_penalty", None) is not None:
+                kwargs["length_penalty"] = gc.length_penalty        # (read by the engine's beam search, DESIGN.md §2i: not ignored there)
             for name, dflt in (("temperature", 1.0), ("eos_token_id", None), ("pad_token_id", None), ("forced_decoder_ids", None),
                                ("top_k", 50), ("top_p", 1.0),
                                ("length_penalty", 1.0), ("bad_words_ids", None), ("min_length", 0), ("min_new_tokens", None)):
                 v = getattr(gc, name, None)
-                if v is None or v == dflt or (own is not None and v == getattr(own, name, None)):
+                if v is None or v == dflt or (own is not None and v == getattr(own, name, None)) or (beam_call and name == "length_penalty"):
                     continue
                 ignored.append(name)
             if ignored:
@@ -715,8 +801,9 @@ class WhisperMedusaModel:
         if sc_side is not None:
             sc_req = sc_side
         sc_side = sc_side is not None
-        if kwargs.get("num_beams", 1) not in (None, 1):
-            raise Exception("Beam search is not supported with medusa for now")                     # model.py:1153-1156
+        # model.py:1153-1156 raises for num_beams > 1; with vanilla=True the engine runs HF's _beam_search on its plain decode path
+        beam = self._beam_request(kwargs, temperature, logits_processor, stopping_criteria,
+                                  side=sc_req is not None or bool(return_token_timestamps) or kwargs.get("_tt_req") is not None)
         if prefix_allowed_tokens_fn:
             raise NotImplementedError("prefix_allowed_tokens_fn is not supported by the HIP engine")
         tt_req = None
@@ -759,6 +846,8 @@ class WhisperMedusaModel:
         B = input_features.shape[0]
         if B > self._max_batch:
             self.set_max_batch(B)
+        if beam is not None and beam["n"] > self._max_batch:        # (a wrapper may have resized the context since the request was read)
+            raise ValueError(f"num_beams={beam['n']} exceeds max_batch={self._max_batch}: call set_max_batch first")
         gp = self._gen_params(language, task, kwargs.get("exponential_decay_length_penalty"),
                               kwargs.get("max_new_tokens"), kwargs.get("max_length"),
                               # (sampling: attempt 0 of a fallback schedule at temperature 0 is today's call with that tuple — exact-match
@@ -770,6 +859,8 @@ class WhisperMedusaModel:
                               kwargs.get("begin_suppress_tokens"), prompt_ids, timestamps=bool(return_timestamps),
                               repetition_penalty=rep_pen, no_repeat_ngram_size=rep_g)
         gp._time_precision = float(time_precision)
+        if beam is not None:
+            gp.num_beams, gp.length_penalty, gp.early_stopping = beam["n"], beam["length_penalty"], beam["early_stopping"]
         if logits_processor or stopping_criteria:
             gp = lower_processors(gp, logits_processor, stopping_criteria)
         self._last_prompt = list(gp.prompt)
@@ -785,6 +876,8 @@ class WhisperMedusaModel:
                 raise NotImplementedError("sampling (sampling_seed) is not supported on the host processor path (logits_processor= / "
                                           "stopping_criteria= that the engine cannot lower)")
             n_ctx = 1           # the model's own engine: the micro-batch pool is not taught sampling
+        if beam is not None:
+            n_ctx = 1           # ... nor beams: the beams of a clip share one context
         if n_ctx > 1 and B >= 2:
             pool = self._get_pool(n_ctx)
             tsf = None
@@ -816,7 +909,9 @@ class WhisperMedusaModel:
             return self._outputs(seqs, gp, return_dict_in_generate, return_segments)
         # language detection just encoded exactly these clips on this engine (one language group, same order): its encoder output and
         # cross-K/V are still resident — decode from them instead of running the encoder a second time
-        if samp is None and not (kwargs.get("_encoded_batch") == B and getattr(eng, "_B", None) == B):
+        # (beam search over more clips than max_batch // num_beams encodes group by group: _beam_decode)
+        if samp is None and not (kwargs.get("_encoded_batch") == B and getattr(eng, "_B", None) == B) \
+                and not (beam is not None and B * beam["n"] > eng.max_batch):
             eng.encode(feats)                                               # F1 + F2
         if samp is not None:
             seqs, infos, kept, att, ms = self._decode_with_fallback(eng, feats, gp, samp, sc_req, kwargs.get("_encoded_batch") == B and
@@ -838,6 +933,13 @@ class WhisperMedusaModel:
             out = self._outputs(seqs, gp, return_dict_in_generate, return_segments, tt, tt_side, sc, sc_side)
             if sc is None and isinstance(out, dict):
                 out.update(fb)
+            if beam is not None:
+                # the score of a clip whose kept attempt is the beam search; NaN where a sampled retry was kept
+                ss = torch.tensor([self._fallback_beams[b][0][1] if (kept[b] == 0.0 and b in self._fallback_beams) else float("nan") for b in range(B)],
+                                  dtype=torch.float32, device=self.device)
+                self.last_sequences_scores = ss
+                if isinstance(out, dict):
+                    out["sequences_scores"] = ss
             return out
         if streamer is not None or host_crit:
             # one iteration per engine call: the streamer gets the tokens of every iteration (model.py:1034-1035 prompt, :758-759
@@ -874,9 +976,11 @@ class WhisperMedusaModel:
             seqs = [s_[: stop_len[b]] if stop_len[b] is not None else s_ for b, s_ in enumerate(seqs)]
             if streamer is not None:
                 streamer.end()
+        elif beam is not None:
+            seqs = self._beam_decode(eng, feats, gp, True)                  # (encoded above; more than one group encodes again)
         else:
             seqs = eng.decode(gp, B)                                        # F3..F14
-        self.last_stats = eng.stats()
+        self.last_stats = eng.stats() if beam is None else self._last_beam_stats
         sc = None
         if sc_req is not None:
             # scoring first: a skipped clip's row becomes prompt + EOS before anything else looks at it (two replays when token timestamps
@@ -889,6 +993,16 @@ class WhisperMedusaModel:
             rows, ms = self._token_ts_run(eng, seqs, gp, tt_req, 0)
             self.last_stats["ms_token_timestamps"] = ms
             tt = self._token_ts_tensor(rows, seqs, gp)
+        if beam is not None:
+            # HF: `sequences` [B * num_return_sequences, T], clip-major and best first, and `sequences_scores` with return_dict_in_generate
+            r = beam["num_return_sequences"]
+            seqs = [h[k][0] for h in self._last_beam for k in range(r)] if r > 1 else seqs
+            ss = torch.tensor([h[k][1] for h in self._last_beam for k in range(r)], dtype=torch.float32, device=self.device)
+            self.last_sequences_scores = ss
+            out = self._outputs(seqs, gp, return_dict_in_generate, return_segments, tt, tt_side, sc, sc_side)
+            if isinstance(out, dict):
+                out["sequences_scores"] = ss
+            return out
         return self._outputs(seqs, gp, return_dict_in_generate, return_segments, tt, tt_side, sc, sc_side)
 
     # ---- token log-probabilities, no-speech probability, quality gating (engine: csrc/wm_score.hip) --------------------------
@@ -1231,6 +1345,8 @@ class WhisperMedusaModel:
         tts: List[Optional[torch.Tensor]] = [None] * len(langs)
         scs: List[Optional[dict]] = [None] * len(langs)
         ms_tt = ms_sc = 0.0
+        nret = int(kw.get("num_return_sequences") or 1) if (kw.get("vanilla") and kw.get("num_beams") not in (None, 1)) else 1
+        bscores: Dict[int, torch.Tensor] = {}
         for l, idx in groups.items():
             # one group = every clip in its original order: the engine still holds the encoder pass detect_language() ran
             reuse = {"_encoded_batch": len(langs)} if len(groups) == 1 else {}
@@ -1247,13 +1363,18 @@ class WhisperMedusaModel:
                 ms_tt += self.last_stats.get("ms_token_timestamps", 0.0)
             if sreq is not None:
                 ms_sc += self.last_stats.get("ms_token_logprobs", 0.0)
+            if kw.get("vanilla") and kw.get("num_beams") not in (None, 1):
+                bscores.update({i: self.last_sequences_scores[j * nret: (j + 1) * nret] for j, i in enumerate(idx)})
             for j, i in enumerate(idx):
-                rows[i] = out[j]
+                rows[i] = out[j] if nret == 1 else out[j * nret: (j + 1) * nret]
                 plens[i] = len(self._last_prompt)
                 if req is not None:
                     tts[i] = self._last_tt[j]
                 if sreq is not None:
                     scs[i] = {k: v[j] for k, v in self._last_sc.items() if not k.startswith("_")}
+        if nret > 1:            # beam search with num_return_sequences: every clip brings nret rows, clip-major
+            rows = [r_ for r in rows for r_ in r]
+            plens = [p_ for p_ in plens for _ in range(nret)]
         T = max(r.numel() for r in rows)
         t = torch.full((len(rows), T), self.config.pad_token_id, dtype=torch.long, device=self.device)
         for i, r in enumerate(rows):
@@ -1287,8 +1408,13 @@ class WhisperMedusaModel:
             if souter:
                 self._last_sc = sc
                 sc = None
-        return self._wrap_outputs(t, plens, self.config.pad_token_id, self.config.eos_token_id, rdg, rseg, timestamps=rts,
-                                  time_precision=tprec, token_timestamps=tt, scores=sc)
+        out = self._wrap_outputs(t, plens, self.config.pad_token_id, self.config.eos_token_id, rdg, rseg, timestamps=rts,
+                                 time_precision=tprec, token_timestamps=tt, scores=sc)
+        if bscores:
+            self.last_sequences_scores = torch.cat([bscores[i] for i in range(len(langs))])
+            if isinstance(out, dict):
+                out["sequences_scores"] = self.last_sequences_scores
+        return out
 
     def _generate_longform(self, input_features, kw):
         """`chunk_longform=True`: clips longer than 30 s (the reference raises, model.py:1213-1214) are cut into 30 s windows,
@@ -1638,13 +1764,14 @@ class WhisperMedusaModel:
         if mine:
             out = self.generate(input_features[mine], **kw)
             rows = out["sequences"] if isinstance(out, dict) else out
-            local = [(s_, rows[j].tolist()) for j, s_ in enumerate(mine)]
+            nret = rows.shape[0] // len(mine)       # beam search with num_return_sequences: nret rows per clip, clip-major
+            local = [(s_ * nret + k, rows[j * nret + k].tolist()) for j, s_ in enumerate(mine) for k in range(nret)]
             if scoring:     # every rank's per-stream score fields travel like its ids (ragged Python lists)
                 local_sc = [(s_, {k: v[j].tolist() for k, v in self.last_scores.items()}) for j, s_ in enumerate(mine)]
         seqs = _dist.gather_token_lists(local)
         pad = self.config.pad_token_id
         T = max(len(s_) for s_ in seqs)
-        t = torch.full((B, T), pad, dtype=torch.long, device=self.device)
+        t = torch.full((len(seqs), T), pad, dtype=torch.long, device=self.device)
         for i, s_ in enumerate(seqs):
             t[i, : len(s_)] = torch.tensor(s_, dtype=torch.long)
         if not scoring:

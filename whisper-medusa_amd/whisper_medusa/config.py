@@ -15,7 +15,7 @@ from __future__ import annotations
 import json
 import os
 from dataclasses import dataclass, field, asdict
-from typing import List, Optional, Tuple
+from typing import List, Optional, Tuple, Union
 
 HEAD_DIM = 64  # every Whisper size uses 64-wide attention heads
 
@@ -352,6 +352,11 @@ class GenParams:
     sampling_temperature: float = 0.0
     sampling_seed: int = 0
     sampling_keys: Optional[List[int]] = None        # one 64-bit stream key per stream; None: 0 .. B - 1
+
+    # Beam search on the plain decode path (wm_set_beam): num_beams > 1 with vanilla=True runs HF's _beam_search in the engine
+    num_beams: int = 1
+    length_penalty: float = 1.0
+    early_stopping: Union[bool, str] = False         # False, True or "never" (HF generation_config.early_stopping)
 
     @property
     def repeat_rules(self) -> bool:

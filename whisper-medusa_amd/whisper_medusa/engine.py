@@ -57,6 +57,13 @@ class WmSampleParams(C.Structure):
     _fields_ = [("temperature", C.c_float), ("seed", C.c_uint64), ("stream_keys", C.POINTER(C.c_uint64)), ("n_keys", C.c_int32)]
 
 
+class WmBeamParams(C.Structure):
+    _fields_ = [("num_beams", C.c_int32), ("length_penalty", C.c_float), ("early_stopping", C.c_int32)]
+
+
+EARLY_STOPPING_MODES = {False: 0, True: 1, "never": 2}      # wm_beam_params.early_stopping (HF generation_config.early_stopping)
+
+
 class WmAlignParams(C.Structure):
     _fields_ = [("heads", C.POINTER(C.c_int32)), ("n_heads", C.c_int32), ("median_filter_width", C.c_int32), ("time_precision", C.c_float)]
 
@@ -78,7 +85,8 @@ EXPORTS = ["wm_create", "wm_destroy", "wm_last_error", "wm_abi_version", "wm_bui
            "wm_decode_begin_ts", "wm_select_rows",
            "wm_token_timestamps", "wm_get_align_probs", "wm_get_align_matrix", "wm_dtw",
            "wm_score_tokens", "wm_score_rows", "wm_set_repeat_rules", "wm_score_tokens_topk", "wm_topk_rows",
-           "wm_logmel_long", "wm_gather_windows", "wm_set_sampling", "wm_sample_rows"]
+           "wm_logmel_long", "wm_gather_windows", "wm_set_sampling", "wm_sample_rows",
+           "wm_set_beam", "wm_get_beam_result", "wm_beam_rows", "wm_beam_reorder_kv"]
 
 _lib = {}
 
@@ -128,6 +136,11 @@ def load_library(path: Optional[str] = None, act_fp16: bool = False) -> C.CDLL:
     lib.wm_set_sampling.argtypes = [vp, C.POINTER(WmSampleParams)]
     lib.wm_sample_rows.argtypes = [vp, C.POINTER(WmGenParams), C.POINTER(WmTimestampParams), C.POINTER(WmSampleParams), i32, f32p, i32p, i32, i32p,
                                    C.POINTER(C.c_uint64), i32p, f32p, i32p]
+    lib.wm_set_beam.argtypes = [vp, C.POINTER(WmBeamParams)]
+    lib.wm_get_beam_result.argtypes = [vp, i32, i32, i32p, i32, i32p, f32p]
+    lib.wm_beam_rows.argtypes = [vp, C.POINTER(WmGenParams), C.POINTER(WmTimestampParams), C.POINTER(WmBeamParams), i32, i32, f32p, i32p, i32, i32, f32p,
+                                 f32p, i32p, i32p, i32p, i32p, i32p, i32p, f32p, i32p, i32p, i32p, f32p]
+    lib.wm_beam_reorder_kv.argtypes = [vp, i32, i32p, i32]
     lib.wm_decode_run.argtypes = [vp, i32, i32p]
     lib.wm_get_tokens.argtypes = [vp, i32, i32p, i32, i32p]
     lib.wm_get_stats.argtypes = [vp, C.POINTER(WmStats)]
@@ -351,10 +364,84 @@ class Engine:
         else:
             self.set_sampling(T, int(gp.sampling_seed), gp.sampling_keys, B)
 
+    @staticmethod
+    def _beam_struct(num_beams: int, length_penalty: float = 1.0, early_stopping=False) -> WmBeamParams:
+        if isinstance(early_stopping, str):
+            es = early_stopping
+        else:
+            es = bool(early_stopping)
+        if es not in EARLY_STOPPING_MODES:
+            raise ValueError(f"`early_stopping` must be a boolean or 'never', but is {early_stopping!r}")
+        return WmBeamParams(int(num_beams), float(length_penalty), EARLY_STOPPING_MODES[es])
+
+    def set_beam(self, num_beams: Optional[int], length_penalty: float = 1.0, early_stopping=False) -> None:
+        """wm_set_beam: beam search for the following plain decodes (``gp.vanilla``), sticky until cleared (``num_beams`` None or 1).  The
+        decode's B is then the number of clips; it runs B * num_beams streams (<= max_batch)."""
+        if num_beams is None or int(num_beams) == 1:
+            self._check(self.lib.wm_set_beam(self.h, None), "wm_set_beam")
+            return
+        bp = self._beam_struct(num_beams, length_penalty, early_stopping)
+        self._check(self.lib.wm_set_beam(self.h, C.byref(bp)), "wm_set_beam")
+
+    def _set_beam(self, gp: GenParams) -> None:
+        """The context's beam request follows ``gp`` before every decode (wm_set_beam is sticky), like the sampling request."""
+        self.set_beam(int(getattr(gp, "num_beams", 1) or 1), float(getattr(gp, "length_penalty", 1.0)), getattr(gp, "early_stopping", False))
+
+    def beam_result(self, clip: int, rank: int):
+        """wm_get_beam_result: (ids, score) of the finished hypothesis ``rank`` (0 = best) of ``clip`` of the last beam decode."""
+        cap = self.cfg.max_target_positions + 16
+        buf = (C.c_int32 * cap)()
+        n, sc = C.c_int32(0), C.c_float(0)
+        self._check(self.lib.wm_get_beam_result(self.h, int(clip), int(rank), buf, cap, C.byref(n), C.byref(sc)), "wm_get_beam_result")
+        return list(buf[: min(n.value, cap)]), float(sc.value)
+
+    def beam_reorder_kv(self, beam_idx: Sequence[int], length: int) -> None:
+        """wm_beam_reorder_kv: stream s takes over the self K/V rows [0, length) of stream ``beam_idx[s]`` (the reorder of a beam step alone)."""
+        idx = np.ascontiguousarray(beam_idx, dtype=np.int32)
+        self._kv_stamp = object()
+        self._check(self.lib.wm_beam_reorder_kv(self.h, len(idx), idx.ctypes.data_as(C.POINTER(C.c_int32)), int(length)), "wm_beam_reorder_kv")
+
+    def beam_rows(self, gp: GenParams, logits: np.ndarray, prefixes: Sequence[Sequence[int]], num_beams: int, length_penalty: float = 1.0,
+                  early_stopping=False, init_scores=None) -> dict:
+        """Beam-search parity tap (wm_beam_rows): ``logits [S, G, n, V]`` through the select, bookkeeping and ids-reorder kernels, stream
+        g * n + j starting from ``prefixes[g * n + j]`` (one common length) with running score ``init_scores[g * n + j]`` (None: HF's first step).
+        Returns numpy arrays cand_val / cand_beam / cand_tok [S, G, 2n], beam_idx [S, G * n], steps [G], fin_ids [G, n, Tmax], fin_len /
+        fin_score / fin_set [G, n], run_ids [G * n, Tmax], run_len / run_score [G * n]."""
+        x = np.ascontiguousarray(logits, dtype=np.float32)
+        S, G, n, V = x.shape
+        if V != self.cfg.vocab_size or n != int(num_beams) or len(prefixes) != G * n or len({len(p) for p in prefixes}) != 1:
+            raise ValueError("beam_rows: logits must be [S, G, num_beams, vocab] with one prefix per stream, all of one length")
+        plen = len(prefixes[0])
+        Tmax = plen + S
+        pre = np.zeros((G * n, Tmax), dtype=np.int32)
+        for s, p in enumerate(prefixes):
+            pre[s, :plen] = p
+        init = None if init_scores is None else np.ascontiguousarray(init_scores, dtype=np.float32).reshape(G * n)
+        o = dict(cand_val=np.zeros((S, G, 2 * n), np.float32), cand_beam=np.zeros((S, G, 2 * n), np.int32), cand_tok=np.zeros((S, G, 2 * n), np.int32),
+                 beam_idx=np.zeros((S, G * n), np.int32), steps=np.zeros(G, np.int32), fin_ids=np.zeros((G, n, Tmax), np.int32),
+                 fin_len=np.zeros((G, n), np.int32), fin_score=np.zeros((G, n), np.float32), fin_set=np.zeros((G, n), np.int32),
+                 run_ids=np.zeros((G * n, Tmax), np.int32), run_len=np.zeros(G * n, np.int32), run_score=np.zeros(G * n, np.float32))
+        g, _keep = self._gen_struct(gp)
+        self._set_repeat_rules(gp)
+        ts = self._ts_struct(gp) if gp.timestamps else None
+        bp = self._beam_struct(num_beams, length_penalty, early_stopping)
+        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        ip = lambda a: a.ctypes.data_as(i32p)      # noqa: E731
+        fp = lambda a: a.ctypes.data_as(f32p)      # noqa: E731
+        self._kv_stamp = object()
+        self._check(self.lib.wm_beam_rows(self.h, C.byref(g), C.byref(ts) if ts is not None else None, C.byref(bp), G, S, fp(x), ip(pre), Tmax, plen,
+                                          None if init is None else fp(init), fp(o["cand_val"]), ip(o["cand_beam"]), ip(o["cand_tok"]),
+                                          ip(o["beam_idx"]), ip(o["steps"]), ip(o["fin_ids"]), ip(o["fin_len"]), fp(o["fin_score"]), ip(o["fin_set"]),
+                                          ip(o["run_ids"]), ip(o["run_len"]), fp(o["run_score"])), "wm_beam_rows")
+        return o
+
     def decode(self, gp: GenParams, B: int, max_iters: int = 1 << 30, on_iteration=None) -> List[List[int]]:
+        """``gp.num_beams > 1`` (with ``gp.vanilla``): beam search over B clips (B * num_beams streams); the ids returned are every clip's best
+        finished hypothesis, the others are read with ``beam_result``."""
         g, _keep = self._gen_struct(gp)
         self._set_repeat_rules(gp)
         self._set_sampling(gp, B)
+        self._set_beam(gp)
         self._kv_stamp = object()             # the decode loop rewrites the self-attention cache: forward()'s cache handles go stale
         if gp.timestamps:                     # WhisperTimeStampLogitsProcessor in the loop (include/wm.h wm_decode_begin_ts)
             ts = self._ts_struct(gp)
