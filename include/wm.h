@@ -278,6 +278,39 @@ int wm_set_beam(wm_ctx* ctx, const wm_beam_params* bp /* NULL = off */);
  * no beam decode or is not finished. */
 int wm_get_beam_result(wm_ctx* ctx, int clip, int rank, int32_t* out_ids /* HOST */, int cap, int* n, float* score);
 
+/* Sequence bias on the plain decode path (additive to ABI v9; csrc/wm_seq_bias.hip).  Stands in for HF generate(sequence_bias=...) and
+ * generate(bad_words_ids=...) — SequenceBiasLogitsProcessor and NoBadWordsLogitsProcessor (transformers generation/logits_process.py; the second is the
+ * first with every bias -inf), which GenerationMixin._get_logits_processor puts BEFORE every other processor this engine implements; the reference
+ * builds neither (model.py:1168-1207).  An entry is a token sequence of length m (1..WM_SEQ_BIAS_MAX_LEN) with a bias b.  A row with prefix ids[:len]
+ * (decoder prompt included: HF's input_ids) is edited IN PLACE before anything else reads it.  For every token n that is the last id of an entry:
+ *   1. s = +0.0f; a one-token entry (n,) sets s to its bias;
+ *   2. every longer entry ending in n, in the CALLER'S order: when m <= len and ids[len - m + 1 .. len - 1] equals its first m - 1 ids, s = s + b
+ *      (one fp32 add; an entry longer than the context is ignored, so an entry whose m - 1 leading ids would be the whole context — m = len + 1 —
+ *      is ignored too);
+ *   3. x[n] = x[n] + s (one fp32 add).
+ * This is the arithmetic of SequenceBiasLogitsProcessor.__call__ (the bias vector is built in fp32, then scores + bias): the row equals HF's as fp32
+ * values, -inf included.  No atomics touch the row and the order of the sums is fixed: a token's value does not depend on the batch slot, the batch
+ * size or graph replay.  One thread owns one target token (its entries form a GROUP: the one-token entry first, then caller order); a row costs
+ * `groups` read-modify-writes, never a sweep of the vocabulary.
+ * Greedy and sampled plain decodes edit the raw logits row behind the base pass, before the repetition rules, the processors of wm_gen_params and the
+ * timestamp rules (HF's order).  A beam decode (wm_set_beam) edits it AFTER the log-softmax normaliser of the raw row is taken (HF: processors run on
+ * log_softmax(raw)): the engine computes (x + s) - lse where HF computes (x - lse) + s — equal up to one fp32 rounding.
+ * Sticky on the context until cleared (NULL), like wm_set_repeat_rules; read by wm_decode_begin / wm_decode_begin_ts only (the scoring and alignment
+ * replays do not know the bias).  The tables live in device memory allocated once at their maximum size: a captured graph stays valid across tables
+ * with the same number of groups.  WM_ERR_ARG (wm_last_error names the cause) from wm_set_sequence_bias: n outside [1, WM_SEQ_BIAS_MAX], a length
+ * outside [1, WM_SEQ_BIAS_MAX_LEN], an id outside [0, vocab), a bias that is NaN or +inf, two identical entries; from wm_decode_begin*, which know eos
+ * and the path: wm_gen_params.vanilla == 0, a candidate-tree context, a -inf entry of more than one token whose last id is eos — or a one-token one
+ * while the exponential decay is on — (the decay's x + |x| p would turn it into NaN). */
+#define WM_SEQ_BIAS_MAX 1024       /* entries */
+#define WM_SEQ_BIAS_MAX_LEN 16     /* tokens per entry */
+typedef struct wm_seq_bias_params {
+    const int32_t* tokens;   /* HOST, the entries' ids back to back */
+    const int32_t* lens;     /* HOST [n], 1..WM_SEQ_BIAS_MAX_LEN */
+    const float*   bias;     /* HOST [n], finite or -inf */
+    int32_t n;
+} wm_seq_bias_params;
+int wm_set_sequence_bias(wm_ctx* ctx, const wm_seq_bias_params* sb /* NULL = off */);
+
 /* ---- F3..F14 the Medusa decode loop (replaces _medusa_greedy_search, model.py:404-835) ---- */
 int wm_decode_begin(wm_ctx* ctx, const wm_gen_params* gp, int B);
 /* wm_decode_begin with the timestamp rules on (ts != NULL; NULL = wm_decode_begin).  WM_ERR_ARG (wm_last_error says why): a candidate tree
@@ -402,6 +435,15 @@ int wm_beam_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params
                  const float* logits, const int32_t* prefixes, int Tmax, int prefix_len, const float* init_scores /* may be NULL */,
                  float* cand_val, int32_t* cand_beam, int32_t* cand_tok, int32_t* beam_idx, int32_t* out_steps,
                  int32_t* fin_ids, int32_t* fin_len, float* fin_score, int32_t* fin_set, int32_t* run_ids, int32_t* run_len, float* run_score);
+/* Sequence-bias parity tap (HF SequenceBiasLogitsProcessor.__call__ on caller-given rows): the kernel alone, no model.  R rows (HOST float32
+ * [R][vocab]) through k_seq_bias under the entries of sb (checked and grouped as wm_set_sequence_bias does; the context's own sticky table is
+ * untouched and back in place afterwards), row r under prefix prefixes[r][0 .. lens[r]) (HOST int32 [R][Tmax]); out (HOST float32 [R][vocab]) = the
+ * edited rows.  WM_ERR_ARG (wm_last_error names the cause) for a bad sb, R < 1, lens outside [1, Tmax].  Overwrites ctx->logits of the decode state
+ * (begin again afterwards).  Any R >= 1 (worked in groups of 15). */
+int wm_seq_bias_rows(wm_ctx* ctx, const wm_seq_bias_params* sb, int R,
+                     const float* logits /* HOST [R][vocab] */,
+                     const int32_t* prefixes /* HOST [R][Tmax] */, int Tmax, const int32_t* lens /* [R] */,
+                     float* out /* HOST [R][vocab] */);
 /* The K/V reorder of a beam step alone (HF: Cache.reorder_cache(beam_idx) behind _beam_search step g): stream s < B_streams takes over the self
  * K/V rows [0, len) of every kv layer from stream beam_idx[s] (HOST int32 [B_streams], each in [0, B_streams)), through the shadow buffer;
  * beam_idx[s] == s moves nothing.  WM_ERR_ARG for B_streams outside [1, max_batch], len outside [1, n_tgt], an index out of range.  Overwrites

@@ -490,6 +490,9 @@ int wm_beam_step(wm_ctx* ctx, const GenDev& gp, const TsDev& ts, const BeamDev& 
     const int per = (gp.V + SEL_SP - 1) / SEL_SP;
     k_beam_lse<<<dim3(SEL_SP, rows), dim3(256), 0, st>>>(ctx->logits, gp, bd, ctx->done);
     WM_HIP(hipGetLastError());
+    // sequence bias (wm_set_sequence_bias): HF runs its processors on log_softmax(raw), so the normaliser above is the unbiased row's; the rows
+    // are edited in place before the kernels below subtract it.  (The taps run with the context's scalars swapped: ctx->sbias is a decode's.)
+    if (kv && ctx->sbias.on) { if (int rc = wm_seq_bias_launch(ctx, ctx->sbias, ctx->ids, gp.Tids, ctx->L, gp.Tids, rows)) return rc; }
     if (ts.on) {
         k_beam_region<<<dim3(SEL_SP, rows), dim3(256), rp_bytes, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, ts, bd, ctx->done);
         WM_HIP(hipGetLastError());

@@ -1879,6 +1879,12 @@ int wm_dec_iteration(wm_ctx* ctx, int Mper_base)
             const int nb = min(chunk, B - b0);
             int rc = wm_dec_pass(ctx, b0, nb, Mper_base, 0, 0, 0);
             if (rc) return rc;
+            // sequence bias (wm_set_sequence_bias; wm_seq_bias.hip): HF's first processor edits the raw row in place, so everything below — arg-max,
+            // rules, draw — reads the biased row.  Beams apply it themselves, behind their log-softmax normaliser (wm_beam_step)
+            if (ctx->sbias.on && !ctx->beam.on) {
+                rc = wm_seq_bias_launch(ctx, ctx->sbias, ctx->ids + (size_t)b0 * gp.Tids, gp.Tids, ctx->L + b0, gp.Tids, nb);
+                if (rc) return rc;
+            }
             if (ctx->beam.on) {     // beam search (wm_set_beam; wm_beam.hip): select, bookkeeping and reorder stand in for the arg-max and the accept below
                 return wm_beam_step(ctx, gp, ts, ctx->beam, true);
             }

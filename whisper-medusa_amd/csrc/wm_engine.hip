@@ -42,6 +42,7 @@ extern "C" void wm_destroy(wm_ctx* ctx)
     wm_align_free(ctx);
     wm_score_free(ctx);
     wm_beam_free(ctx);
+    wm_seq_bias_free(ctx);
     if (ctx->ev0) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) hipEventDestroy(ctx->ev1);
     if (ctx->own_stream && ctx->stream) hipStreamDestroy(ctx->stream);
@@ -451,6 +452,8 @@ extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm
         sd = wm_sampling_dev(ctx, ctx->samp_set_temp, ctx->samp_set_seed);
         WM_HIP(hipMemcpyAsync(ctx->samp_keys, ctx->samp_set_keys.data(), B * sizeof(uint64_t), hipMemcpyHostToDevice, st));    // (awaited below: wm_proc_setup ends idle)
     }
+    SeqBiasDev sbd{};                      // sequence bias (wm_set_sequence_bias): the sticky table's device form, after what only a decode can check
+    if (int rc = wm_seq_bias_begin(ctx, "wm_decode_begin", gp, &sbd)) return rc;
     GenDev g{}; TsDev ts{};
     if (int rc = wm_proc_setup(ctx, "wm_decode_begin", gp, tsp, &g, &ts)) return rc;
     g.max_length = std::min(gp->max_length, ctx->Tmax);
@@ -470,24 +473,27 @@ extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm
     if (beam) {
         if (int rc = wm_beam_begin(ctx, ctx->beam_set, G, g, true, nullptr, P, &bd)) return rc;
         // the other decodes' graphs stay: what they were compared against waits in beam_keep until the next decode without beams
-        if (!ctx->beam_keep_valid) { ctx->beam_keep_gp = ctx->gp; ctx->beam_keep_ts = ctx->ts; ctx->beam_keep_samp = ctx->samp; ctx->beam_keep_B = ctx->graph_B; ctx->beam_keep_valid = true; }
+        if (!ctx->beam_keep_valid) { ctx->beam_keep_gp = ctx->gp; ctx->beam_keep_ts = ctx->ts; ctx->beam_keep_samp = ctx->samp; ctx->beam_keep_sbias = ctx->sbias; ctx->beam_keep_B = ctx->graph_B; ctx->beam_keep_valid = true; }
         const BeamDev& o = ctx->beam_graph_bd; const TsDev& t = ctx->beam_graph_ts;
         const bool same_b = ctx->graph_beam && std::memcmp(&g, &ctx->beam_graph_gp, sizeof(GenDev)) == 0 && ts.on == t.on && ts.tb == t.tb && ts.nots == t.nots &&
                             ts.mit == t.mit && ts.rp == t.rp && ts.rp_pen == t.rp_pen && ts.rp_g == t.rp_g && bd.n == o.n && bd.G == o.G && bd.es == o.es &&
-                            bd.lp_pos == o.lp_pos && bd.rows_cap == o.rows_cap && bd.sh_kv == o.sh_kv;
+                            bd.lp_pos == o.lp_pos && bd.rows_cap == o.rows_cap && bd.sh_kv == o.sh_kv &&
+                            sbd.on == ctx->beam_graph_sbias.on && sbd.ngroups == ctx->beam_graph_sbias.ngroups;
         if (!same_b && ctx->graph_beam) { hipGraphExecDestroy(ctx->graph_beam); ctx->graph_beam = nullptr; }
-        ctx->beam_graph_gp = g; ctx->beam_graph_ts = ts; ctx->beam_graph_bd = bd;
+        ctx->beam_graph_gp = g; ctx->beam_graph_ts = ts; ctx->beam_graph_bd = bd; ctx->beam_graph_sbias = sbd;
     } else if (ctx->beam_keep_valid) {
-        ctx->gp = ctx->beam_keep_gp; ctx->ts = ctx->beam_keep_ts; ctx->samp = ctx->beam_keep_samp; ctx->graph_B = ctx->beam_keep_B; ctx->beam_keep_valid = false;
+        ctx->gp = ctx->beam_keep_gp; ctx->ts = ctx->beam_keep_ts; ctx->samp = ctx->beam_keep_samp; ctx->sbias = ctx->beam_keep_sbias; ctx->graph_B = ctx->beam_keep_B; ctx->beam_keep_valid = false;
     }
     const bool same = ctx->graph && ctx->graph_B == B && std::memcmp(&g, &ctx->gp, sizeof(GenDev)) == 0 && ts.on == ctx->ts.on &&
                       ts.tb == ctx->ts.tb && ts.nots == ctx->ts.nots && ts.mit == ctx->ts.mit && ts.rp == ctx->ts.rp &&
                       ts.rp_pen == ctx->ts.rp_pen && ts.rp_g == ctx->ts.rp_g &&
                       // the captured launches carry the sampling scalars by value (the stream keys live in device memory, rewritten above)
-                      sd.on == ctx->samp.on && (!sd.on || (sd.inv_t == ctx->samp.inv_t && sd.seed_lo == ctx->samp.seed_lo && sd.seed_hi == ctx->samp.seed_hi));
+                      sd.on == ctx->samp.on && (!sd.on || (sd.inv_t == ctx->samp.inv_t && sd.seed_lo == ctx->samp.seed_lo && sd.seed_hi == ctx->samp.seed_hi)) &&
+                      // ... and whether k_seq_bias is launched, over how many groups (its tables keep their addresses)
+                      sbd.on == ctx->sbias.on && sbd.ngroups == ctx->sbias.ngroups;
     if (!beam && !same && ctx->graph) { hipGraphExecDestroy(ctx->graph); ctx->graph = nullptr; }
     if (!beam && !same && ctx->graph_base) { hipGraphExecDestroy(ctx->graph_base); ctx->graph_base = nullptr; }
-    ctx->gp = g; ctx->Bdec = B; ctx->ts = ts; ctx->samp = sd; ctx->beam = bd; ctx->beam_clips = beam ? G : 0;
+    ctx->gp = g; ctx->Bdec = B; ctx->ts = ts; ctx->samp = sd; ctx->sbias = sbd; ctx->beam = bd; ctx->beam_clips = beam ? G : 0;
 
     std::vector<int> ids((size_t)B * Tids, gp->pad_token_id), L(B, P), zero(B, 0);
     for (int b = 0; b < B; ++b) for (int i = 0; i < P; ++i) ids[(size_t)b * Tids + i] = gp->prompt[i];

@@ -93,6 +93,19 @@ struct BeamDev {
     bf16_t* sh_kv;                  // shadow of the self K/V: K [nkv][G * n][H][rows_cap][64], then V the same
 };
 
+// Sequence bias on the plain decode path (wm_set_sequence_bias; csrc/wm_seq_bias.hip).  Passed by value to k_seq_bias, which edits
+// the fp32 logits rows in place before k_select1* / k_sample1 / the k_beam_* select kernels read them; nothing else reads it.  The tables belong to
+// wm_seq_bias_state (allocated once at their maximum size: the addresses never change); `ngroups` rides in the launch, so it takes part in the
+// decision to reuse a captured graph.  Entries are stored in group order: group g = entries [gstart[g], gstart[g + 1]) that end in token gtok[g].
+struct SeqBiasDev {
+    int on, ngroups;
+    const int* gtok;                // [ngroups] the group's target token (distinct)
+    const int* gstart;              // [ngroups + 1]
+    const int* elen;                // [entries] m
+    const float* ebias;             // [entries]
+    const int* etok;                // [entries][WM_SEQ_BIAS_MAX_LEN] the entry's first m - 1 ids
+};
+
 // state after one more sampled token / the record of a row whose sampled prefix has state `st` (host: wm_decode_begin_ts, device: the select kernels)
 __host__ __device__ __forceinline__ int4 ts_fold(int4 st, int tok, int tb)
 {
@@ -272,6 +285,11 @@ struct wm_ctx {
     bool beam_keep_valid = false; GenDev beam_keep_gp{}; TsDev beam_keep_ts{}; SampDev beam_keep_samp{}; int beam_keep_B = 0;
     hipGraphExec_t graph_beam = nullptr;        // one steady-state beam step; beam_graph_gp / _ts / _bd: what it was captured with
     GenDev beam_graph_gp{}; TsDev beam_graph_ts{}; BeamDev beam_graph_bd{};
+    // wm_set_sequence_bias: sticky until cleared.  seq_bias_state holds the device tables and the host copy of what the caller set; sbias = the
+    // current decode's (on = 0: off).  Like samp it waits in beam_keep_sbias while a beam decode owns the context's scalars; beam_graph_sbias is
+    // what the beam graph was captured with
+    struct wm_seq_bias_state* seq_bias_state = nullptr;
+    SeqBiasDev sbias{}, beam_keep_sbias{}, beam_graph_sbias{};
     int Bdec = 0;
     bool began = false, first_done = false;
     long long iters = 0;
@@ -339,6 +357,13 @@ int wm_beam_step(wm_ctx* ctx, const GenDev& gp, const TsDev& ts, const BeamDev& 
 int wm_beam_expand(wm_ctx* ctx, int G, int n);      // cross K/V of clip g: slot g -> slots g * n .. g * n + n - 1; Benc becomes G * n
 int wm_beam_compact(wm_ctx* ctx);                   // and back (slot g * n -> g) when it sits expanded; Benc becomes G again
 void wm_beam_free(wm_ctx* ctx);
+// implemented in wm_seq_bias.hip (sequence bias on the plain decode path; include/wm.h wm_set_sequence_bias)
+// the device form of the context's sticky table for a decode that begins: on = 0 when none is set.  Checks what only the decode knows (the path, the
+// candidate tree, eos against the -inf entries; errors under `who`).
+int wm_seq_bias_begin(wm_ctx* ctx, const char* who, const wm_gen_params* gp, SeqBiasDev* out);
+// k_seq_bias over `nrows` rows of ctx->logits: row r under the prefix ids + r * ids_stride of lens[r] ids (DEV; clamped to [0, len_cap])
+int wm_seq_bias_launch(wm_ctx* ctx, const SeqBiasDev& sb, const int* ids, int ids_stride, const int* lens, int len_cap, int nrows);
+void wm_seq_bias_free(wm_ctx* ctx);
 // implemented in wm_align.hip
 void wm_align_free(wm_ctx* ctx);
 // implemented in wm_score.hip

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from .config import MedusaConfig, GenParams, ACCEPT_TYPICAL, ACCEPT_GREEDY
-from .engine import Engine
+from .engine import Engine, SEQ_BIAS_MAX as _SEQ_BIAS_MAX, SEQ_BIAS_MAX_LEN as _SEQ_BIAS_MAX_LEN
 from . import weights as _weights
 from . import synth as _synth
 from . import timestamps as _timestamps
@@ -170,6 +170,80 @@ def lower_processors(gp: GenParams, logits_processor, stopping_criteria) -> GenP
             host.append(crit)
             gp._host_criteria = host
     return gp
+
+
+# ---- sequence bias, bad words and hotwords (engine: csrc/wm_seq_bias.hip) -----------------------------------------------------
+def _is_int(t) -> bool:
+    return isinstance(t, (int, np.integer)) and not isinstance(t, bool)
+
+
+def sequence_bias_entries(sequence_bias, vocab_size: int) -> List[Tuple[Tuple[int, ...], float]]:
+    """HF ``generate(sequence_bias=)`` -> [(ids, bias), ..] in the caller's order, under SequenceBiasLogitsProcessor's own validation and
+    messages (transformers generation/logits_process.py ``_validate_arguments`` / ``_prepare_bias_variables``).  Both of HF's forms: a dict
+    ``{tuple(ids): float}`` or a list of ``[ids, float]``, where a repeated sequence keeps its first place and its last value (HF's dict
+    conversion)."""
+    sb = sequence_bias
+    if (not isinstance(sb, dict) and not isinstance(sb, list)) or len(sb) == 0:
+        raise ValueError(f"`sequence_bias` has to be a non-empty dictionary, or non-empty list of lists but is {sb}.")
+    if isinstance(sb, dict):
+        if any(not isinstance(k, tuple) for k in sb):
+            raise ValueError(f"`sequence_bias` has to be a dict with tuples as keys, but is {sb}.")
+        if any(len(k) == 0 or any(not _is_int(t) or t < 0 for t in k) for k in sb):
+            raise ValueError(f"Each key in `sequence_bias` has to be a non-empty tuple of positive integers, but is {sb}.")
+        if any(not isinstance(b, float) for b in sb.values()):
+            raise ValueError(f"`sequence_bias` has to be a dict with floats as values, but is {sb}.")
+        merged = dict(sb)
+    else:
+        def ok(e):
+            return (isinstance(e, (list, tuple)) and len(e) == 2 and isinstance(e[0], list) and len(e[0]) > 0
+                    and all(_is_int(t) and t >= 0 for t in e[0]) and isinstance(e[1], float))
+        if any(not ok(e) for e in sb):
+            raise ValueError(f"Each element in `sequence_bias` has to be a non-empty list of lists of positive integers and float, but is {sb}.")
+        merged = {}
+        for ids, b in sb:
+            merged[tuple(ids)] = b
+    bad = [int(t) for k in merged for t in k if t >= vocab_size]
+    if bad:
+        raise ValueError(f"The model vocabulary size is {vocab_size}, but the following tokens were being biased: {bad}")
+    return [(tuple(int(t) for t in k), float(b)) for k, b in merged.items()]
+
+
+def bad_words_entries(bad_words_ids, eos_token_id: int, vocab_size: int) -> List[Tuple[Tuple[int, ...], float]]:
+    """HF ``generate(bad_words_ids=)`` -> -inf entries, under NoBadWordsLogitsProcessor's validation and messages; ``[eos]`` is filtered out as
+    that processor does."""
+    bw = bad_words_ids
+    if not isinstance(bw, list) or len(bw) == 0:
+        raise ValueError(f"`bad_words_ids` has to be a non-empty list, but is {bw}.")
+    if any(not isinstance(w, list) for w in bw):
+        raise ValueError(f"`bad_words_ids` has to be a list of lists, but is {bw}.")
+    if any(any(not _is_int(t) or t < 0 for t in w) for w in bw):
+        raise ValueError(f"Each list in `bad_words_ids` has to be a list of positive integers, but is {bw}.")
+    kept = [w for w in bw if w != [int(eos_token_id)]]
+    if any(len(w) == 0 for w in kept):
+        raise ValueError(f"Each key in `sequence_bias` has to be a non-empty tuple of positive integers, but is {bw}.")
+    bad = [int(t) for w in kept for t in w if t >= vocab_size]
+    if bad:
+        raise ValueError(f"The model vocabulary size is {vocab_size}, but the following tokens were being biased: {bad}")
+    return list({tuple(int(t) for t in w): float("-inf") for w in kept}.items())
+
+
+def hotword_entries(hotwords, boost: float, tokenizer) -> List[Tuple[Tuple[int, ...], float]]:
+    """The contextual-biasing convenience as a pure function: every word is encoded as ``w`` and as ``" " + w`` (no special tokens) and EVERY
+    prefix t0, t0 t1, .. of each encoding becomes an entry with ``boost`` — each token of the phrase is lifted once its predecessors were
+    emitted.  Duplicates collapse (first place kept).  ``tokenizer``: anything with ``encode(text, add_special_tokens=False) -> ids``."""
+    if isinstance(hotwords, str) or not isinstance(hotwords, (list, tuple)) or len(hotwords) == 0 or any(not isinstance(w, str) or not w for w in hotwords):
+        raise ValueError(f"`hotwords` has to be a non-empty list of non-empty strings, but is {hotwords!r}")
+    if isinstance(boost, bool) or not isinstance(boost, (int, float, np.floating, np.integer)) or not np.isfinite(float(boost)):
+        raise ValueError(f"`hotword_boost` has to be a finite float, but is {boost!r}")
+    if tokenizer is None or not hasattr(tokenizer, "encode"):
+        raise ValueError("`hotwords` needs a tokenizer (tokenizer=, or a model built with its processor): something with encode(text, add_special_tokens=False)")
+    out: Dict[Tuple[int, ...], float] = {}
+    for w in hotwords:
+        for text in (w, " " + w):
+            ids = [int(t) for t in tokenizer.encode(text, add_special_tokens=False)]
+            for k in range(1, len(ids) + 1):
+                out.setdefault(tuple(ids[:k]), float(boost))
+    return list(out.items())
 
 
 def _resolve_checkpoint(name_or_path, revision=None, cache_dir=None, local_files_only=False) -> str:
@@ -598,6 +672,73 @@ class WhisperMedusaModel:
                              "or more first")
         return dict(n=n, length_penalty=lp, early_stopping=es, num_return_sequences=r)
 
+    # ---- sequence bias, bad words, hotwords on the plain decode path (engine: csrc/wm_seq_bias.hip) ----------------------------------
+    def _bias_request(self, kwargs, samp, temperature, logits_processor, stopping_criteria, side: dict):
+        """The bias side of a generate() call: None unless ``sequence_bias=``, ``bad_words_ids=`` or ``hotwords=`` is given; else the entries
+        [(ids, bias), ..] — HF's two processors merged into one table, a sequence given both ways keeps -inf — after HF's own validation and after
+        refusing, each by the argument's name, what the bias does not run with.  ``side``: name -> value of the requests that replay the final ids."""
+        given = [n for n in ("sequence_bias", "bad_words_ids", "hotwords") if kwargs.get(n) is not None]
+        if not given:
+            if kwargs.get("hotword_boost") is not None:
+                raise ValueError("`hotword_boost` needs `hotwords`")
+            return None
+        names = " / ".join(given)
+        cfg = self.config
+        merged: Dict[Tuple[int, ...], float] = {}
+        if kwargs.get("sequence_bias") is not None:
+            merged.update(sequence_bias_entries(kwargs["sequence_bias"], cfg.vocab_size))
+        if kwargs.get("hotwords") is not None:
+            tok = kwargs.get("tokenizer")
+            if tok is None:
+                proc = getattr(self, "processor", None)
+                tok = getattr(proc, "tokenizer", None) or getattr(self, "tokenizer", None)
+            boost = kwargs.get("hotword_boost")
+            for ids, b in hotword_entries(kwargs["hotwords"], 2.0 if boost is None else boost, tok):
+                if any(t < 0 or t >= cfg.vocab_size for t in ids):
+                    raise ValueError(f"The model vocabulary size is {cfg.vocab_size}, but the following tokens were being biased: {list(ids)}")
+                merged.setdefault(ids, b)            # (an explicit sequence_bias entry on the same sequence wins over the convenience)
+        if kwargs.get("bad_words_ids") is not None:
+            for ids, b in bad_words_entries(kwargs["bad_words_ids"], cfg.eos_token_id, cfg.vocab_size):
+                merged[ids] = b                      # -inf wins
+        entries = list(merged.items())
+        plain = bool(kwargs.get("vanilla")) or (samp is not None and not samp["fallback"] and samp["temps"][0] > 0.0)
+        if isinstance(temperature, (tuple, list)):
+            raise NotImplementedError(f"{names} is not supported with a tuple `temperature` (the fallback schedule scores its attempts in a replay "
+                                      "that does not know the bias)")
+        if not plain:
+            raise NotImplementedError(f"{names} runs on the plain decode path only: pass vanilla=True (the Medusa loop's select, candidate and "
+                                      "accept kernels do not know the bias)")
+        if cfg.is_tree:
+            raise NotImplementedError(f"{names} is not supported with a candidate tree (medusa_choices with top-k > 1)")
+        if (logits_processor and any(type(p_).__name__ not in _LOWERABLE_PROCESSORS for p_ in logits_processor)) or \
+                (stopping_criteria and any(type(c_).__name__ not in _LOWERABLE_CRITERIA for c_ in stopping_criteria)):
+            raise NotImplementedError(f"{names} is not supported on the host processor path (logits_processor= / stopping_criteria=); pass HF's "
+                                      "SequenceBiasLogitsProcessor there instead")
+        if kwargs.get("streamer") is not None:
+            raise NotImplementedError(f"{names} is not supported with streamer=")
+        if kwargs.get("chunk_longform"):
+            raise NotImplementedError(f"{names} is not supported with chunk_longform (short-form only)")
+        if kwargs.get("sequential_longform"):
+            raise NotImplementedError(f"{names} is not supported with sequential_longform (short-form only)")
+        if self._micro_batches not in (None, 1):
+            raise NotImplementedError(f"{names} is not supported with the micro-batch pool (set_micro_batches)")
+        for n, v in side.items():
+            if v is not None and v is not False:
+                raise NotImplementedError(f"{names} is not supported together with {n}: it replays the final ids through kernels that do not "
+                                          "know the bias")
+        if len(entries) > _SEQ_BIAS_MAX:
+            raise ValueError(f"{names}: {len(entries)} entries, the engine holds at most {_SEQ_BIAS_MAX} (WM_SEQ_BIAS_MAX)")
+        long = [ids for ids, _ in entries if len(ids) > _SEQ_BIAS_MAX_LEN]
+        if long:
+            raise ValueError(f"{names}: a sequence of {len(long[0])} tokens, the engine holds at most {_SEQ_BIAS_MAX_LEN} per entry (WM_SEQ_BIAS_MAX_LEN)")
+        bad = [ids for ids, b in entries if b == float("-inf") and len(ids) > 1 and ids[-1] == cfg.eos_token_id]
+        if bad:
+            raise ValueError(f"{names}: a banned sequence of more than one token ends in eos_token_id ({list(bad[0])}): under the exponential "
+                             "decay HF's processors turn its -inf into NaN")
+        if any(not np.isfinite(b) and b != float("-inf") for _, b in entries):
+            raise ValueError(f"{names}: a bias has to be finite or -inf")
+        return entries
+
     def _beam_decode(self, eng, feats, gp: GenParams, encoded: bool):
         """Beam search over the clips ``feats`` in groups of max_batch // num_beams, each group encoded and decoded in turn (B clips need
         B * num_beams streams).  Returns every clip's best finished hypothesis; all of them — [(ids, score)] * num_beams per clip, best first —
@@ -743,6 +884,12 @@ class WhisperMedusaModel:
         if samp is None and kwargs.get("do_sample"):
             raise NotImplementedError("sampling (do_sample=True) is not supported with medusa; pass sampling_seed= for the engine's seeded "
                                       "sampling on the plain decode path")      # model.py:1128-1156: no Medusa branch
+        # HF SequenceBiasLogitsProcessor / NoBadWordsLogitsProcessor (the reference's generate() builds neither): one in-place edit of the logits
+        # row on the engine's plain decode path, before every other processor
+        bias = self._bias_request(kwargs, samp, temperature, logits_processor, stopping_criteria,
+                                  dict(return_token_logprobs=return_token_logprobs, top_logprobs=top_logprobs, no_speech_threshold=no_speech_threshold,
+                                       logprob_threshold=logprob_threshold, compression_ratio_threshold=compression_ratio_threshold,
+                                       return_token_timestamps=return_token_timestamps))
         if top_logprobs is not None:
             if isinstance(top_logprobs, bool) or not isinstance(top_logprobs, (int, np.integer)) or not 1 <= int(top_logprobs) <= _scores.TOPK_MAX:
                 raise ValueError(f"`top_logprobs` has to be an integer in 1..{_scores.TOPK_MAX}, but is {top_logprobs!r}")
@@ -861,6 +1008,8 @@ class WhisperMedusaModel:
         gp._time_precision = float(time_precision)
         if beam is not None:
             gp.num_beams, gp.length_penalty, gp.early_stopping = beam["n"], beam["length_penalty"], beam["early_stopping"]
+        if bias is not None:
+            gp.sequence_bias = bias
         if logits_processor or stopping_criteria:
             gp = lower_processors(gp, logits_processor, stopping_criteria)
         self._last_prompt = list(gp.prompt)
@@ -876,8 +1025,8 @@ class WhisperMedusaModel:
                 raise NotImplementedError("sampling (sampling_seed) is not supported on the host processor path (logits_processor= / "
                                           "stopping_criteria= that the engine cannot lower)")
             n_ctx = 1           # the model's own engine: the micro-batch pool is not taught sampling
-        if beam is not None:
-            n_ctx = 1           # ... nor beams: the beams of a clip share one context
+        if beam is not None or bias is not None:
+            n_ctx = 1           # ... nor beams (the beams of a clip share one context), nor the sequence bias
         if n_ctx > 1 and B >= 2:
             pool = self._get_pool(n_ctx)
             tsf = None

@@ -358,6 +358,10 @@ class GenParams:
     length_penalty: float = 1.0
     early_stopping: Union[bool, str] = False         # False, True or "never" (HF generation_config.early_stopping)
 
+    # Sequence bias on the plain decode path (wm_set_sequence_bias): HF SequenceBiasLogitsProcessor / NoBadWordsLogitsProcessor as an
+    # in-place edit of the logits row; [(ids, bias), ..] in the caller's order, a bias finite or -inf.  None / empty = off; needs vanilla=True
+    sequence_bias: Optional[List[Tuple[Tuple[int, ...], float]]] = None
+
     @property
     def repeat_rules(self) -> bool:
         return float(self.repetition_penalty) != 1.0 or int(self.no_repeat_ngram_size) != 0

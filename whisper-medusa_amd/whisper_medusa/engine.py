@@ -64,6 +64,30 @@ class WmBeamParams(C.Structure):
 EARLY_STOPPING_MODES = {False: 0, True: 1, "never": 2}      # wm_beam_params.early_stopping (HF generation_config.early_stopping)
 
 
+class WmSeqBiasParams(C.Structure):
+    _fields_ = [("tokens", C.POINTER(C.c_int32)), ("lens", C.POINTER(C.c_int32)), ("bias", C.POINTER(C.c_float)), ("n", C.c_int32)]
+
+
+SEQ_BIAS_MAX, SEQ_BIAS_MAX_LEN = 1024, 16                  # WM_SEQ_BIAS_MAX / WM_SEQ_BIAS_MAX_LEN (include/wm.h)
+
+
+def seq_bias_groups(entries):
+    """The grouped table wm_set_sequence_bias builds from ``entries`` [(ids, bias), ..] (include/wm.h): one group per target token — the last id —
+    in the order of first appearance, its one-token entry first, then the caller's order.  Returns [(target, [(ids, bias), ..]), ..]: the host-side
+    restatement of the lowering, for tests and tools."""
+    groups, where = [], {}
+    for ids, b in entries:
+        ids = tuple(int(t) for t in ids)
+        g = where.setdefault(ids[-1], len(groups))
+        if g == len(groups):
+            groups.append((ids[-1], []))
+        if len(ids) == 1:
+            groups[g][1].insert(0, (ids, float(b)))
+        else:
+            groups[g][1].append((ids, float(b)))
+    return groups
+
+
 class WmAlignParams(C.Structure):
     _fields_ = [("heads", C.POINTER(C.c_int32)), ("n_heads", C.c_int32), ("median_filter_width", C.c_int32), ("time_precision", C.c_float)]
 
@@ -86,7 +110,8 @@ EXPORTS = ["wm_create", "wm_destroy", "wm_last_error", "wm_abi_version", "wm_bui
            "wm_token_timestamps", "wm_get_align_probs", "wm_get_align_matrix", "wm_dtw",
            "wm_score_tokens", "wm_score_rows", "wm_set_repeat_rules", "wm_score_tokens_topk", "wm_topk_rows",
            "wm_logmel_long", "wm_gather_windows", "wm_set_sampling", "wm_sample_rows",
-           "wm_set_beam", "wm_get_beam_result", "wm_beam_rows", "wm_beam_reorder_kv"]
+           "wm_set_beam", "wm_get_beam_result", "wm_beam_rows", "wm_beam_reorder_kv",
+           "wm_set_sequence_bias", "wm_seq_bias_rows"]
 
 _lib = {}
 
@@ -141,6 +166,8 @@ def load_library(path: Optional[str] = None, act_fp16: bool = False) -> C.CDLL:
     lib.wm_beam_rows.argtypes = [vp, C.POINTER(WmGenParams), C.POINTER(WmTimestampParams), C.POINTER(WmBeamParams), i32, i32, f32p, i32p, i32, i32, f32p,
                                  f32p, i32p, i32p, i32p, i32p, i32p, i32p, f32p, i32p, i32p, i32p, f32p]
     lib.wm_beam_reorder_kv.argtypes = [vp, i32, i32p, i32]
+    lib.wm_set_sequence_bias.argtypes = [vp, C.POINTER(WmSeqBiasParams)]
+    lib.wm_seq_bias_rows.argtypes = [vp, C.POINTER(WmSeqBiasParams), i32, f32p, i32p, i32, i32p, f32p]
     lib.wm_decode_run.argtypes = [vp, i32, i32p]
     lib.wm_get_tokens.argtypes = [vp, i32, i32p, i32, i32p]
     lib.wm_get_stats.argtypes = [vp, C.POINTER(WmStats)]
@@ -387,6 +414,46 @@ class Engine:
         """The context's beam request follows ``gp`` before every decode (wm_set_beam is sticky), like the sampling request."""
         self.set_beam(int(getattr(gp, "num_beams", 1) or 1), float(getattr(gp, "length_penalty", 1.0)), getattr(gp, "early_stopping", False))
 
+    @staticmethod
+    def _seq_bias_struct(entries):
+        """[(ids, bias), ..] -> (wm_seq_bias_params, the arrays it points into).  The checks are the library's (wm_set_sequence_bias)."""
+        ent = [(tuple(int(t) for t in ids), float(b)) for ids, b in entries]
+        tok = np.ascontiguousarray([t for ids, _ in ent for t in ids] or [0], dtype=np.int32)
+        lens = np.ascontiguousarray([len(ids) for ids, _ in ent] or [0], dtype=np.int32)
+        bias = np.ascontiguousarray([b for _, b in ent] or [0.0], dtype=np.float32)
+        i32p = C.POINTER(C.c_int32)
+        sb = WmSeqBiasParams(tok.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), bias.ctypes.data_as(C.POINTER(C.c_float)), len(ent))
+        return sb, (tok, lens, bias)
+
+    def set_sequence_bias(self, entries) -> None:
+        """wm_set_sequence_bias: HF's SequenceBiasLogitsProcessor / NoBadWordsLogitsProcessor for the following plain decodes (``gp.vanilla``),
+        sticky until cleared (``entries`` None).  ``entries``: [(ids, bias), ..] in the caller's order, a bias finite or -inf."""
+        if entries is None:
+            self._check(self.lib.wm_set_sequence_bias(self.h, None), "wm_set_sequence_bias")
+            return
+        sb, _keep = self._seq_bias_struct(entries)
+        self._check(self.lib.wm_set_sequence_bias(self.h, C.byref(sb)), "wm_set_sequence_bias")
+
+    def _set_sequence_bias(self, gp: GenParams) -> None:
+        """The context's sequence bias follows ``gp`` before every decode (wm_set_sequence_bias is sticky), like the repetition rules."""
+        self.set_sequence_bias(getattr(gp, "sequence_bias", None) or None)
+
+    def seq_bias_rows(self, entries, logits: np.ndarray, prefixes: Sequence[Sequence[int]]) -> np.ndarray:
+        """Sequence-bias parity tap (wm_seq_bias_rows): rows ``logits [R, V]``, row r under ``prefixes[r]``, through k_seq_bias alone.  Returns the
+        edited rows, numpy float32 [R, V]."""
+        x = np.ascontiguousarray(logits, dtype=np.float32)
+        R, V = x.shape
+        if V != self.cfg.vocab_size or len(prefixes) != R:
+            raise ValueError("seq_bias_rows: logits must be [R, vocab] with one prefix per row")
+        pre, lens, Tmax, _ = self._pack_ids(prefixes)
+        out = np.zeros_like(x)
+        sb, _keep = self._seq_bias_struct(entries)
+        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        self._kv_stamp = object()
+        self._check(self.lib.wm_seq_bias_rows(self.h, C.byref(sb), R, x.ctypes.data_as(f32p), pre.ctypes.data_as(i32p), Tmax, lens.ctypes.data_as(i32p),
+                                              out.ctypes.data_as(f32p)), "wm_seq_bias_rows")
+        return out
+
     def beam_result(self, clip: int, rank: int):
         """wm_get_beam_result: (ids, score) of the finished hypothesis ``rank`` (0 = best) of ``clip`` of the last beam decode."""
         cap = self.cfg.max_target_positions + 16
@@ -442,6 +509,7 @@ class Engine:
         self._set_repeat_rules(gp)
         self._set_sampling(gp, B)
         self._set_beam(gp)
+        self._set_sequence_bias(gp)
         self._kv_stamp = object()             # the decode loop rewrites the self-attention cache: forward()'s cache handles go stale
         if gp.timestamps:                     # WhisperTimeStampLogitsProcessor in the loop (include/wm.h wm_decode_begin_ts)
             ts = self._ts_struct(gp)
