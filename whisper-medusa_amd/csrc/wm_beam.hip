@@ -27,7 +27,7 @@ struct wm_beam_state {
 
 void wm_beam_free(wm_ctx* ctx)
 {
-    if (ctx->graph_beam) { (void)hipGraphExecDestroy(ctx->graph_beam); ctx->graph_beam = nullptr; }
+    ctx->graphs_beam.drop();                // its graph names the shadow K/V freed below
     delete ctx->beam_state;
     ctx->beam_state = nullptr;
 }

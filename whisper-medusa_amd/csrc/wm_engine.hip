@@ -28,8 +28,7 @@ extern "C" void wm_destroy(wm_ctx* ctx)
     if (!ctx) return;
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
-    if (ctx->graph) hipGraphExecDestroy(ctx->graph);
-    if (ctx->graph_base) hipGraphExecDestroy(ctx->graph_base);
+    ctx->graphs_plain.drop(); ctx->graphs_beam.drop();       // (before the buffers they name are freed)
     if (ctx->hostflags) hipHostFree(ctx->hostflags);
     void* bufs[] = {ctx->feats_own, ctx->clipmax, ctx->A1, ctx->a1, ctx->A2, ctx->eh, ctx->exn, ctx->eq, ctx->ek, ctx->evt, ctx->eff,
                     ctx->enc_out, ctx->kx, ctx->vx, ctx->kc, ctx->vc, ctx->h, ctx->hblk, ctx->hf, ctx->qbuf, ctx->xbuf, ctx->fbuf,
@@ -372,10 +371,7 @@ void wm_decode_invalidate(wm_ctx* ctx, bool drop_graphs)
 {
     ctx->began = false; ctx->use_done = false; ctx->host_carry = false; ctx->dev_carry = false; ctx->step_flow = false;
     if (ctx->beam_expanded) (void)wm_beam_compact(ctx);         // a beam decode that was left unfinished: the cross K/V goes back to its clips' slots
-    if (drop_graphs && ctx->graph_beam) { (void)hipGraphExecDestroy(ctx->graph_beam); ctx->graph_beam = nullptr; }
-    if (drop_graphs) ctx->beam_keep_valid = false;
-    if (drop_graphs && ctx->graph) { (void)hipGraphExecDestroy(ctx->graph); ctx->graph = nullptr; }
-    if (drop_graphs && ctx->graph_base) { (void)hipGraphExecDestroy(ctx->graph_base); ctx->graph_base = nullptr; }
+    if (drop_graphs) { ctx->graphs_plain.drop(); ctx->graphs_beam.drop(); }
 }
 
 // HF RepetitionPenaltyLogitsProcessor / NoRepeatNGramLogitsProcessor inside the select and scoring kernels (include/wm.h)
@@ -443,58 +439,39 @@ extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm
         ctx->err = "wm_decode_begin: prompt length must be in [1, n_tgt - K - 2]"; return WM_ERR_ARG; }
     if (!gp->vanilla && gp->accept_mode == WM_ACCEPT_TYPICAL && !(gp->temperature > 0.f)) {
         ctx->err = "wm_decode_begin: typical acceptance needs temperature > 0"; return WM_ERR_ARG; }
-    hipStream_t st = ctx->stream;
     SampDev sd = ctx->samp; sd.on = 0;
     if (ctx->samp_set_on) {
         if (!gp->vanilla) { ctx->err = "wm_decode_begin: sampling runs on the plain decode path only (wm_gen_params.vanilla = 1)"; return WM_ERR_ARG; }
         if (ctx->tn) { ctx->err = "wm_decode_begin: sampling is not supported with a candidate tree (medusa_choices with top-k > 1)"; return WM_ERR_ARG; }
         if ((int)ctx->samp_set_keys.size() != B) { ctx->err = "wm_decode_begin: wm_sample_params.n_keys must equal B"; return WM_ERR_ARG; }
         sd = wm_sampling_dev(ctx, ctx->samp_set_temp, ctx->samp_set_seed);
-        WM_HIP(hipMemcpyAsync(ctx->samp_keys, ctx->samp_set_keys.data(), B * sizeof(uint64_t), hipMemcpyHostToDevice, st));    // (awaited below: wm_proc_setup ends idle)
     }
     SeqBiasDev sbd{};                      // sequence bias (wm_set_sequence_bias): the sticky table's device form, after what only a decode can check
     if (int rc = wm_seq_bias_begin(ctx, "wm_decode_begin", gp, &sbd)) return rc;
+    // the processors' tables and the scalars of this decode
     GenDev g{}; TsDev ts{};
     if (int rc = wm_proc_setup(ctx, "wm_decode_begin", gp, tsp, &g, &ts)) return rc;
     g.max_length = std::min(gp->max_length, ctx->Tmax);
     g.hard_max_length = std::min(gp->hard_max_length, ctx->Tmax);
     g.inv_temp = (gp->accept_mode == WM_ACCEPT_TYPICAL && gp->temperature > 0.f) ? 1.0f / gp->temperature : 1.0f;
-    g.force_accept = gp->force_accept;
-    g.accept_mode = gp->accept_mode; g.vanilla = gp->vanilla;
-    ctx->fuse = std::getenv("WM_NO_CARRY") == nullptr;
-    ctx->host_carry = ctx->fuse && B == 1 && !gp->vanilla;
-    ctx->dev_carry = ctx->fuse && B > 1 && !gp->vanilla;
+    g.force_accept = gp->force_accept; g.accept_mode = gp->accept_mode; g.vanilla = gp->vanilla;
+    const bool fuse = std::getenv("WM_NO_CARRY") == nullptr;
+    const bool host_carry = fuse && B == 1 && !gp->vanilla, dev_carry = fuse && B > 1 && !gp->vanilla;
     // several streams with the per-stream carry, chain candidates: the merged-step schedule (a stream that needs a base pass gets its one
     // row inside the other streams' verify pass: wm_dec_step).  WM_NO_STEP=1: the lock-step iteration (base pass + verify pass for everybody).
-    ctx->step_flow = ctx->dev_carry && ctx->tn == 0 && std::getenv("WM_NO_STEP") == nullptr;
-    g.fuse = ctx->host_carry ? 1 : (ctx->dev_carry ? (ctx->step_flow ? 3 : 2) : 0);
-    g.sib = (ctx->host_carry && ctx->tn == 0 && ctx->sib_cfg > 0 && std::getenv("WM_NO_SIBLINGS") == nullptr) ? ctx->sib_cfg : 0;
+    const bool step_flow = dev_carry && ctx->tn == 0 && std::getenv("WM_NO_STEP") == nullptr;
+    g.fuse = host_carry ? 1 : (dev_carry ? (step_flow ? 3 : 2) : 0);
+    g.sib = (host_carry && ctx->tn == 0 && ctx->sib_cfg > 0 && std::getenv("WM_NO_SIBLINGS") == nullptr) ? ctx->sib_cfg : 0;
     BeamDev bd{};
-    if (beam) {
-        if (int rc = wm_beam_begin(ctx, ctx->beam_set, G, g, true, nullptr, P, &bd)) return rc;
-        // the other decodes' graphs stay: what they were compared against waits in beam_keep until the next decode without beams
-        if (!ctx->beam_keep_valid) { ctx->beam_keep_gp = ctx->gp; ctx->beam_keep_ts = ctx->ts; ctx->beam_keep_samp = ctx->samp; ctx->beam_keep_sbias = ctx->sbias; ctx->beam_keep_B = ctx->graph_B; ctx->beam_keep_valid = true; }
-        const BeamDev& o = ctx->beam_graph_bd; const TsDev& t = ctx->beam_graph_ts;
-        const bool same_b = ctx->graph_beam && std::memcmp(&g, &ctx->beam_graph_gp, sizeof(GenDev)) == 0 && ts.on == t.on && ts.tb == t.tb && ts.nots == t.nots &&
-                            ts.mit == t.mit && ts.rp == t.rp && ts.rp_pen == t.rp_pen && ts.rp_g == t.rp_g && bd.n == o.n && bd.G == o.G && bd.es == o.es &&
-                            bd.lp_pos == o.lp_pos && bd.rows_cap == o.rows_cap && bd.sh_kv == o.sh_kv &&
-                            sbd.on == ctx->beam_graph_sbias.on && sbd.ngroups == ctx->beam_graph_sbias.ngroups;
-        if (!same_b && ctx->graph_beam) { hipGraphExecDestroy(ctx->graph_beam); ctx->graph_beam = nullptr; }
-        ctx->beam_graph_gp = g; ctx->beam_graph_ts = ts; ctx->beam_graph_bd = bd; ctx->beam_graph_sbias = sbd;
-    } else if (ctx->beam_keep_valid) {
-        ctx->gp = ctx->beam_keep_gp; ctx->ts = ctx->beam_keep_ts; ctx->samp = ctx->beam_keep_samp; ctx->sbias = ctx->beam_keep_sbias; ctx->graph_B = ctx->beam_keep_B; ctx->beam_keep_valid = false;
-    }
-    const bool same = ctx->graph && ctx->graph_B == B && std::memcmp(&g, &ctx->gp, sizeof(GenDev)) == 0 && ts.on == ctx->ts.on &&
-                      ts.tb == ctx->ts.tb && ts.nots == ctx->ts.nots && ts.mit == ctx->ts.mit && ts.rp == ctx->ts.rp &&
-                      ts.rp_pen == ctx->ts.rp_pen && ts.rp_g == ctx->ts.rp_g &&
-                      // the captured launches carry the sampling scalars by value (the stream keys live in device memory, rewritten above)
-                      sd.on == ctx->samp.on && (!sd.on || (sd.inv_t == ctx->samp.inv_t && sd.seed_lo == ctx->samp.seed_lo && sd.seed_hi == ctx->samp.seed_hi)) &&
-                      // ... and whether k_seq_bias is launched, over how many groups (its tables keep their addresses)
-                      sbd.on == ctx->sbias.on && sbd.ngroups == ctx->sbias.ngroups;
-    if (!beam && !same && ctx->graph) { hipGraphExecDestroy(ctx->graph); ctx->graph = nullptr; }
-    if (!beam && !same && ctx->graph_base) { hipGraphExecDestroy(ctx->graph_base); ctx->graph_base = nullptr; }
-    ctx->gp = g; ctx->Bdec = B; ctx->ts = ts; ctx->samp = sd; ctx->sbias = sbd; ctx->beam = bd; ctx->beam_clips = beam ? G : 0;
-
+    if (beam) { if (int rc = wm_beam_begin(ctx, ctx->beam_set, G, g, true, nullptr, P, &bd)) return rc; }
+    // the captured graphs: this decode's slot keeps its graphs when they were captured with the same key; the other slot is not touched
+    const DecGraphKey key = wm_dec_graph_key(g, B, ts, sd, sbd, bd);
+    DecGraphSlot& slot = beam ? ctx->graphs_beam : ctx->graphs_plain;
+    if (!(key == slot.key)) { slot.drop(); slot.key = key; }
+    ctx->fuse = fuse; ctx->host_carry = host_carry; ctx->dev_carry = dev_carry; ctx->step_flow = step_flow;
+    ctx->gp = g; ctx->Bdec = B; ctx->ts = ts; ctx->samp = sd; ctx->sbias = sbd; ctx->beam = bd; ctx->beam_clips = beam ? G : 0;       // (the context's scalars are this decode's from here on)
+    hipStream_t st = ctx->stream;           // uploads
+    if (sd.on) WM_HIP(hipMemcpyAsync(ctx->samp_keys, ctx->samp_set_keys.data(), B * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     std::vector<int> ids((size_t)B * Tids, gp->pad_token_id), L(B, P), zero(B, 0);
     for (int b = 0; b < B; ++b) for (int i = 0; i < P; ++i) ids[(size_t)b * Tids + i] = gp->prompt[i];
     WM_HIP(hipMemcpyAsync(ctx->ids, ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice, st));
@@ -559,6 +536,7 @@ extern "C" int wm_decode_run(wm_ctx* ctx, int max_iters, int* n_unfinished)
     if (!ctx->began) { ctx->err = "wm_decode_run: call wm_decode_begin first"; return WM_ERR_STATE; }
     hipStream_t st = ctx->stream;
     const bool use_graph = std::getenv("WM_NO_GRAPH") == nullptr;
+    DecGraphSlot& gs = ctx->beam.on ? ctx->graphs_beam : ctx->graphs_plain;       // the slot wm_decode_begin_ts keyed for this decode
     int left = 0, done = 0;
     int rc = count_unfinished(ctx, &left);
     if (rc) return rc;
@@ -577,12 +555,12 @@ extern "C" int wm_decode_run(wm_ctx* ctx, int max_iters, int* n_unfinished)
                 const bool need_base = ctx->hostflags[0] == 0;
                 const bool warm = ctx->iters >= 2;
                 if (need_base) {
-                    if (use_graph && warm && !ctx->graph_base) { rc = capture_graph(ctx, &ctx->graph_base, wm_dec_iter_base); if (rc) return rc; }
-                    if (use_graph && ctx->graph_base) WM_HIP(hipGraphLaunch(ctx->graph_base, st));
+                    if (use_graph && warm && !gs.base) { rc = capture_graph(ctx, &gs.base, wm_dec_iter_base); if (rc) return rc; }
+                    if (use_graph && gs.base) WM_HIP(hipGraphLaunch(gs.base, st));
                     else { rc = wm_dec_iter_base(ctx, 1); if (rc) return rc; }
                 }
-                if (use_graph && warm && !ctx->graph) { rc = capture_graph(ctx, &ctx->graph, wm_dec_iter_rest); if (rc) return rc; ctx->graph_B = ctx->Bdec; }
-                if (use_graph && ctx->graph) { WM_HIP(hipGraphLaunch(ctx->graph, st)); ctx->graph_replays++; }
+                if (use_graph && warm && !gs.step) { rc = capture_graph(ctx, &gs.step, wm_dec_iter_rest); if (rc) return rc; }
+                if (use_graph && gs.step) { WM_HIP(hipGraphLaunch(gs.step, st)); ctx->graph_replays++; }
                 else { rc = wm_dec_iter_rest(ctx, 1); if (rc) return rc; }
             }
             WM_HIP(hipStreamSynchronize(st));
@@ -602,13 +580,9 @@ extern "C" int wm_decode_run(wm_ctx* ctx, int max_iters, int* n_unfinished)
                     ctx->first_done = true;
                 } else {
                     int (*body)(wm_ctx*, int) = ctx->step_flow ? wm_dec_step : wm_dec_iteration;
-                    hipGraphExec_t& gx = ctx->beam.on ? ctx->graph_beam : ctx->graph;      // (a beam step has a graph of its own: the others survive it)
-                    if (use_graph && ctx->iters >= 2 && !gx) {   // shapes are warm: capture one steady-state iteration / step
-                        rc = capture_graph(ctx, &gx, body);
-                        if (rc) return rc;
-                        if (!ctx->beam.on) ctx->graph_B = ctx->Bdec;
-                    }
-                    if (use_graph && gx) { WM_HIP(hipGraphLaunch(gx, st)); ctx->graph_replays++; }
+                    // shapes are warm: capture one steady-state iteration / step
+                    if (use_graph && ctx->iters >= 2 && !gs.step) { rc = capture_graph(ctx, &gs.step, body); if (rc) return rc; }
+                    if (use_graph && gs.step) { WM_HIP(hipGraphLaunch(gs.step, st)); ctx->graph_replays++; }
                     else { rc = body(ctx, 1); if (rc) return rc; }
                 }
                 ctx->iters++; done++;
@@ -844,7 +818,7 @@ extern "C" int wm_forward_logits(wm_ctx* ctx, int B, const int32_t* tokens, int 
     GenDev g = ctx->gp;
     g.K = K; g.V = V; g.Vpad = ctx->Vpad; g.Tids = Tids; g.vanilla = 0;
     ctx->gp = g;
-    wm_decode_invalidate(ctx, true);
+    wm_decode_invalidate(ctx, true);        // (drops both graph slots, as ever)
     std::vector<float> rowbuf((size_t)nout * ctx->Vpad);
     for (int b = 0; b < B; ++b) {
         std::vector<int> v(T);

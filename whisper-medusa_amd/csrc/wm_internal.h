@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cstring>
 #include <string>
 #include <vector>
 #include "../../include/wm.h"
@@ -64,7 +65,7 @@ struct TsDev {
 static inline bool wm_rules_on(const TsDev& t) { return t.on || t.rp; }
 
 // Seeded sampling on the plain decode path (wm_set_sampling).  Passed by value to k_sample1 / k_sample_fin, which stand in for
-// k_select1* / k_select_argmax* in the vanilla branch of wm_dec_iteration while sampling is on; nothing else reads it.
+// k_select1* / k_select_argmax* in the vanilla branch of wm_dec_iteration while sampling is on; nothing else reads it (the scalars: DecGraphKey).
 struct SampDev {
     int on; float inv_t;                // fl(1 / temperature): the sampling temperature (GenDev.inv_temp stays typical acceptance's)
     unsigned seed_lo, seed_hi;          // Philox key
@@ -95,8 +96,8 @@ struct BeamDev {
 
 // Sequence bias on the plain decode path (wm_set_sequence_bias; csrc/wm_seq_bias.hip).  Passed by value to k_seq_bias, which edits
 // the fp32 logits rows in place before k_select1* / k_sample1 / the k_beam_* select kernels read them; nothing else reads it.  The tables belong to
-// wm_seq_bias_state (allocated once at their maximum size: the addresses never change); `ngroups` rides in the launch, so it takes part in the
-// decision to reuse a captured graph.  Entries are stored in group order: group g = entries [gstart[g], gstart[g + 1]) that end in token gtok[g].
+// wm_seq_bias_state (allocated once at their maximum size: the addresses never change); `on` and `ngroups` ride in the launch, so they are part of
+// DecGraphKey (below).  Entries are stored in group order: group g = entries [gstart[g], gstart[g + 1]) that end in token gtok[g].
 struct SeqBiasDev {
     int on, ngroups;
     const int* gtok;                // [ngroups] the group's target token (distinct)
@@ -104,6 +105,36 @@ struct SeqBiasDev {
     const int* elen;                // [entries] m
     const float* ebias;             // [entries]
     const int* etok;                // [entries][WM_SEQ_BIAS_MAX_LEN] the entry's first m - 1 ids
+};
+
+// What a captured decode graph was captured with: every scalar its launches carry by value.  wm_decode_begin_ts keeps the graphs of a slot (below)
+// exactly when the decode's key equals the slot's.  A new scalar passed by value to a captured launch is added HERE (the struct and
+// wm_dec_graph_key) and nowhere else.  Buffer pointers stay out: every buffer the launches name is allocated once per context, at its max_batch size,
+// and never moves — except the beam shadow K/V, which grows with the call (wm_beam_begin).  The equality is a memcmp: no padding (asserted).
+struct DecGraphKey {
+    const void* sh_kv; int beam_on, n, G, es, lp_pos, rows_cap;         // BeamDev (all zero without beams)
+    GenDev g; int B;                                                    // B: streams (beams: clips x beams)
+    int ts_on, tb, nots, mit, rp; float rp_pen; int rp_g;               // TsDev
+    int samp_on; float inv_t; unsigned seed_lo, seed_hi;                // SampDev (all zero while sampling is off)
+    int sb_on, ngroups, pad_;                                           // SeqBiasDev (pad_: an even number of words, no tail padding)
+};
+static_assert(sizeof(GenDev) == 19 * 4 && sizeof(DecGraphKey) == sizeof(void*) + sizeof(GenDev) + 21 * 4, "DecGraphKey must have no padding");
+static inline bool operator==(const DecGraphKey& a, const DecGraphKey& b) { return std::memcmp(&a, &b, sizeof(DecGraphKey)) == 0; }
+static inline DecGraphKey wm_dec_graph_key(const GenDev& g, int B, const TsDev& ts, const SampDev& sd, const SeqBiasDev& sbd, const BeamDev& bd)
+{
+    DecGraphKey k{};
+    k.g = g; k.B = B; k.sb_on = sbd.on; k.ngroups = sbd.ngroups;
+    k.ts_on = ts.on; k.tb = ts.tb; k.nots = ts.nots; k.mit = ts.mit; k.rp = ts.rp; k.rp_pen = ts.rp_pen; k.rp_g = ts.rp_g;
+    if (sd.on) { k.samp_on = sd.on; k.inv_t = sd.inv_t; k.seed_lo = sd.seed_lo; k.seed_hi = sd.seed_hi; }
+    if (bd.on) { k.beam_on = bd.on; k.n = bd.n; k.G = bd.G; k.es = bd.es; k.lp_pos = bd.lp_pos; k.rows_cap = bd.rows_cap; k.sh_kv = bd.sh_kv; }
+    return k;
+}
+// The captured graphs of one kind of decode and their key.  step: one steady-state iteration / merged step / beam step (single-stream carry path:
+// what follows the base pass); base: that path's base pass.  drop() is the only place a graph is destroyed (hidden: it adds no exported symbol)
+struct DecGraphSlot {
+    DecGraphKey key{};
+    hipGraphExec_t step = nullptr, base = nullptr;
+    __attribute__((visibility("hidden"))) void drop() { for (hipGraphExec_t* x : {&step, &base}) if (*x) { (void)hipGraphExecDestroy(*x); *x = nullptr; } }
 };
 
 // state after one more sampled token / the record of a row whose sampled prefix has state `st` (host: wm_decode_begin_ts, device: the select kernels)
@@ -245,7 +276,6 @@ struct wm_ctx {
     float* rs_table = nullptr; int rs_og = 0, rs_nw = 0, rs_width = 0;     // cached resampling filter bank [taps][phases]
     bool dev_carry = false;                                                 // several streams: per-stream carry flags on the device
     int *hostflags = nullptr, *hostflags_dev = nullptr;                     // host-mapped {carry, finished}
-    hipGraphExec_t graph_base = nullptr;
     bf16_t *xbuf = nullptr, *fbuf = nullptr, *ybuf = nullptr;
     // LayerNorm fold (round 6): operand gamma o x of the next LayerNorm-fed GEMM (hi / lo planes, written by the launch that produced x), the
     // rows' statistics partials [d / 16 tiles][Rcap rows] and the fold vectors of every decoder layer; WM_LN_FOLD=0 keeps the LayerNorm launches
@@ -265,37 +295,30 @@ struct wm_ctx {
     int* tap_tok = nullptr;
     int* done = nullptr;                   // [0] = all streams finished, [1] = number of finished streams
     bool use_done = false;
+    // gp / ts / samp / sbias / beam: the scalars of the decode or call in flight, nothing else (the graphs' keys live in the slots below)
     GenDev gp{};
-    TsDev ts{};                            // timestamp rules of the current decode (ts.on = 0: off); buffers allocated in wm_create
+    TsDev ts{};                            // timestamp rules (ts.on = 0: off); buffers allocated in wm_create
     wm_repeat_params rep{1.0f, 0};         // wm_set_repeat_rules: sticky until cleared (neutral = off)
     // wm_set_sampling: sticky until cleared.  samp_set = what the caller gave (keys copied to the host vector; empty: 0 .. B - 1), samp = the
     // current decode's (on = 0: off); its buffers (part, val, samp_keys) are allocated in wm_create
     bool samp_set_on = false; float samp_set_temp = 1.0f; uint64_t samp_set_seed = 0; std::vector<uint64_t> samp_set_keys;
     SampDev samp{};
     unsigned long long* samp_keys = nullptr;    // [max(maxB, 16)]
-    // wm_set_beam: sticky until cleared.  beam = the current decode's (on = 0: off); its buffers live in beam_state.  While a beam decode owns
-    // ctx->gp / ts / samp, the scalars the other captured graphs (graph, graph_base) were compared against wait in beam_keep: the next decode
-    // without beams takes them back, so those graphs survive a beam call
+    // wm_set_beam: sticky until cleared.  beam = the current decode's (on = 0: off); its buffers live in beam_state
     bool beam_set_on = false; wm_beam_params beam_set{};
     BeamDev beam{};
     struct wm_beam_state* beam_state = nullptr;
     int beam_clips = 0;                         // G of the current beam decode
     bool beam_expanded = false;                 // the cross K/V sits replicated (slot g * n + j); wm_decode_run / wm_decode_invalidate move it back
     bool beam_done = false;                     // the last decode was a beam decode and all its clips are done (wm_get_beam_result)
-    bool beam_keep_valid = false; GenDev beam_keep_gp{}; TsDev beam_keep_ts{}; SampDev beam_keep_samp{}; int beam_keep_B = 0;
-    hipGraphExec_t graph_beam = nullptr;        // one steady-state beam step; beam_graph_gp / _ts / _bd: what it was captured with
-    GenDev beam_graph_gp{}; TsDev beam_graph_ts{}; BeamDev beam_graph_bd{};
-    // wm_set_sequence_bias: sticky until cleared.  seq_bias_state holds the device tables and the host copy of what the caller set; sbias = the
-    // current decode's (on = 0: off).  Like samp it waits in beam_keep_sbias while a beam decode owns the context's scalars; beam_graph_sbias is
-    // what the beam graph was captured with
+    // wm_set_sequence_bias: sticky until cleared.  seq_bias_state: the device tables and the host copy of what the caller set; sbias: this decode's
     struct wm_seq_bias_state* seq_bias_state = nullptr;
-    SeqBiasDev sbias{}, beam_keep_sbias{}, beam_graph_sbias{};
+    SeqBiasDev sbias{};
     int Bdec = 0;
     bool began = false, first_done = false;
     long long iters = 0;
-
-    hipGraphExec_t graph = nullptr;
-    int graph_B = 0;
+    // a decode with beams works on graphs_beam, every other on graphs_plain: a key that differs drops that slot alone, each survives the other's calls
+    DecGraphSlot graphs_plain, graphs_beam;
     int graph_replays = 0;
 
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -377,11 +400,12 @@ int wm_proc_setup(wm_ctx* ctx, const char* who, const wm_gen_params* gp, const w
 // A call outside the decode loop (replay, parity tap, forward pass) overwrites what a decode in flight lives on (ids, L, kvlen, self K/V,
 // the processors' tables).  Clears `began` (wm_decode_run refuses until the next wm_decode_begin) and the modes the launches read off the
 // context: use_done (no early exit on the done flag), host_carry / dev_carry (no carried hidden rows), step_flow (no merged-step schedule;
-// wm_get_stats reports no schedule_steps).  The captured graphs depend only on GenDev / TsDev and buffer addresses: they are kept for a
-// following wm_decode_begin with the same parameters, unless drop_graphs (wm_forward_logits changes ctx->gp for good).
+// wm_get_stats reports no schedule_steps).  The captured graphs depend only on their DecGraphKey and on buffer addresses: both slots are kept for
+// a following wm_decode_begin with the same key, unless drop_graphs (wm_forward_logits).
 void wm_decode_invalidate(wm_ctx* ctx, bool drop_graphs = false);
-// A call's own scalars in ctx->gp / ctx->ts for the lifetime of the object; the decode's come back on every exit path, so that
-// wm_decode_begin_ts still finds its captured graph.
+// A call's own scalars in ctx->gp / ctx->ts for the lifetime of the object; the decode's come back on every exit path.  Not for the graphs (their
+// keys live in the slots) but for the readers of a finished decode: after a replay or tap wm_get_tokens reads the decode's gp.Tids / gp.eos, and
+// wm_token_timestamps / wm_forward_logits start from its ctx->gp.  (wm_get_beam_result reads ctx->beam, wm_get_stats counters: never swapped.)
 struct wm_scalars_swap {
     wm_ctx* ctx; GenDev gp; TsDev ts;
     wm_scalars_swap(wm_ctx* c, const GenDev& g, const TsDev& t) : ctx(c), gp(c->gp), ts(c->ts) { c->gp = g; c->ts = t; }
