@@ -232,13 +232,37 @@ int wm_set_repeat_rules(wm_ctx* ctx, const wm_repeat_params* rp /* NULL = off */
  * x_n = word (n & 3) of Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85) with key (seed_lo, seed_hi)
  * and counter (n >> 2, t, key_lo, key_hi), `key` the 64-bit stream key the caller gives each stream.  A token's noise therefore depends on
  * (seed, stream key, position, token id) alone: not on the batch slot, the batch size, the slicing of the vocabulary or graph replay.
- * This samples softmax(v / T) over the WHOLE distribution — openai-whisper's Categorical(logits / T); HF's default top_k = 50 warper is not applied
- * (the deviation; an explicit top_k / top_p is refused by the Python layer).
+ * Without a filter this samples softmax(v / T) over the WHOLE distribution — openai-whisper's Categorical(logits / T); HF's default top_k = 50
+ * warper is not applied by default (the deviation): wm_set_sampling_filter below adds top_k / top_p / min_p as one value threshold per row.  HF's
+ * own top_k= / top_p= keywords stay refused by the Python layer, which has sampling_top_k= / sampling_top_p= / sampling_min_p= for the engine's.
  * Sticky on the context until cleared (NULL); read by wm_decode_begin / wm_decode_begin_ts, which then return WM_ERR_ARG (wm_last_error says why)
  * when n_keys != B, when wm_gen_params.vanilla == 0 (sampling runs on the plain decode path only) or on a candidate-tree context.  wm_set_sampling
  * itself: WM_ERR_ARG for a temperature that is not finite or <= 0, n_keys < 0.  wm_gen_params.temperature keeps its meaning (typical acceptance). */
 typedef struct wm_sample_params { float temperature; uint64_t seed; const uint64_t* stream_keys /* HOST [n_keys]; NULL: 0..B-1 */; int32_t n_keys; } wm_sample_params;
 int wm_set_sampling(wm_ctx* ctx, const wm_sample_params* sp /* NULL = off */);
+
+/* Top-k, top-p and min-p filters of the seeded draw (additive to ABI v9; csrc/wm_sample.hip k_filter_prep / k_filter_row): HF's
+ * TopKLogitsWarper, TopPLogitsWarper and MinPLogitsWarper, min_tokens_to_keep = 1, as ONE fp32 value threshold tau per row, applied between steps
+ * 2 and 3 above.  R = the ids step 2 leaves with v_n > -inf, m = max_R v, a_n = fl(fl(v_n - m) * fl(1/T)) (1/T > 0 keeps the order, so the whole
+ * filter is defined on v):
+ *   top_k >= 1 (0 = off): tau_k = the k-th largest value of {v_n : n in R}, counted with multiplicity; -inf when |R| <= k.  Keep v_n >= tau_k: ties
+ *      at the k-th place are all kept, as `scores < topk(scores, k)[0][..., -1]` keeps them.  Pure ordering: exact on every row.
+ *   0 < top_p < 1 (1 = off): on the set K1 top-k leaves, q_n = exp(a_n) / sum_K1 exp(a_j); a value x is kept iff the values strictly greater
+ *      than x hold less than top_p of the mass (TopPLogitsWarper removes the ascending prefix whose cumulative mass is <= 1 - top_p), so the
+ *      maximum always stays.  Equal values share one fate; HF's sort may split a tie at the boundary (the one deviation: a superset of HF's set).
+ *      The engine adds the masses as integers: round(expf(a_n) * 2^40) in 64 bits, so that the sum does not depend on its order (error of the
+ *      quantisation <= V * 2^-41 of the largest mass); tau_p = the value at which the sum, from the largest value down, first reaches
+ *      ceil(top_p * total), the product taken in fp64: a total above 2^53 units (up to V * 2^40, about 2^56) rounds by up to 4 units on its way
+ *      to fp64 and the product by as much again — deterministic (a function of the integer total alone) and at most 2^-36 of the largest mass.
+ *   0 < min_p <= 1 (0 = off): keep n iff expf(a_n) >= min_p (MinPLogitsWarper: the ratio to the maximum survives HF's renormalisation); tau_m =
+ *      the smallest value of R that passes.
+ *   tau = max(tau_k, tau_p, tau_m); step 3 becomes the arg-max over {n in R : v_n >= tau} of the same fused multiply-add with the same noise.  The
+ *      comparison is a float comparison (-0.0 == +0.0).  A filter that keeps everything gives today's token and perturbed value bit for bit.
+ * The filtered draw depends on (seed, stream key, position, the row's values) alone: no float is added in an order that the batch slot, the batch
+ * size, the grid or graph replay could change.  Sticky like wm_set_sampling and read only while sampling is on: wm_decode_begin* returns WM_ERR_ARG
+ * when a filter is set and the decode does not sample.  The setter: WM_ERR_ARG for top_k < 0, top_p outside (0, 1], min_p outside [0, 1]. */
+typedef struct wm_sample_filter { int32_t top_k; float top_p; float min_p; } wm_sample_filter;
+int wm_set_sampling_filter(wm_ctx* ctx, const wm_sample_filter* f /* NULL = off */);
 
 /* Beam search on the plain decode path (additive to ABI v9; csrc/wm_beam.hip).  Stands in for HF generate(num_beams=n) with
  * do_sample off — GenerationMixin._beam_search (transformers generation/utils.py) and its helpers _get_top_k_continuations,
@@ -421,6 +445,13 @@ int wm_select_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_para
 int wm_sample_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* ts /* may be NULL */, const wm_sample_params* sp, int R,
                    const float* logits, const int32_t* prefixes, int Tmax, const int32_t* lens, const uint64_t* keys /* HOST [R] */,
                    int32_t* out_token, float* out_value /* winner's perturbed value */, int32_t* out_forced);
+/* Filter parity tap, the counterpart of wm_sample_rows with the same inputs plus the filter f (not NULL; all three off is allowed and runs
+ * wm_sample_rows' kernels): the rows go through k_sample1 / k_filter_prep / k_filter_row.  Outputs (HOST, [R] each): out_thr the row's threshold tau
+ * (-inf: nothing is cut), out_kept the number of ids the decision leaves with v >= tau (both only written while a filter is on: -inf and -1
+ * otherwise), then wm_sample_rows' forced, token and value.  WM_ERR_ARG as wm_sample_rows, and for a filter wm_set_sampling_filter refuses. */
+int wm_filter_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* ts /* may be NULL */, const wm_sample_params* sp,
+                   const wm_sample_filter* f, int R, const float* logits, const int32_t* prefixes, int Tmax, const int32_t* lens,
+                   const uint64_t* keys /* HOST [R] */, float* out_thr, int32_t* out_kept, int32_t* out_forced, int32_t* out_token, float* out_value);
 /* Beam-search parity tap (HF GenerationMixin._beam_search steps b to g on caller-given rows): S steps of logits (HOST float32 [S][G][n][vocab],
  * n = bp->num_beams, G clips) through the select, bookkeeping and ids-reorder kernels of the beam decode — no model, no K/V.  Stream s = g * n + j
  * starts from prefixes[s][0 .. prefix_len) (HOST int32 [G * n][Tmax]; one common length, >= gp->prompt_len = P of the length penalty) with running

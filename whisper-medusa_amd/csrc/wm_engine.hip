@@ -36,7 +36,7 @@ extern "C" void wm_destroy(wm_ctx* ctx)
                     ctx->finished, ctx->cand, ctx->niter, ctx->hist, ctx->supmask, ctx->exppen, ctx->tap_tok, ctx->done,
                     ctx->hf_keep, ctx->hb_keep, ctx->carry, ctx->rowinfo, ctx->sinfo, ctx->steprows, ctx->rs_table, ctx->tree, ctx->sibtree, ctx->sibpart, ctx->sel_src, ctx->sel_n, ctx->sel_base, ctx->exn8, ctx->exs,
                     ctx->xn, ctx->lnstats, ctx->foldv, ctx->kx8, ctx->vx8, ctx->kxs, ctx->vxs,
-                    ctx->ts.st, ctx->ts.ver, ctx->ts.part1t, ctx->ts.forced, ctx->samp.part, ctx->samp.val, ctx->samp_keys};
+                    ctx->ts.st, ctx->ts.ver, ctx->ts.part1t, ctx->ts.forced, ctx->samp.part, ctx->samp.val, ctx->samp_keys, ctx->samp.fv, ctx->samp.thr, ctx->samp.kept};
     for (void* b : bufs) if (b) hipFree(b);
     wm_align_free(ctx);
     wm_score_free(ctx);
@@ -255,6 +255,11 @@ extern "C" int wm_create(const wm_config* cfg, const wm_weights* w, int device, 
     CREATE_HIP(dev_alloc(&ctx->samp.part, RW * 16 * 8, st));
     CREATE_HIP(dev_alloc(&ctx->samp.val, RW + B, st));
     CREATE_HIP(dev_alloc(&ctx->samp_keys, std::max<size_t>(B, 16), st));
+    // its filters (wm_set_sampling_filter): the processed rows after the decision, thresholds, kept counts; filter off until a request says otherwise
+    CREATE_HIP(dev_alloc(&ctx->samp.fv, std::max<size_t>(B, 16) * ctx->Vpad, st));
+    CREATE_HIP(dev_alloc(&ctx->samp.thr, RW + B, st));
+    CREATE_HIP(dev_alloc(&ctx->samp.kept, RW + B, st));
+    ctx->samp.top_k = 0; ctx->samp.top_p = 1.0f; ctx->samp.min_p = 0.0f;
     const size_t Tids = ctx->Tal;
     CREATE_HIP(dev_alloc(&ctx->ids, B * Tids, st));
     CREATE_HIP(dev_alloc(&ctx->L, B, st));
@@ -406,11 +411,27 @@ extern "C" int wm_set_sampling(wm_ctx* ctx, const wm_sample_params* sp)
     else for (int i = 0; i < sp->n_keys; ++i) ctx->samp_set_keys.push_back((uint64_t)i);       // NULL: 0 .. n_keys - 1 (n_keys is still checked against B)
     return WM_OK;
 }
-// the device form of a sampling request: fl(1 / T), the seed's two words, the context's buffers
-static SampDev wm_sampling_dev(wm_ctx* ctx, float temperature, uint64_t seed)
+static int wm_filter_check(wm_ctx* ctx, const char* who, const wm_sample_filter* f)
+{
+    if (f->top_k < 0) { ctx->err = std::string(who) + ": top_k must be >= 0 (0 = off)"; return WM_ERR_ARG; }
+    if (!(f->top_p > 0.f && f->top_p <= 1.f)) { ctx->err = std::string(who) + ": top_p must be in (0, 1] (1 = off)"; return WM_ERR_ARG; }
+    if (!(f->min_p >= 0.f && f->min_p <= 1.f)) { ctx->err = std::string(who) + ": min_p must be in [0, 1] (0 = off)"; return WM_ERR_ARG; }
+    return WM_OK;
+}
+extern "C" int wm_set_sampling_filter(wm_ctx* ctx, const wm_sample_filter* f)
+{
+    if (!ctx) return WM_ERR_ARG;
+    if (!f) { ctx->samp_filter_on = false; ctx->samp_filter = wm_sample_filter{0, 1.0f, 0.0f}; return WM_OK; }
+    if (int rc = wm_filter_check(ctx, "wm_set_sampling_filter", f)) return rc;
+    ctx->samp_filter_on = true; ctx->samp_filter = *f;
+    return WM_OK;
+}
+// the device form of a sampling request: fl(1 / T), the seed's two words, the filter (NULL: off), the context's buffers
+static SampDev wm_sampling_dev(wm_ctx* ctx, float temperature, uint64_t seed, const wm_sample_filter* f)
 {
     SampDev d = ctx->samp;
     d.on = 1; d.inv_t = 1.0f / temperature; d.seed_lo = (unsigned)seed; d.seed_hi = (unsigned)(seed >> 32); d.keys = ctx->samp_keys;
+    d.top_k = f ? f->top_k : 0; d.top_p = f ? f->top_p : 1.0f; d.min_p = f ? f->min_p : 0.0f;
     return d;
 }
 
@@ -444,7 +465,9 @@ extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm
         if (!gp->vanilla) { ctx->err = "wm_decode_begin: sampling runs on the plain decode path only (wm_gen_params.vanilla = 1)"; return WM_ERR_ARG; }
         if (ctx->tn) { ctx->err = "wm_decode_begin: sampling is not supported with a candidate tree (medusa_choices with top-k > 1)"; return WM_ERR_ARG; }
         if ((int)ctx->samp_set_keys.size() != B) { ctx->err = "wm_decode_begin: wm_sample_params.n_keys must equal B"; return WM_ERR_ARG; }
-        sd = wm_sampling_dev(ctx, ctx->samp_set_temp, ctx->samp_set_seed);
+        sd = wm_sampling_dev(ctx, ctx->samp_set_temp, ctx->samp_set_seed, ctx->samp_filter_on ? &ctx->samp_filter : nullptr);
+    } else if (ctx->samp_filter_on) {
+        ctx->err = "wm_decode_begin: a sampling filter is set (wm_set_sampling_filter) but this decode does not sample (wm_set_sampling)"; return WM_ERR_ARG;
     }
     SeqBiasDev sbd{};                      // sequence bias (wm_set_sequence_bias): the sticky table's device form, after what only a decode can check
     if (int rc = wm_seq_bias_begin(ctx, "wm_decode_begin", gp, &sbd)) return rc;
@@ -752,27 +775,31 @@ extern "C" int wm_select_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_tim
     return rc;
 }
 
-// Sampling parity tap: caller-given rows through k_sample1 / k_sample_fin (include/wm.h), row r at position lens[r] under its own prefix.
-extern "C" int wm_sample_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* tsp, const wm_sample_params* sp, int R,
-                              const float* logits, const int32_t* prefixes, int Tmax, const int32_t* lens, const uint64_t* keys,
-                              int32_t* out_token, float* out_value, int32_t* out_forced)
+// Sampling parity taps: caller-given rows through k_sample1 / k_sample_fin — with a filter: k_sample1 / k_filter_prep / k_filter_row — (include/wm.h),
+// row r at position lens[r] under its own prefix.  wm_sample_rows: f, out_thr, out_kept NULL.
+static int wm_sample_rows_impl(wm_ctx* ctx, const char* who_, const wm_gen_params* gp, const wm_timestamp_params* tsp, const wm_sample_params* sp,
+                               const wm_sample_filter* f, int R, const float* logits, const int32_t* prefixes, int Tmax, const int32_t* lens,
+                               const uint64_t* keys, float* out_thr, int32_t* out_kept, int32_t* out_token, float* out_value, int32_t* out_forced)
 {
+    const std::string who(who_);
     if (!ctx) return WM_ERR_ARG;
     if (!gp || !sp || R < 1 || !logits || !prefixes || Tmax < 1 || !lens || !keys || !out_token || !out_value || !out_forced) {
-        ctx->err = "wm_sample_rows: bad arguments"; return WM_ERR_ARG; }
-    if (int rc = wm_sampling_check(ctx, "wm_sample_rows", sp)) return rc;
+        ctx->err = who + ": bad arguments"; return WM_ERR_ARG; }
+    if (int rc = wm_sampling_check(ctx, who_, sp)) return rc;
+    if (f) { if (int rc = wm_filter_check(ctx, who_, f)) return rc; }
     for (int r = 0; r < R; ++r)
-        if (lens[r] < 1 || lens[r] > std::min(Tmax, ctx->Tmax)) { ctx->err = "wm_sample_rows: lens must be in [1, min(Tmax, n_tgt)]"; return WM_ERR_ARG; }
+        if (lens[r] < 1 || lens[r] > std::min(Tmax, ctx->Tmax)) { ctx->err = who + ": lens must be in [1, min(Tmax, n_tgt)]"; return WM_ERR_ARG; }
     WM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     GenDev g{}; TsDev ts{};
-    if (int rc = wm_proc_setup(ctx, "wm_sample_rows", gp, tsp, &g, &ts)) return rc;
+    if (int rc = wm_proc_setup(ctx, who_, gp, tsp, &g, &ts)) return rc;
     g.max_length = g.hard_max_length = ctx->Tmax;
     g.inv_temp = 1.0f; g.force_accept = -1;
     g.accept_mode = WM_ACCEPT_GREEDY; g.vanilla = 1;
     wm_decode_invalidate(ctx);
     wm_scalars_swap swap(ctx, g, ts);
-    const SampDev sd = wm_sampling_dev(ctx, sp->temperature, sp->seed);
+    const SampDev sd = wm_sampling_dev(ctx, sp->temperature, sp->seed, f);
+    const bool flt = wm_filter_on(sd);
     int* buf = nullptr;
     WM_HIP(hipMalloc(reinterpret_cast<void**>(&buf), ((size_t)15 * Tmax + 15) * sizeof(int)));
     ts.rp_ids = buf; ts.rp_stride = Tmax; ts.rp_len = buf + (size_t)15 * Tmax;      // repetition rules: the rows' own prefixes
@@ -792,19 +819,36 @@ extern "C" int wm_sample_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_tim
         if (e == hipSuccess && ts.on) e = hipMemcpyAsync(ts.ver, recs.data(), n * sizeof(int4), hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpy2DAsync(ctx->logits, (size_t)ctx->Vpad * sizeof(float), logits + (size_t)r0 * ctx->V,
                                                   (size_t)ctx->V * sizeof(float), (size_t)ctx->V * sizeof(float), n, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) { ctx->err = std::string("wm_sample_rows: ") + hipGetErrorString(e); rc = WM_ERR_HIP; break; }
+        if (e != hipSuccess) { ctx->err = std::string(who + ": ") + hipGetErrorString(e); rc = WM_ERR_HIP; break; }
         rc = wm_sample_launch(ctx, g, ts, sd, buf + (size_t)15 * Tmax, n, 0, 1);
         if (rc) break;
         e = hipMemcpyAsync(out_token + r0, ctx->amax, n * sizeof(int), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipMemcpyAsync(out_value + r0, sd.val, n * sizeof(float), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess && wm_rules_on(ts)) e = hipMemcpyAsync(out_forced + r0, ts.forced, n * sizeof(int), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && flt && out_thr) e = hipMemcpyAsync(out_thr + r0, sd.thr, n * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && flt && out_kept) e = hipMemcpyAsync(out_kept + r0, sd.kept, n * sizeof(int), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);          // (the host staging of this chunk is reused by the next)
-        if (e != hipSuccess) { ctx->err = std::string("wm_sample_rows: ") + hipGetErrorString(e); rc = WM_ERR_HIP; break; }
+        if (e != hipSuccess) { ctx->err = std::string(who + ": ") + hipGetErrorString(e); rc = WM_ERR_HIP; break; }
         if (!wm_rules_on(ts)) std::fill(out_forced + r0, out_forced + r0 + n, 0);
+        if (!flt && out_thr) std::fill(out_thr + r0, out_thr + r0 + n, -INFINITY);
+        if (!flt && out_kept) std::fill(out_kept + r0, out_kept + r0 + n, -1);
     }
     (void)hipStreamSynchronize(st);
     (void)hipFree(buf);
     return rc;
+}
+extern "C" int wm_sample_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* tsp, const wm_sample_params* sp, int R,
+                              const float* logits, const int32_t* prefixes, int Tmax, const int32_t* lens, const uint64_t* keys,
+                              int32_t* out_token, float* out_value, int32_t* out_forced)
+{
+    return wm_sample_rows_impl(ctx, "wm_sample_rows", gp, tsp, sp, nullptr, R, logits, prefixes, Tmax, lens, keys, nullptr, nullptr, out_token, out_value, out_forced);
+}
+extern "C" int wm_filter_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* tsp, const wm_sample_params* sp, const wm_sample_filter* f,
+                              int R, const float* logits, const int32_t* prefixes, int Tmax, const int32_t* lens, const uint64_t* keys,
+                              float* out_thr, int32_t* out_kept, int32_t* out_forced, int32_t* out_token, float* out_value)
+{
+    if (ctx && (!f || !out_thr || !out_kept)) { ctx->err = "wm_filter_rows: bad arguments"; return WM_ERR_ARG; }
+    return wm_sample_rows_impl(ctx, "wm_filter_rows", gp, tsp, sp, f, R, logits, prefixes, Tmax, lens, keys, out_thr, out_kept, out_token, out_value, out_forced);
 }
 
 // forward(): one decoder pass over T tokens per stream at positions pos0.., K/V appended at row pos0.

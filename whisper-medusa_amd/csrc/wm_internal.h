@@ -72,7 +72,12 @@ struct SampDev {
     const unsigned long long* keys;     // DEV [rows] the 64-bit stream key of every row (counter words 2 and 3)
     float* part;                        // [Rcap][SEL_SP][8] slice partials {max text, perturbed max text, its id, max ts, sum exp ts at 1, perturbed max ts, its id, 0}
     float* val;                         // [Rcap] the winner's perturbed value (wm_sample_rows reads it)
+    // top-k / top-p / min-p filters (wm_set_sampling_filter): off = 0, 1, 0.  k_filter_prep / k_filter_row read them
+    int top_k; float top_p, min_p;
+    float* fv;                          // [max(maxB, 16)][Vpad] the processed row after the decision
+    float* thr; int* kept;              // [Rcap] the row's threshold and the number of region ids at or above it (wm_filter_rows reads them)
 };
+static inline bool wm_filter_on(const SampDev& sd) { return sd.top_k > 0 || sd.top_p < 1.0f || sd.min_p > 0.0f; }
 
 // Beam search on the plain decode path (wm_set_beam; csrc/wm_beam.hip).  Passed by value to the k_beam_* kernels, which stand in for
 // k_select1* / k_select_argmax* / k_accept_vanilla1* in the vanilla branch of wm_dec_iteration while beams are on; nothing else reads it.  Stream
@@ -116,16 +121,17 @@ struct DecGraphKey {
     GenDev g; int B;                                                    // B: streams (beams: clips x beams)
     int ts_on, tb, nots, mit, rp; float rp_pen; int rp_g;               // TsDev
     int samp_on; float inv_t; unsigned seed_lo, seed_hi;                // SampDev (all zero while sampling is off)
-    int sb_on, ngroups, pad_;                                           // SeqBiasDev (pad_: an even number of words, no tail padding)
+    int top_k; float top_p, min_p;                                      // SampDev's filter (all zero while sampling is off; off: 0, 1, 0)
+    int sb_on, ngroups;                                                 // SeqBiasDev (an even number of words: no tail padding)
 };
-static_assert(sizeof(GenDev) == 19 * 4 && sizeof(DecGraphKey) == sizeof(void*) + sizeof(GenDev) + 21 * 4, "DecGraphKey must have no padding");
+static_assert(sizeof(GenDev) == 19 * 4 && sizeof(DecGraphKey) == sizeof(void*) + sizeof(GenDev) + 23 * 4, "DecGraphKey must have no padding");
 static inline bool operator==(const DecGraphKey& a, const DecGraphKey& b) { return std::memcmp(&a, &b, sizeof(DecGraphKey)) == 0; }
 static inline DecGraphKey wm_dec_graph_key(const GenDev& g, int B, const TsDev& ts, const SampDev& sd, const SeqBiasDev& sbd, const BeamDev& bd)
 {
     DecGraphKey k{};
     k.g = g; k.B = B; k.sb_on = sbd.on; k.ngroups = sbd.ngroups;
     k.ts_on = ts.on; k.tb = ts.tb; k.nots = ts.nots; k.mit = ts.mit; k.rp = ts.rp; k.rp_pen = ts.rp_pen; k.rp_g = ts.rp_g;
-    if (sd.on) { k.samp_on = sd.on; k.inv_t = sd.inv_t; k.seed_lo = sd.seed_lo; k.seed_hi = sd.seed_hi; }
+    if (sd.on) { k.samp_on = sd.on; k.inv_t = sd.inv_t; k.seed_lo = sd.seed_lo; k.seed_hi = sd.seed_hi; k.top_k = sd.top_k; k.top_p = sd.top_p; k.min_p = sd.min_p; }
     if (bd.on) { k.beam_on = bd.on; k.n = bd.n; k.G = bd.G; k.es = bd.es; k.lp_pos = bd.lp_pos; k.rows_cap = bd.rows_cap; k.sh_kv = bd.sh_kv; }
     return k;
 }
@@ -302,6 +308,8 @@ struct wm_ctx {
     // wm_set_sampling: sticky until cleared.  samp_set = what the caller gave (keys copied to the host vector; empty: 0 .. B - 1), samp = the
     // current decode's (on = 0: off); its buffers (part, val, samp_keys) are allocated in wm_create
     bool samp_set_on = false; float samp_set_temp = 1.0f; uint64_t samp_set_seed = 0; std::vector<uint64_t> samp_set_keys;
+    // wm_set_sampling_filter: sticky until cleared, read only while sampling is on (a decode that does not sample refuses it)
+    bool samp_filter_on = false; wm_sample_filter samp_filter{0, 1.0f, 0.0f};
     SampDev samp{};
     unsigned long long* samp_keys = nullptr;    // [max(maxB, 16)]
     // wm_set_beam: sticky until cleared.  beam = the current decode's (on = 0: off); its buffers live in beam_state

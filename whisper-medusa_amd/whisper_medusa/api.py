@@ -577,6 +577,30 @@ class WhisperMedusaModel:
         """The sampling side of a generate() call: None unless ``sampling_seed`` is given AND the call asks for sampling (a positive scalar
         temperature, ``do_sample=True``, or a tuple / list temperature: HF's fallback schedule) — then {seed, ids, seeks, temps, fallback},
         after refusing, each by name, what sampling does not run with."""
+        req = self._sampling_request_unfiltered(temperature, kwargs, logits_processor)
+        flt = self._sampling_filter(kwargs)
+        if req is None:
+            if flt != (0, 1.0, 0.0):
+                given = [k for k in ("sampling_top_k", "sampling_top_p", "sampling_min_p") if kwargs.get(k) is not None]
+                raise ValueError(f"{', '.join(given)} given on a call that does not sample: the filters belong to the engine's seeded sampling "
+                                 "(sampling_seed= with a temperature > 0, do_sample=True or a temperature tuple)")
+            return None
+        req["filter"] = flt
+        return req
+
+    @staticmethod
+    def _sampling_filter(kwargs) -> tuple:
+        """(top_k, top_p, min_p) of ``sampling_top_k= / sampling_top_p= / sampling_min_p=`` (off: 0, 1.0, 0.0), refused in HF's words."""
+        k, p, m = kwargs.get("sampling_top_k"), kwargs.get("sampling_top_p"), kwargs.get("sampling_min_p")
+        if k is not None and (isinstance(k, bool) or not isinstance(k, (int, np.integer)) or int(k) < 0):
+            raise ValueError(f"`sampling_top_k` has to be a non-negative integer (0: off), but is {k!r}")
+        if p is not None and (isinstance(p, bool) or not isinstance(p, (int, float, np.floating)) or not 0.0 < float(p) <= 1.0):
+            raise ValueError(f"`sampling_top_p` has to be a float > 0 and <= 1 (1: off), but is {p!r}")
+        if m is not None and (isinstance(m, bool) or not isinstance(m, (int, float, np.floating)) or not 0.0 <= float(m) <= 1.0):
+            raise ValueError(f"`sampling_min_p` has to be a float in the [0, 1] interval (0: off), but is {m!r}")
+        return (0 if k is None else int(k), 1.0 if p is None else float(p), 0.0 if m is None else float(m))
+
+    def _sampling_request_unfiltered(self, temperature, kwargs, logits_processor) -> Optional[dict]:
         seed = kwargs.get("sampling_seed")
         if seed is None:
             return None
@@ -593,7 +617,8 @@ class WhisperMedusaModel:
             raise ValueError(f"`temperature` has to hold finite values >= 0, but is {temperature!r}")
         if kwargs.get("top_k") is not None or kwargs.get("top_p") is not None:
             raise NotImplementedError("top_k / top_p are not supported with sampling_seed: the engine samples softmax(logits / T) over the whole "
-                                      "vocabulary (openai-whisper's Categorical; HF's default top_k=50 warper is not applied)")
+                                      "vocabulary (openai-whisper's Categorical; HF's default top_k=50 warper is not applied) unless its own filters "
+                                      "are asked for: sampling_top_k= / sampling_top_p= / sampling_min_p= (DESIGN.md §2k), e.g. sampling_top_k=50")
         if self.config.is_tree:
             raise NotImplementedError("sampling (sampling_seed) is not supported with a candidate tree (medusa_choices with top-k > 1)")
         if logits_processor and any(type(p_).__name__ not in _LOWERABLE_PROCESSORS for p_ in logits_processor):
@@ -612,11 +637,12 @@ class WhisperMedusaModel:
         return (int(stream_id) & 0xFFFFFFFF) | (((16 * int(seek_frames) + int(attempt)) & 0xFFFFFFFF) << 32)
 
     @staticmethod
-    def _sampled_gp(gp: GenParams, T: float, seed: int, keys: List[int]) -> GenParams:
-        """``gp`` for one sampled attempt: the engine's plain decode path with the draw in place of the arg-max."""
+    def _sampled_gp(gp: GenParams, T: float, seed: int, keys: List[int], flt: tuple = (0, 1.0, 0.0)) -> GenParams:
+        """``gp`` for one sampled attempt: the engine's plain decode path with the (filtered) draw in place of the arg-max."""
         import dataclasses
         g = dataclasses.replace(gp, vanilla=True, accept_mode=ACCEPT_GREEDY, temperature=0.0, sampling_temperature=float(T),
-                                sampling_seed=int(seed), sampling_keys=list(keys), num_beams=1)     # (HF: a sampled retry runs with one beam)
+                                sampling_seed=int(seed), sampling_keys=list(keys), num_beams=1,     # (HF: a sampled retry runs with one beam)
+                                sampling_top_k=int(flt[0]), sampling_top_p=float(flt[1]), sampling_min_p=float(flt[2]))
         for k, v in vars(gp).items():           # (what generate() hangs on the object: _time_precision)
             if k.startswith("_"):
                 setattr(g, k, v)
@@ -782,7 +808,8 @@ class WhisperMedusaModel:
         for i, T in enumerate(samp["temps"]):
             if len(todo) != B or not (encoded or i > 0):
                 eng.encode(feats if len(todo) == B else feats[todo])        # (a rare path: one encoder pass over the flagged streams)
-            gp_i = gp if T == 0.0 else self._sampled_gp(gp, T, samp["seed"], [self.sampling_stream_key(ids[b], seeks[b], i) for b in todo])
+            gp_i = gp if T == 0.0 else self._sampled_gp(gp, T, samp["seed"], [self.sampling_stream_key(ids[b], seeks[b], i) for b in todo],
+                                                             samp.get("filter", (0, 1.0, 0.0)))
             if int(getattr(gp_i, "num_beams", 1) or 1) > 1:      # HF generate_with_fallback: num_beams stays exactly when the attempt does not sample
                 out = self._beam_decode(eng, feats if len(todo) == B else feats[todo], gp_i, True)
                 for j, b in enumerate(todo):

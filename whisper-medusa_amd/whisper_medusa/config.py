@@ -352,6 +352,10 @@ class GenParams:
     sampling_temperature: float = 0.0
     sampling_seed: int = 0
     sampling_keys: Optional[List[int]] = None        # one 64-bit stream key per stream; None: 0 .. B - 1
+    # its filters (wm_set_sampling_filter): one value threshold per row between the timestamp decision and the draw; off = 0, 1.0, 0.0
+    sampling_top_k: int = 0
+    sampling_top_p: float = 1.0
+    sampling_min_p: float = 0.0
 
     # Beam search on the plain decode path (wm_set_beam): num_beams > 1 with vanilla=True runs HF's _beam_search in the engine
     num_beams: int = 1

@@ -57,6 +57,10 @@ class WmSampleParams(C.Structure):
     _fields_ = [("temperature", C.c_float), ("seed", C.c_uint64), ("stream_keys", C.POINTER(C.c_uint64)), ("n_keys", C.c_int32)]
 
 
+class WmSampleFilter(C.Structure):
+    _fields_ = [("top_k", C.c_int32), ("top_p", C.c_float), ("min_p", C.c_float)]
+
+
 class WmBeamParams(C.Structure):
     _fields_ = [("num_beams", C.c_int32), ("length_penalty", C.c_float), ("early_stopping", C.c_int32)]
 
@@ -109,7 +113,7 @@ EXPORTS = ["wm_create", "wm_destroy", "wm_last_error", "wm_abi_version", "wm_bui
            "wm_decode_begin_ts", "wm_select_rows",
            "wm_token_timestamps", "wm_get_align_probs", "wm_get_align_matrix", "wm_dtw",
            "wm_score_tokens", "wm_score_rows", "wm_set_repeat_rules", "wm_score_tokens_topk", "wm_topk_rows",
-           "wm_logmel_long", "wm_gather_windows", "wm_set_sampling", "wm_sample_rows",
+           "wm_logmel_long", "wm_gather_windows", "wm_set_sampling", "wm_sample_rows", "wm_set_sampling_filter", "wm_filter_rows",
            "wm_set_beam", "wm_get_beam_result", "wm_beam_rows", "wm_beam_reorder_kv",
            "wm_set_sequence_bias", "wm_seq_bias_rows"]
 
@@ -161,6 +165,9 @@ def load_library(path: Optional[str] = None, act_fp16: bool = False) -> C.CDLL:
     lib.wm_set_sampling.argtypes = [vp, C.POINTER(WmSampleParams)]
     lib.wm_sample_rows.argtypes = [vp, C.POINTER(WmGenParams), C.POINTER(WmTimestampParams), C.POINTER(WmSampleParams), i32, f32p, i32p, i32, i32p,
                                    C.POINTER(C.c_uint64), i32p, f32p, i32p]
+    lib.wm_set_sampling_filter.argtypes = [vp, C.POINTER(WmSampleFilter)]
+    lib.wm_filter_rows.argtypes = [vp, C.POINTER(WmGenParams), C.POINTER(WmTimestampParams), C.POINTER(WmSampleParams), C.POINTER(WmSampleFilter), i32,
+                                   f32p, i32p, i32, i32p, C.POINTER(C.c_uint64), f32p, i32p, i32p, i32p, f32p]
     lib.wm_set_beam.argtypes = [vp, C.POINTER(WmBeamParams)]
     lib.wm_get_beam_result.argtypes = [vp, i32, i32, i32p, i32, i32p, f32p]
     lib.wm_beam_rows.argtypes = [vp, C.POINTER(WmGenParams), C.POINTER(WmTimestampParams), C.POINTER(WmBeamParams), i32, i32, f32p, i32p, i32, i32, f32p,
@@ -390,6 +397,21 @@ class Engine:
             self.set_sampling(None)
         else:
             self.set_sampling(T, int(gp.sampling_seed), gp.sampling_keys, B)
+        # (the filter follows gp too; set while T == 0 it stays set, and the decode refuses it by name: it is never ignored)
+        flt = (int(getattr(gp, "sampling_top_k", 0) or 0), float(getattr(gp, "sampling_top_p", 1.0)), float(getattr(gp, "sampling_min_p", 0.0) or 0.0))
+        if flt != getattr(self, "_filter_set", (0, 1.0, 0.0)):       # (a context starts with the filter off: the default path makes no call)
+            self.set_sampling_filter(*flt)
+
+    def set_sampling_filter(self, top_k: Optional[int] = 0, top_p: float = 1.0, min_p: float = 0.0) -> None:
+        """wm_set_sampling_filter: top-k / top-p / min-p for the following sampled decodes, sticky until cleared (``top_k=None``,
+        or all three off: 0, 1.0, 0.0).  Read only while sampling is on; a decode that does not sample refuses a set filter."""
+        if top_k is None or (int(top_k) == 0 and float(top_p) == 1.0 and float(min_p) == 0.0):
+            self._check(self.lib.wm_set_sampling_filter(self.h, None), "wm_set_sampling_filter")
+            self._filter_set = (0, 1.0, 0.0)
+            return
+        f = WmSampleFilter(int(top_k), float(top_p), float(min_p))
+        self._check(self.lib.wm_set_sampling_filter(self.h, C.byref(f)), "wm_set_sampling_filter")
+        self._filter_set = (int(top_k), float(top_p), float(min_p))
 
     @staticmethod
     def _beam_struct(num_beams: int, length_penalty: float = 1.0, early_stopping=False) -> WmBeamParams:
@@ -588,6 +610,31 @@ class Engine:
                                             pre.ctypes.data_as(i32p), Tmax, lens.ctypes.data_as(i32p), k64.ctypes.data_as(C.POINTER(C.c_uint64)),
                                             tok.ctypes.data_as(i32p), val.ctypes.data_as(f32p), fo.ctypes.data_as(i32p)), "wm_sample_rows")
         return dict(token=tok, value=val, ts_forced=fo)
+
+    def filter_rows(self, gp: GenParams, logits: np.ndarray, prefixes: Sequence[Sequence[int]], keys: Sequence[int], temperature: float,
+                    seed: int, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0) -> dict:
+        """Filter parity tap (wm_filter_rows): ``sample_rows`` with the top-k / top-p / min-p filter, through k_sample1 / k_filter_prep /
+        k_filter_row.  Returns numpy arrays thr (the row's threshold; -inf: nothing cut), kept (ids at or above it), ts_forced, token, value."""
+        x = np.ascontiguousarray(logits, dtype=np.float32)
+        R, V = x.shape
+        if V != self.cfg.vocab_size or len(prefixes) != R or len(keys) != R:
+            raise ValueError("filter_rows: logits must be [R, vocab] with one prefix and one stream key per row")
+        pre, lens, Tmax, _ = self._pack_ids(prefixes)
+        k64 = np.ascontiguousarray([int(k) & (2 ** 64 - 1) for k in keys], dtype=np.uint64)
+        tok = np.zeros(R, np.int32); val = np.zeros(R, np.float32); fo = np.zeros(R, np.int32)
+        thr = np.zeros(R, np.float32); kept = np.zeros(R, np.int32)
+        g, _keep = self._gen_struct(gp)
+        self._set_repeat_rules(gp)
+        ts = self._ts_struct(gp) if gp.timestamps else None
+        sp = WmSampleParams(float(temperature), int(seed) & (2 ** 64 - 1), None, 0)
+        f = WmSampleFilter(int(top_k), float(top_p), float(min_p))
+        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        self._kv_stamp = object()
+        self._check(self.lib.wm_filter_rows(self.h, C.byref(g), C.byref(ts) if ts is not None else None, C.byref(sp), C.byref(f), R,
+                                            x.ctypes.data_as(f32p), pre.ctypes.data_as(i32p), Tmax, lens.ctypes.data_as(i32p),
+                                            k64.ctypes.data_as(C.POINTER(C.c_uint64)), thr.ctypes.data_as(f32p), kept.ctypes.data_as(i32p),
+                                            fo.ctypes.data_as(i32p), tok.ctypes.data_as(i32p), val.ctypes.data_as(f32p)), "wm_filter_rows")
+        return dict(thr=thr, kept=kept, ts_forced=fo, token=tok, value=val)
 
     # ---- token-level timestamps (include/wm.h wm_token_timestamps) ---------------------------------
     def token_timestamps(self, seqs: Sequence[Sequence[int]], n_prompt, alignment_heads: Sequence[Sequence[int]], median_filter_width: int = 7,
