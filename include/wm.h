@@ -335,6 +335,21 @@ typedef struct wm_seq_bias_params {
 } wm_seq_bias_params;
 int wm_set_sequence_bias(wm_ctx* ctx, const wm_seq_bias_params* sb /* NULL = off */);
 
+/* Per-stream decoder prompts of ONE common length (additive to ABI v9).  Stands in for the rows HF's
+ * WhisperGenerationMixin._retrieve_init_tokens builds for generate(language=[...]) — one row of init tokens per clip, which differ in the language
+ * token alone — and which the reference never builds (model.py:1519-1537 takes one language).  prompts: HOST int32 [B][P], copied; clip b of the next
+ * decodes starts from row b.  wm_gen_params.prompt stays what it is — the caller passes a representative row (stream 0's) — and keeps every scalar it
+ * defines: P, begin_index, the start of the exponential decay, max_length.  The rows differ in ids only, and the ids of a decode are per-stream state
+ * already (ids, L, kvlen, the committed timestamp state): the prompt pass reads each stream's own row, no select kernel changes and the keys of the
+ * captured graphs do not see the table — two tables reuse one graph.  With timestamp rules the committed state of ids[begin_index:P] is folded per
+ * stream.  With beams (wm_set_beam) B is the number of CLIPS: every beam of clip g starts from row g and the "never set" entry of its finished table
+ * (wm_get_beam_result) is row g.  The replays (wm_score_tokens, wm_token_timestamps) take full id rows and need nothing.
+ * Sticky on the context until cleared (NULL), like wm_set_repeat_rules / wm_set_sequence_bias; read by wm_decode_begin / wm_decode_begin_ts only.
+ * WM_ERR_ARG from wm_set_stream_prompts: B < 1, P < 1 with prompts given; from wm_decode_begin* (wm_last_error names the cause): P !=
+ * wm_gen_params.prompt_len, B != the decode's number of clips, an id outside [0, vocab), timestamp rules on and a row whose first id is not below
+ * timestamp_begin.  Prompts of different lengths (ragged rows) do not exist. */
+int wm_set_stream_prompts(wm_ctx* ctx, const int32_t* prompts /* HOST [B][P], NULL = off */, int B, int P);
+
 /* ---- F3..F14 the Medusa decode loop (replaces _medusa_greedy_search, model.py:404-835) ---- */
 int wm_decode_begin(wm_ctx* ctx, const wm_gen_params* gp, int B);
 /* wm_decode_begin with the timestamp rules on (ts != NULL; NULL = wm_decode_begin).  WM_ERR_ARG (wm_last_error says why): a candidate tree
@@ -416,6 +431,22 @@ int wm_score_tokens_topk(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestam
                          int32_t* top_ids /* HOST [B][Tmax][topk] */, float* top_logprobs /* HOST [B][Tmax][topk] */, int32_t* ranks /* HOST [B][Tmax] */,
                          float* ms /* may be NULL */);
 
+/* ---- language detection on the device (additive to ABI v9; csrc/wm_lang.hip) ----
+ * Stands in for HF WhisperGenerationMixin.detect_language (transformers generation_whisper.py), which the reference reaches through
+ * _retrieve_init_tokens when `language` is None (model.py:1519-1537): one decoder pass over <|startoftranscript|>, every id that is no language token
+ * masked to -inf, arg-max.  Needs wm_encode with the same B (else WM_ERR_STATE).  One base pass over start_token at position 0 for all B streams —
+ * the launches of wm_forward_logits(.., T = 1, pos0 = 0, disable_medusa = 1), one batch instead of stream by stream — then k_lang_pick: one block
+ * per row gathers the n candidates lang_ids (HOST int32 [n]) from the row and reduces them (wave64 shuffles, one LDS round across the waves; no
+ * atomics, no sweep of the vocabulary).  out[b] (HOST int32 [B]) = the candidate with the largest value, among equal values the SMALLEST TOKEN ID —
+ * what HF's mask + argmax and torch.argmax on the CPU return; the answer does not depend on the order of lang_ids, the row's slot or B.  B ints come
+ * back, never a logits row.  A NaN candidate counts as -inf; when every candidate is -inf the smallest id wins.  *ms (may be NULL): hipEvent time of
+ * pass + pick.  Overwrites the decode state like wm_forward_logits (begin again afterwards); the captured graphs are kept.
+ * WM_ERR_ARG (wm_last_error names the cause): n outside [1, WM_LANG_MAX], an id outside [0, vocab), two equal ids, start_token outside the
+ * vocabulary, a null pointer. */
+#define WM_LANG_MAX 256
+int wm_detect_language(wm_ctx* ctx, int B, const int32_t* lang_ids /* HOST [n] */, int n, int32_t start_token, int32_t* out /* HOST [B] */,
+                       float* ms /* may be NULL */);
+
 /* ---- parity taps (test-only views of intermediate state; no reference equivalent except
  * forward(), model.py:1223-1347) ---- */
 /* encoder output [B][n_ctx][d_model] as float32 to HOST */
@@ -475,6 +506,12 @@ int wm_seq_bias_rows(wm_ctx* ctx, const wm_seq_bias_params* sb, int R,
                      const float* logits /* HOST [R][vocab] */,
                      const int32_t* prefixes /* HOST [R][Tmax] */, int Tmax, const int32_t* lens /* [R] */,
                      float* out /* HOST [R][vocab] */);
+/* Language-pick parity tap (HF detect_language's mask + argmax on caller-given rows): k_lang_pick alone, no model.  R rows (HOST float32 [R][vocab])
+ * under the candidates lang_ids (HOST int32 [n]); out (HOST int32 [R]) as wm_detect_language defines it.  WM_ERR_ARG (wm_last_error names the cause)
+ * as wm_detect_language's for lang_ids / n, and for R < 1 or a null pointer.  Overwrites ctx->logits of the decode state (begin again afterwards).
+ * Any R >= 1 (worked in groups of 15). */
+int wm_lang_pick_rows(wm_ctx* ctx, int R, const float* logits /* HOST [R][vocab] */, const int32_t* lang_ids /* HOST [n] */, int n,
+                      int32_t* out /* HOST [R] */);
 /* The K/V reorder of a beam step alone (HF: Cache.reorder_cache(beam_idx) behind _beam_search step g): stream s < B_streams takes over the self
  * K/V rows [0, len) of every kv layer from stream beam_idx[s] (HOST int32 [B_streams], each in [0, B_streams)), through the shadow buffer;
  * beam_idx[s] == s moves nothing.  WM_ERR_ARG for B_streams outside [1, max_batch], len outside [1, n_tgt], an index out of range.  Overwrites

@@ -36,7 +36,7 @@ extern "C" void wm_destroy(wm_ctx* ctx)
                     ctx->finished, ctx->cand, ctx->niter, ctx->hist, ctx->supmask, ctx->exppen, ctx->tap_tok, ctx->done,
                     ctx->hf_keep, ctx->hb_keep, ctx->carry, ctx->rowinfo, ctx->sinfo, ctx->steprows, ctx->rs_table, ctx->tree, ctx->sibtree, ctx->sibpart, ctx->sel_src, ctx->sel_n, ctx->sel_base, ctx->exn8, ctx->exs,
                     ctx->xn, ctx->lnstats, ctx->foldv, ctx->kx8, ctx->vx8, ctx->kxs, ctx->vxs,
-                    ctx->ts.st, ctx->ts.ver, ctx->ts.part1t, ctx->ts.forced, ctx->samp.part, ctx->samp.val, ctx->samp_keys, ctx->samp.fv, ctx->samp.thr, ctx->samp.kept};
+                    ctx->ts.st, ctx->ts.ver, ctx->ts.part1t, ctx->ts.forced, ctx->samp.part, ctx->samp.val, ctx->samp_keys, ctx->samp.fv, ctx->samp.thr, ctx->samp.kept, ctx->lang_ids, ctx->lang_out};
     for (void* b : bufs) if (b) hipFree(b);
     wm_align_free(ctx);
     wm_score_free(ctx);
@@ -260,6 +260,9 @@ extern "C" int wm_create(const wm_config* cfg, const wm_weights* w, int device, 
     CREATE_HIP(dev_alloc(&ctx->samp.thr, RW + B, st));
     CREATE_HIP(dev_alloc(&ctx->samp.kept, RW + B, st));
     ctx->samp.top_k = 0; ctx->samp.top_p = 1.0f; ctx->samp.min_p = 0.0f;
+    // language detection (wm_detect_language): the candidates and the picks of k_lang_pick
+    CREATE_HIP(dev_alloc(&ctx->lang_ids, WM_LANG_MAX, st));
+    CREATE_HIP(dev_alloc(&ctx->lang_out, std::max<size_t>(B, 16), st));
     const size_t Tids = ctx->Tal;
     CREATE_HIP(dev_alloc(&ctx->ids, B * Tids, st));
     CREATE_HIP(dev_alloc(&ctx->L, B, st));
@@ -435,6 +438,33 @@ static SampDev wm_sampling_dev(wm_ctx* ctx, float temperature, uint64_t seed, co
     return d;
 }
 
+// Per-stream prompts of one length (include/wm.h): kept on the context, read by wm_decode_begin / wm_decode_begin_ts
+extern "C" int wm_set_stream_prompts(wm_ctx* ctx, const int32_t* prompts, int B, int P)
+{
+    if (!ctx) return WM_ERR_ARG;
+    if (!prompts) { ctx->sp_rows.clear(); ctx->sp_B = ctx->sp_P = 0; return WM_OK; }
+    if (B < 1 || P < 1) { ctx->err = "wm_set_stream_prompts: B and P must be >= 1"; return WM_ERR_ARG; }
+    ctx->sp_rows.assign(prompts, prompts + (size_t)B * P); ctx->sp_B = B; ctx->sp_P = P;
+    return WM_OK;
+}
+// what only a decode can check of the sticky table: its shape against the decode's clips and prompt length, the ids, the timestamp rules' start token
+static int wm_stream_prompts_check(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* tsp, int G)
+{
+    const std::string w = "wm_decode_begin: stream prompts (wm_set_stream_prompts): ";
+    if (ctx->sp_P != gp->prompt_len) {
+        ctx->err = w + "rows of " + std::to_string(ctx->sp_P) + " ids, wm_gen_params.prompt_len is " + std::to_string(gp->prompt_len) + " (one common length)"; return WM_ERR_ARG; }
+    if (ctx->sp_B != G) { ctx->err = w + std::to_string(ctx->sp_B) + " rows for a decode of " + std::to_string(G) + " clips"; return WM_ERR_ARG; }
+    for (int b = 0; b < G; ++b) {
+        const int32_t* row = ctx->sp_rows.data() + (size_t)b * ctx->sp_P;
+        for (int i = 0; i < ctx->sp_P; ++i)
+            if (row[i] < 0 || row[i] >= ctx->V) {
+                ctx->err = w + "row " + std::to_string(b) + ": token id " + std::to_string(row[i]) + " outside the vocabulary"; return WM_ERR_ARG; }
+        if (tsp && row[0] >= tsp->timestamp_begin) {
+            ctx->err = w + "row " + std::to_string(b) + ": timestamps: the start token must lie below timestamp_begin"; return WM_ERR_ARG; }
+    }
+    return WM_OK;
+}
+
 extern "C" int wm_decode_begin(wm_ctx* ctx, const wm_gen_params* gp, int B) { return wm_decode_begin_ts(ctx, gp, nullptr, B); }
 
 extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* tsp, int B)
@@ -458,6 +488,9 @@ extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm
     if (P < 1 || P >= ctx->Tmax - ctx->K - 1) {
         // same condition class as the reference's over-long prompt ValueError (model.py:1526-1529)
         ctx->err = "wm_decode_begin: prompt length must be in [1, n_tgt - K - 2]"; return WM_ERR_ARG; }
+    // per-stream prompts (wm_set_stream_prompts): row g of the table is clip g's; none set: wm_gen_params.prompt for everybody
+    const int32_t* sp = ctx->sp_rows.empty() ? nullptr : ctx->sp_rows.data();
+    if (sp) { if (!gp->prompt) { ctx->err = "wm_decode_begin: bad prompt"; return WM_ERR_ARG; } if (int rc = wm_stream_prompts_check(ctx, gp, tsp, G)) return rc; }
     if (!gp->vanilla && gp->accept_mode == WM_ACCEPT_TYPICAL && !(gp->temperature > 0.f)) {
         ctx->err = "wm_decode_begin: typical acceptance needs temperature > 0"; return WM_ERR_ARG; }
     SampDev sd = ctx->samp; sd.on = 0;
@@ -496,7 +529,10 @@ extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm
     hipStream_t st = ctx->stream;           // uploads
     if (sd.on) WM_HIP(hipMemcpyAsync(ctx->samp_keys, ctx->samp_set_keys.data(), B * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     std::vector<int> ids((size_t)B * Tids, gp->pad_token_id), L(B, P), zero(B, 0);
-    for (int b = 0; b < B; ++b) for (int i = 0; i < P; ++i) ids[(size_t)b * Tids + i] = gp->prompt[i];
+    for (int b = 0; b < B; ++b) {             // (beams: stream b is a beam of clip b / nbeam)
+        const int32_t* row = sp ? sp + (size_t)(b / nbeam) * P : gp->prompt;
+        for (int i = 0; i < P; ++i) ids[(size_t)b * Tids + i] = row[i];
+    }
     WM_HIP(hipMemcpyAsync(ctx->ids, ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice, st));
     WM_HIP(hipMemcpyAsync(ctx->L, L.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
     WM_HIP(hipMemcpyAsync(ctx->kvlen, zero.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
@@ -509,9 +545,8 @@ extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm
     ctx->use_done = true;
     std::vector<int4> tst(B, make_int4(0, 0, -1, 0));
     if (ts.on) {                           // the committed timestamp state of the prompt's sampled part, ids[begin:P] (HF slices input_ids[begin_index:])
-        int4 s0 = make_int4(0, 0, -1, 0);
-        for (int i = std::max(g.begin, 0); i < P; ++i) s0 = ts_fold(s0, gp->prompt[i], ts.tb);
-        std::fill(tst.begin(), tst.end(), s0);
+        for (int b = 0; b < B; ++b)
+            for (int i = std::max(g.begin, 0); i < P; ++i) tst[b] = ts_fold(tst[b], ids[(size_t)b * Tids + i], ts.tb);
         WM_HIP(hipMemcpyAsync(ctx->ts.st, tst.data(), B * sizeof(int4), hipMemcpyHostToDevice, st));
     }
     if (beam) {

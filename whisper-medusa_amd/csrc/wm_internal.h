@@ -322,6 +322,11 @@ struct wm_ctx {
     // wm_set_sequence_bias: sticky until cleared.  seq_bias_state: the device tables and the host copy of what the caller set; sbias: this decode's
     struct wm_seq_bias_state* seq_bias_state = nullptr;
     SeqBiasDev sbias{};
+    // wm_set_stream_prompts: sticky until cleared.  The rows [sp_B][sp_P] of the clips' prompts (empty: off, every stream starts from wm_gen_params.prompt);
+    // wm_decode_begin_ts checks them against its decode and seeds ctx->ids / ctx->ts.st from them.  Nothing on the device: no launch carries them
+    std::vector<int32_t> sp_rows; int sp_B = 0, sp_P = 0;
+    // language detection (wm_lang.hip): the candidate ids [WM_LANG_MAX] and the picks [max(maxB, 16)] of k_lang_pick, allocated in wm_create
+    int *lang_ids = nullptr, *lang_out = nullptr;
     int Bdec = 0;
     bool began = false, first_done = false;
     long long iters = 0;

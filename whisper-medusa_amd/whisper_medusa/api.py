@@ -21,8 +21,9 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-from .config import MedusaConfig, GenParams, ACCEPT_TYPICAL, ACCEPT_GREEDY
+from .config import MedusaConfig, GenParams, ACCEPT_TYPICAL, ACCEPT_GREEDY, language_token
 from .engine import Engine, SEQ_BIAS_MAX as _SEQ_BIAS_MAX, SEQ_BIAS_MAX_LEN as _SEQ_BIAS_MAX_LEN
+from . import engine as _engine_mod
 from . import weights as _weights
 from . import synth as _synth
 from . import timestamps as _timestamps
@@ -531,6 +532,12 @@ class WhisperMedusaModel:
                     begin_suppress_tokens, prompt_ids, timestamps: bool = False, repetition_penalty=None, no_repeat_ngram_size=None) -> GenParams:
         cfg = self.config
         # G1, model.py:1519-1537; timestamps: without <|notimestamps|> (HF _retrieve_init_tokens with return_timestamps)
+        # language=[...] (one entry per clip, already resolved by _language_list): one row of init tokens per clip, as HF's
+        # _retrieve_init_tokens builds them — the rows differ at the language slot alone, so they have ONE length
+        prompts = None
+        if isinstance(language, (list, tuple)):
+            prompts = [_synth.default_prompt(cfg, l, task or "transcribe", timestamps=timestamps) for l in language]
+            language = language[0]
         prompt = _synth.default_prompt(cfg, language or "en", task or "transcribe", timestamps=timestamps)
         begin_suppress_index = None
         if prompt_ids is not None:
@@ -542,6 +549,9 @@ class WhisperMedusaModel:
                                  f"(max_target_positions {cfg.max_target_positions})")
             begin_suppress_index = len(prompt)      # reference model.py:1537: begin_index = init_tokens.shape[1] (without prompt_ids)
             prompt = pid + prompt
+            prompts = None if prompts is None else [pid + r for r in prompts]      # (the shared previous-text part, then each clip's init tokens)
+        if prompts is not None and all(r == prompt for r in prompts):
+            prompts = None                      # equal entries: the scalar call's parameters
         P = len(prompt)
         if max_new_tokens is not None:
             mlen = P + int(max_new_tokens)                                                # G2, model.py:1635-1639
@@ -570,7 +580,50 @@ class WhisperMedusaModel:
                          no_timestamps_token_id=cfg.no_timestamps_token_id if timestamps else -1,
                          max_initial_timestamp_index=cfg.max_initial_timestamp_index if timestamps else None,
                          repetition_penalty=1.0 if repetition_penalty is None else float(repetition_penalty),
-                         no_repeat_ngram_size=0 if no_repeat_ngram_size is None else int(no_repeat_ngram_size))
+                         no_repeat_ngram_size=0 if no_repeat_ngram_size is None else int(no_repeat_ngram_size), prompts=prompts)
+
+    def _language_list(self, language, batch_size: int) -> List[str]:
+        """``language=[...]`` of a generate() call over ``batch_size`` clips -> one language token string ('<|de|>') per clip.  HF's own checks and
+        messages (WhisperGenerationMixin._retrieve_init_tokens): a None inside is a TypeError, a length other than the batch a ValueError; every
+        entry is resolved as a scalar is (``Unsupported language: ...``)."""
+        if any(l is None for l in language):
+            raise TypeError("Expected `language` to be `None`, a single string (e.g. `'en'`), or a list of strings with "
+                            "length equal to the batch size (e.g. `('en', 'fr')` for a batch size of 2). Got a list "
+                            "containing `None`.")
+        if len(language) != batch_size:
+            raise ValueError("When passing a list of languages, the length of the list must match the batch size. "
+                             f"Expected length of {batch_size}, but got {len(language)} languages.")
+        out = []
+        for l in language:
+            if not isinstance(l, str):
+                raise ValueError(f"Unsupported language: {l}")
+            key = language_token(l)
+            if self.config.is_multilingual and key not in self.config.lang_to_id:
+                raise ValueError(f"Unsupported language: {l}")
+            out.append(key)
+        return out
+
+    def _language_candidates(self) -> Tuple[List[str], List[int]]:
+        """The language tokens of lang_to_id that lie inside the vocabulary, by id, and their ids: what language detection picks among."""
+        cfg = self.config
+        toks = [k for k in sorted(cfg.lang_to_id, key=lambda k: cfg.lang_to_id[k]) if 0 <= cfg.lang_to_id[k] < cfg.vocab_size]
+        if not toks:
+            raise ValueError("language detection: no language token of lang_to_id lies inside the vocabulary")
+        return toks, [int(cfg.lang_to_id[t]) for t in toks]
+
+    def _detect_language_on_device(self, feats: torch.Tensor) -> List[str]:
+        """``group_by_language=False``: one encoder pass over ``feats`` on the model's own engine, then the engine's own detection
+        (wm_detect_language: B ints come back, never a logits row).  The encoder pass stays resident for the decode that follows."""
+        B = feats.shape[0]
+        if B > self._max_batch:
+            self.set_max_batch(B)
+        toks, ids = self._language_candidates()
+        if len(ids) > _engine_mod.LANG_MAX:
+            raise ValueError(f"language detection: more than {_engine_mod.LANG_MAX} language tokens")
+        eng = self.engine
+        eng.encode(feats)
+        name = dict(zip(ids, toks))
+        return [name[i] for i in eng.detect_language(ids, self.config.decoder_start_token_id)]
 
     # ---- seeded sampling and HF's temperature fallback (engine: csrc/wm_sample.hip; DESIGN.md §2h) -------------------------------------------
     def _sampling_request(self, temperature, kwargs, logits_processor) -> Optional[dict]:
@@ -777,7 +830,7 @@ class WhisperMedusaModel:
             hi = min(B, lo + per)
             if not (encoded and lo == 0 and hi == B):
                 eng.encode(feats if (lo == 0 and hi == B) else feats[lo:hi])
-            eng.decode(gp, hi - lo)
+            eng.decode(gp.for_streams(range(lo, hi)), hi - lo)      # (per-stream prompts follow their clips into the group)
             hyps += [[eng.beam_result(c, k) for k in range(n)] for c in range(hi - lo)]
             st = eng.stats()
             if stats is None:
@@ -810,6 +863,7 @@ class WhisperMedusaModel:
                 eng.encode(feats if len(todo) == B else feats[todo])        # (a rare path: one encoder pass over the flagged streams)
             gp_i = gp if T == 0.0 else self._sampled_gp(gp, T, samp["seed"], [self.sampling_stream_key(ids[b], seeks[b], i) for b in todo],
                                                              samp.get("filter", (0, 1.0, 0.0)))
+            gp_i = gp_i.for_streams(todo)       # (per-stream prompts follow their streams into the sub-batch)
             if int(getattr(gp_i, "num_beams", 1) or 1) > 1:      # HF generate_with_fallback: num_beams stays exactly when the attempt does not sample
                 out = self._beam_decode(eng, feats if len(todo) == B else feats[todo], gp_i, True)
                 for j, b in enumerate(todo):
@@ -840,7 +894,7 @@ class WhisperMedusaModel:
     @torch.no_grad()
     def generate(self, input_features: Optional[torch.Tensor] = None, generation_config=None, logits_processor=None,
                  stopping_criteria=None, prefix_allowed_tokens_fn=None, synced_gpus: bool = False,
-                 return_timestamps: Optional[bool] = None, task: Optional[str] = None, language: Optional[str] = None,
+                 return_timestamps: Optional[bool] = None, task: Optional[str] = None, language: Optional[Union[str, Sequence[str]]] = None,
                  is_multilingual: Optional[bool] = None, prompt_ids: Optional[torch.Tensor] = None,
                  prompt_condition_type: Optional[str] = None, condition_on_prev_tokens: Optional[bool] = None,
                  temperature: Optional[Union[float, Tuple[float, ...]]] = None,
@@ -863,7 +917,12 @@ class WhisperMedusaModel:
         rank of the emitted id in its row (0: masked); -1 / -inf / 0 where nothing is scored.
 
         ``sequential_longform=True`` with ``return_timestamps=True``: ``input_features [B, n_mels, T]`` of any length — per-clip
-        lengths from ``attention_mask [B, T]`` or ``num_frames=`` — are transcribed by Whisper's sequential long-form loop."""
+        lengths from ``attention_mask [B, T]`` or ``num_frames=`` — are transcribed by Whisper's sequential long-form loop.
+
+        ``language=[...]`` (HF ``language: str | list[str]``): one language per clip, decoded as ONE batch — one encoder pass, one
+        decode, row b carrying clip b's language token.  ``language=None, group_by_language=False``: the languages are detected on the device
+        (``Engine.detect_language``) and the batch is decoded from the same encoder pass, whatever the mix; the default ``True`` detects on the
+        host and decodes every language group as a batch of its own."""
         if generation_config is not None:
             # HF semantics (model.py:936-943 -> GenerationMixin._prepare_generation_config): a copy of the passed config, updated by every
             # explicit argument of this call — an explicit argument wins, the config fills what the call leaves open.  Only the fields this
@@ -994,6 +1053,13 @@ class WhisperMedusaModel:
             raise ValueError("input_features is required")
         if input_features.dim() != 3:
             raise ValueError("input_features must be [B, n_mels, frames]")
+        # language=[...]: one language per clip (HF `language: str | list[str]`, _retrieve_init_tokens).  The entries become language
+        # token strings; the long-form loops below take them as one language per recording, the short-form path as per-stream prompts of one length
+        lang_list = isinstance(language, (list, tuple))
+        if lang_list:
+            language = self._language_list(language, input_features.shape[0])
+            if not self.config.is_multilingual:
+                language, lang_list = None, False       # ignored, as a scalar is (the prompt has no language slot)
         if kwargs.get("sequential_longform"):
             return self._generate_sequential(input_features, attention_mask, dict(kwargs, language=language, task=task, temperature=temperature,
                                                                                   prompt_ids=prompt_ids, _sc_req=sc_req,
@@ -1010,6 +1076,14 @@ class WhisperMedusaModel:
                                                                 return_dict_in_generate=return_dict_in_generate,
                                                                 return_segments=return_segments, time_precision=time_precision))
         if language is None and self.config.is_multilingual and kwargs.get("detect_language", True) and input_features.shape[0] >= 1 \
+                and not kwargs.get("_language_resolved") and kwargs.get("group_by_language", True) is False:
+            # group_by_language=False: encode, detect on the device, then THIS call goes on with the detected list and decodes
+            # from the encoder pass that is resident — one encode, one decode, whatever the mix of languages
+            language = self._detect_language_on_device(input_features.to(self.device, torch.float32).contiguous())
+            self.detected_languages = list(language)
+            lang_list = True
+            kwargs = dict(kwargs, _encoded_batch=input_features.shape[0])
+        if language is None and self.config.is_multilingual and kwargs.get("detect_language", True) and input_features.shape[0] >= 1 \
                 and not kwargs.get("_language_resolved"):
             return self._generate_detecting_language(input_features, dict(kwargs, task=task, temperature=temperature, prompt_ids=prompt_ids,
                                                                           return_dict_in_generate=return_dict_in_generate,
@@ -1018,6 +1092,9 @@ class WhisperMedusaModel:
                                                                           _sc_req=sc_req, _sc_outer=sc_side,
                                                                           return_timestamps=bool(return_timestamps), time_precision=time_precision))
         B = input_features.shape[0]
+        if lang_list and kwargs.get("streamer") is not None:
+            raise NotImplementedError("language=[...] / group_by_language=False (one language per clip) is not supported with streamer= "
+                                      "(the streaming path is built around a single prompt)")
         if B > self._max_batch:
             self.set_max_batch(B)
         if beam is not None and beam["n"] > self._max_batch:        # (a wrapper may have resized the context since the request was read)
@@ -1039,7 +1116,10 @@ class WhisperMedusaModel:
             gp.sequence_bias = bias
         if logits_processor or stopping_criteria:
             gp = lower_processors(gp, logits_processor, stopping_criteria)
-        self._last_prompt = list(gp.prompt)
+        if lang_list and (getattr(gp, "_host_criteria", None) or getattr(gp, "_host_processors", None)):
+            raise NotImplementedError("language=[...] / group_by_language=False (one language per clip) is not supported on the host processor path "
+                                      "(logits_processor= / stopping_criteria= that the engine cannot lower: it is built around a single prompt)")
+        self._last_prompt = list(gp.prompt)         # (per-stream prompts, gp.prompts, have this one's length: the representative row)
         feats = input_features.to(self.device, torch.float32).contiguous()
         n_ctx = self._micro_batches_for(B) if (kwargs.get("streamer") is None and not getattr(gp, "_host_criteria", None)
                                                and not getattr(gp, "_host_processors", None)) else 1
@@ -1058,10 +1138,10 @@ class WhisperMedusaModel:
             pool = self._get_pool(n_ctx)
             tsf = None
             if tt_req is not None:
-                tsf = lambda e, sq, lo: self._token_ts_run(e, sq, gp, tt_req, lo)       # noqa: E731
+                tsf = lambda e, sq, lo: self._token_ts_run(e, sq, gp.for_streams(range(lo, lo + len(sq))), tt_req, lo)       # noqa: E731
             extra = {"token_ts": tsf} if tsf is not None else {}
             if sc_req is not None:
-                extra["score"] = lambda e, sq, lo: self._score_run(e, sq, gp, sc_req)    # noqa: E731
+                extra["score"] = lambda e, sq, lo: self._score_run(e, sq, gp.for_streams(range(lo, lo + len(sq))), sc_req)    # noqa: E731
             seqs = pool.run(feats, gp, **extra)      # F1..F14 per micro-batch, concurrently
             self.last_stats = pool.last_stats
             tt = self._token_ts_tensor(pool.last_token_timestamps, seqs, gp) if tt_req is not None else None
@@ -1204,7 +1284,7 @@ class WhisperMedusaModel:
             ns = None if nsp is None else float(nsp[b])
             fb, skip = _scores.gate(ns, avg, cr, req["no_speech_threshold"], req["logprob_threshold"], req["compression_ratio_threshold"])
             if skip:
-                s = list(gp.prompt) + [gp.eos_token_id]
+                s = list(gp.prompt_of(b)) + [gp.eos_token_id]       # (its own prompt: per-stream prompts)
                 row = np.zeros(len(s), dtype=np.float32)
             infos.append(dict(token_logprobs=row, avg_logprob=avg, compression_ratio=cr, no_speech_prob=ns, skipped=skip, needs_fallback=fb))
             if k:
@@ -1622,6 +1702,8 @@ class WhisperMedusaModel:
             first = self.detect_language(win[::n])
             kw["detect_language"] = False
             langs = first
+        elif isinstance(kw.get("language"), (list, tuple)):
+            langs = list(kw["language"])            # language=[...]: one language per recording (generate() has checked and resolved them)
         else:
             langs = [kw.get("language")] * B
         kw.pop("language", None)
@@ -1800,6 +1882,8 @@ class WhisperMedusaModel:
         feats = input_features.to(self.device, torch.float32).contiguous()
         detect = kw.get("language") is None and cfg.is_multilingual and kw.pop("detect_language", True)
         langs: List[Optional[str]] = [None if detect else kw.get("language")] * B
+        if isinstance(kw.get("language"), (list, tuple)):
+            langs = list(kw["language"])            # language=[...]: one language per recording (generate() has checked and resolved them)
         kw.pop("language", None)
         kw.pop("detect_language", None)
         prompts: List[Optional[List[int]]] = [None] * B
@@ -1928,6 +2012,9 @@ class WhisperMedusaModel:
             return self.generate(input_features, **kw)
         rank, world = td.get_rank(), td.get_world_size()
         mine = _dist.shard_streams(B, rank, world)
+        if isinstance(kw.get("language"), (list, tuple)):
+            # language=[...]: checked against the WHOLE batch, then split with the clips
+            kw = dict(kw, language=[self._language_list(kw["language"], B)[s_] for s_ in mine])
         local, local_sc = [], []
         gc = kw.get("generation_config")        # (the thresholds may come through a passed generation_config, as in generate())
         scoring = any(kw.get(k) is not None or getattr(gc, k, None) is not None

@@ -15,7 +15,7 @@ from __future__ import annotations
 import json
 import os
 from dataclasses import dataclass, field, asdict
-from typing import List, Optional, Tuple, Union
+from typing import List, Optional, Sequence, Tuple, Union
 
 HEAD_DIM = 64  # every Whisper size uses 64-wide attention heads
 
@@ -365,6 +365,25 @@ class GenParams:
     # Sequence bias on the plain decode path (wm_set_sequence_bias): HF SequenceBiasLogitsProcessor / NoBadWordsLogitsProcessor as an
     # in-place edit of the logits row; [(ids, bias), ..] in the caller's order, a bias finite or -inf.  None / empty = off; needs vanilla=True
     sequence_bias: Optional[List[Tuple[Tuple[int, ...], float]]] = None
+
+    # Per-stream prompts of one common length (wm_set_stream_prompts): row b is clip b's decoder prompt (generate(language=[...]):
+    # the rows differ in the language token).  `prompt` stays a valid representative — row 0 — for every scalar derived from it.  None = off
+    prompts: Optional[List[List[int]]] = None
+
+    def prompt_of(self, b: int) -> List[int]:
+        """The decoder prompt of stream ``b`` of this decode."""
+        return self.prompt if not self.prompts else self.prompts[b]
+
+    def for_streams(self, idx: Sequence[int]) -> "GenParams":
+        """These parameters for the sub-batch ``idx`` of this decode's streams: the per-stream prompts follow their streams (the object itself
+        when there are none)."""
+        if not self.prompts:
+            return self
+        import copy
+        g = copy.copy(self)             # (keeps what generate() hangs on the object: _time_precision)
+        g.prompts = [list(self.prompts[b]) for b in idx]
+        g.prompt = list(g.prompts[0])
+        return g
 
     @property
     def repeat_rules(self) -> bool:

@@ -115,7 +115,10 @@ EXPORTS = ["wm_create", "wm_destroy", "wm_last_error", "wm_abi_version", "wm_bui
            "wm_score_tokens", "wm_score_rows", "wm_set_repeat_rules", "wm_score_tokens_topk", "wm_topk_rows",
            "wm_logmel_long", "wm_gather_windows", "wm_set_sampling", "wm_sample_rows", "wm_set_sampling_filter", "wm_filter_rows",
            "wm_set_beam", "wm_get_beam_result", "wm_beam_rows", "wm_beam_reorder_kv",
-           "wm_set_sequence_bias", "wm_seq_bias_rows"]
+           "wm_set_sequence_bias", "wm_seq_bias_rows",
+           "wm_set_stream_prompts", "wm_detect_language", "wm_lang_pick_rows"]
+
+LANG_MAX = 256                                             # WM_LANG_MAX (include/wm.h)
 
 _lib = {}
 
@@ -175,6 +178,9 @@ def load_library(path: Optional[str] = None, act_fp16: bool = False) -> C.CDLL:
     lib.wm_beam_reorder_kv.argtypes = [vp, i32, i32p, i32]
     lib.wm_set_sequence_bias.argtypes = [vp, C.POINTER(WmSeqBiasParams)]
     lib.wm_seq_bias_rows.argtypes = [vp, C.POINTER(WmSeqBiasParams), i32, f32p, i32p, i32, i32p, f32p]
+    lib.wm_set_stream_prompts.argtypes = [vp, i32p, i32, i32]
+    lib.wm_detect_language.argtypes = [vp, i32, i32p, i32, i32, i32p, f32p]
+    lib.wm_lang_pick_rows.argtypes = [vp, i32, f32p, i32p, i32, i32p]
     lib.wm_decode_run.argtypes = [vp, i32, i32p]
     lib.wm_get_tokens.argtypes = [vp, i32, i32p, i32, i32p]
     lib.wm_get_stats.argtypes = [vp, C.POINTER(WmStats)]
@@ -460,6 +466,53 @@ class Engine:
         """The context's sequence bias follows ``gp`` before every decode (wm_set_sequence_bias is sticky), like the repetition rules."""
         self.set_sequence_bias(getattr(gp, "sequence_bias", None) or None)
 
+    def set_stream_prompts(self, prompts: Optional[Sequence[Sequence[int]]]) -> None:
+        """wm_set_stream_prompts: one decoder prompt per clip for the following decodes, all of one length, sticky until cleared
+        (``prompts`` None).  The shape is checked against the decode by wm_decode_begin*."""
+        if prompts is None:
+            self._check(self.lib.wm_set_stream_prompts(self.h, None, 0, 0), "wm_set_stream_prompts")
+            return
+        rows = [[int(t) for t in r] for r in prompts]
+        if not rows or len({len(r) for r in rows}) != 1:
+            raise ValueError("set_stream_prompts: one prompt per clip, all of one length (ragged prompts are not supported)")
+        a = np.ascontiguousarray(rows, dtype=np.int32)
+        self._check(self.lib.wm_set_stream_prompts(self.h, a.ctypes.data_as(C.POINTER(C.c_int32)), a.shape[0], a.shape[1]), "wm_set_stream_prompts")
+
+    def _set_stream_prompts(self, gp: GenParams) -> None:
+        """The context's per-stream prompts follow ``gp`` before every decode (wm_set_stream_prompts is sticky): a missing field clears them, so a
+        pooled context never inherits the table of an earlier call."""
+        self.set_stream_prompts(getattr(gp, "prompts", None) or None)
+
+    def detect_language(self, lang_ids: Sequence[int], start_token: int) -> List[int]:
+        """wm_detect_language: the language token of every clip of the resident encoder pass — one base pass over ``start_token``, then the pick
+        among ``lang_ids`` on the device (the largest value, among equal values the smallest id).  B ints come back, never a logits row.
+        Overwrites the decode state; ``last_detect_ms`` holds the hipEvent time."""
+        if self._B is None:
+            raise RuntimeError("detect_language: encode first")
+        ids = np.ascontiguousarray([int(t) for t in lang_ids], dtype=np.int32)
+        out = np.zeros(self._B, dtype=np.int32)
+        ms = C.c_float(0)
+        i32p = C.POINTER(C.c_int32)
+        self._kv_stamp = object()
+        self._check(self.lib.wm_detect_language(self.h, self._B, ids.ctypes.data_as(i32p), len(ids), int(start_token), out.ctypes.data_as(i32p),
+                                                C.byref(ms)), "wm_detect_language")
+        self.last_detect_ms = ms.value
+        return [int(t) for t in out]
+
+    def lang_pick_rows(self, logits: np.ndarray, lang_ids: Sequence[int]) -> np.ndarray:
+        """Language-pick parity tap (wm_lang_pick_rows): rows ``logits [R, V]`` through k_lang_pick alone.  Returns numpy int32 [R]: the id of
+        ``lang_ids`` with the largest value in the row, among equal values the smallest id."""
+        x = np.ascontiguousarray(logits, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != self.cfg.vocab_size:
+            raise ValueError("lang_pick_rows: logits must be [R, vocab]")
+        ids = np.ascontiguousarray([int(t) for t in lang_ids], dtype=np.int32)
+        out = np.zeros(x.shape[0], dtype=np.int32)
+        i32p = C.POINTER(C.c_int32)
+        self._kv_stamp = object()
+        self._check(self.lib.wm_lang_pick_rows(self.h, x.shape[0], x.ctypes.data_as(C.POINTER(C.c_float)), ids.ctypes.data_as(i32p), len(ids),
+                                               out.ctypes.data_as(i32p)), "wm_lang_pick_rows")
+        return out
+
     def seq_bias_rows(self, entries, logits: np.ndarray, prefixes: Sequence[Sequence[int]]) -> np.ndarray:
         """Sequence-bias parity tap (wm_seq_bias_rows): rows ``logits [R, V]``, row r under ``prefixes[r]``, through k_seq_bias alone.  Returns the
         edited rows, numpy float32 [R, V]."""
@@ -532,6 +585,7 @@ class Engine:
         self._set_sampling(gp, B)
         self._set_beam(gp)
         self._set_sequence_bias(gp)
+        self._set_stream_prompts(gp)
         self._kv_stamp = object()             # the decode loop rewrites the self-attention cache: forward()'s cache handles go stale
         if gp.timestamps:                     # WhisperTimeStampLogitsProcessor in the loop (include/wm.h wm_decode_begin_ts)
             ts = self._ts_struct(gp)

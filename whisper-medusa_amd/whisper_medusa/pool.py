@@ -106,7 +106,8 @@ class ContextPool:
             res = [self._one(self.engines[0], x, gp, from_wav, None if token_ts is None else (lambda e, s: token_ts(e, s, 0)),
                              None if score is None else (lambda e, s: score(e, s, 0)))]
         else:
-            futs = [self._ex.submit(self._one, self.engines[i], x[lo:hi].contiguous(), gp, from_wav,
+            # (per-stream prompts, GenParams.prompts: every context gets its own streams' rows)
+            futs = [self._ex.submit(self._one, self.engines[i], x[lo:hi].contiguous(), gp.for_streams(range(lo, hi)), from_wav,
                                     None if token_ts is None else (lambda e, s, lo=lo: token_ts(e, s, lo)),
                                     None if score is None else (lambda e, s, lo=lo: score(e, s, lo)))
                     for i, (lo, hi) in enumerate(bounds)]
