@@ -463,7 +463,7 @@ int wm_forward_logits(wm_ctx* ctx, int B, const int32_t* tokens /* HOST [B][T] *
  * exponential decay does not; the sampling temperature is gp->temperature.  Outputs (HOST, [R] each): the processed arg-max, p(probe_tokens[r]) under the softmax at 1/T, the entropy
  * H = -sum p log(p + 1e-5) (medusa_utils.py:566-568), and 1 where the log-softmax decision masked all text.  What it stands in for: HF
  * WhisperTimeStampLogitsProcessor.__call__ on one row plus the typical-acceptance statistics.  Overwrites the decode state like
- * wm_forward_logits (begin again afterwards).  Any R >= 1 (worked in groups of 15). */
+ * wm_forward_logits (begin again afterwards).  Any R >= 1 (worked in groups of WM_TAP_ROWS, csrc/wm_internal.h). */
 int wm_select_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* ts, int R, const float* logits, const int32_t* prefixes,
                    int Tmax, const int32_t* lens, const int32_t* probe_tokens, int32_t* out_argmax, float* out_p_probe, float* out_entropy,
                    int32_t* out_ts_forced);
@@ -501,7 +501,7 @@ int wm_beam_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params
  * [R][vocab]) through k_seq_bias under the entries of sb (checked and grouped as wm_set_sequence_bias does; the context's own sticky table is
  * untouched and back in place afterwards), row r under prefix prefixes[r][0 .. lens[r]) (HOST int32 [R][Tmax]); out (HOST float32 [R][vocab]) = the
  * edited rows.  WM_ERR_ARG (wm_last_error names the cause) for a bad sb, R < 1, lens outside [1, Tmax].  Overwrites ctx->logits of the decode state
- * (begin again afterwards).  Any R >= 1 (worked in groups of 15). */
+ * (begin again afterwards).  Any R >= 1 (worked in groups of WM_TAP_ROWS, csrc/wm_internal.h). */
 int wm_seq_bias_rows(wm_ctx* ctx, const wm_seq_bias_params* sb, int R,
                      const float* logits /* HOST [R][vocab] */,
                      const int32_t* prefixes /* HOST [R][Tmax] */, int Tmax, const int32_t* lens /* [R] */,
@@ -509,7 +509,7 @@ int wm_seq_bias_rows(wm_ctx* ctx, const wm_seq_bias_params* sb, int R,
 /* Language-pick parity tap (HF detect_language's mask + argmax on caller-given rows): k_lang_pick alone, no model.  R rows (HOST float32 [R][vocab])
  * under the candidates lang_ids (HOST int32 [n]); out (HOST int32 [R]) as wm_detect_language defines it.  WM_ERR_ARG (wm_last_error names the cause)
  * as wm_detect_language's for lang_ids / n, and for R < 1 or a null pointer.  Overwrites ctx->logits of the decode state (begin again afterwards).
- * Any R >= 1 (worked in groups of 15). */
+ * Any R >= 1 (worked in groups of WM_TAP_ROWS, csrc/wm_internal.h). */
 int wm_lang_pick_rows(wm_ctx* ctx, int R, const float* logits /* HOST [R][vocab] */, const int32_t* lang_ids /* HOST [n] */, int n,
                       int32_t* out /* HOST [R] */);
 /* The K/V reorder of a beam step alone (HF: Cache.reorder_cache(beam_idx) behind _beam_search step g): stream s < B_streams takes over the self

@@ -608,7 +608,7 @@ extern "C" int wm_beam_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_times
     std::vector<int4> tst(Bs, make_int4(0, 0, -1, 0));
     for (int s = 0; s < Bs; ++s) {
         for (int t = 0; t < prefix_len; ++t) ids[(size_t)s * Tids + t] = prefixes[(size_t)s * Tmax + t];
-        for (int t = std::max(g.begin, 0); ts.on && t < prefix_len; ++t) tst[s] = ts_fold(tst[s], prefixes[(size_t)s * Tmax + t], ts.tb);
+        if (ts.on) tst[s] = ts_fold_ids(tst[s], prefixes + (size_t)s * Tmax, g.begin, prefix_len, ts.tb);
     }
     WM_HIP(hipMemcpyAsync(ctx->ids, ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice, st));
     if (int rc = wm_beam_seed_table(ctx, bd)) return rc;
@@ -624,8 +624,7 @@ extern "C" int wm_beam_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_times
     for (int g0 = 0; g0 < G; ++g0) out_steps[g0] = S;
     const int n2 = 2 * n;
     for (int step = 0; step < S; ++step) {
-        WM_HIP(hipMemcpy2DAsync(ctx->logits, (size_t)ctx->Vpad * sizeof(float), logits + (size_t)step * Bs * ctx->V, (size_t)ctx->V * sizeof(float),
-                                (size_t)ctx->V * sizeof(float), Bs, hipMemcpyHostToDevice, st));
+        WM_HIP(wm_tap_upload_logits(ctx, logits + (size_t)step * Bs * ctx->V, Bs));        // (step-shaped, not group-shaped: the taps' logits upload alone)
         if (int rc = wm_beam_step(ctx, g, ts, bd, false)) return rc;
         WM_HIP(hipMemcpyAsync(cand_val + (size_t)step * G * n2, bd.cval, (size_t)G * n2 * sizeof(float), hipMemcpyDeviceToHost, st));
         WM_HIP(hipMemcpyAsync(cand_beam + (size_t)step * G * n2, bd.cbeam, (size_t)G * n2 * sizeof(int), hipMemcpyDeviceToHost, st));

@@ -545,8 +545,7 @@ extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm
     ctx->use_done = true;
     std::vector<int4> tst(B, make_int4(0, 0, -1, 0));
     if (ts.on) {                           // the committed timestamp state of the prompt's sampled part, ids[begin:P] (HF slices input_ids[begin_index:])
-        for (int b = 0; b < B; ++b)
-            for (int i = std::max(g.begin, 0); i < P; ++i) tst[b] = ts_fold(tst[b], ids[(size_t)b * Tids + i], ts.tb);
+        for (int b = 0; b < B; ++b) tst[b] = ts_fold_ids(tst[b], ids.data() + (size_t)b * Tids, g.begin, P, ts.tb);
         WM_HIP(hipMemcpyAsync(ctx->ts.st, tst.data(), B * sizeof(int4), hipMemcpyHostToDevice, st));
     }
     if (beam) {
@@ -764,9 +763,9 @@ extern "C" int wm_select_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_tim
     if (!ctx) return WM_ERR_ARG;
     if (!gp || (!tsp && ctx->rep.repetition_penalty == 1.0f && ctx->rep.no_repeat_ngram_size == 0) || R < 1 || !logits || !prefixes || Tmax < 1 || !lens || !probe_tokens || !out_argmax || !out_p_probe || !out_entropy ||
         !out_ts_forced) { ctx->err = "wm_select_rows: bad arguments"; return WM_ERR_ARG; }
-    for (int r = 0; r < R; ++r)
-        if (lens[r] < 1 || lens[r] > Tmax || probe_tokens[r] < 0 || probe_tokens[r] >= ctx->V) {
-            ctx->err = "wm_select_rows: lens must be in [1, Tmax] and probe tokens inside the vocabulary"; return WM_ERR_ARG; }
+    bool probes_ok = true;
+    for (int r = 0; r < R; ++r) probes_ok = probes_ok && probe_tokens[r] >= 0 && probe_tokens[r] < ctx->V;
+    if (int rc = wm_tap_check_lens(ctx, "wm_select_rows", lens, R, Tmax, false, probes_ok, " and probe tokens inside the vocabulary")) return rc;
     WM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     GenDev g{}; TsDev ts{};
@@ -777,37 +776,26 @@ extern "C" int wm_select_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_tim
     g.accept_mode = WM_ACCEPT_TYPICAL; g.vanilla = 0;
     wm_decode_invalidate(ctx);
     wm_scalars_swap swap(ctx, g, ts);
-    const int L0 = lens[0];
-    WM_HIP(hipMemcpyAsync(ctx->L, &L0, sizeof(int), hipMemcpyHostToDevice, st));
-    int* buf = nullptr;
-    WM_HIP(hipMalloc(reinterpret_cast<void**>(&buf), ((size_t)R * Tmax + R) * sizeof(int)));
-    int rc = WM_OK;
-    std::vector<float> h2(16 * SEL_SP);
-    for (int r0 = 0; r0 < R && rc == WM_OK; r0 += 15) {
-        const int n = std::min(15, R - r0);
-        hipError_t e = hipMemcpyAsync(buf, prefixes + (size_t)r0 * Tmax, (size_t)n * Tmax * sizeof(int), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(buf + (size_t)n * Tmax, lens + r0, n * sizeof(int), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(ctx->cand + 1, probe_tokens + r0, n * sizeof(int), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpy2DAsync(ctx->logits, (size_t)ctx->Vpad * sizeof(float), logits + (size_t)r0 * ctx->V,
-                                                  (size_t)ctx->V * sizeof(float), (size_t)ctx->V * sizeof(float), n, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) { ctx->err = std::string("wm_select_rows: ") + hipGetErrorString(e); rc = WM_ERR_HIP; break; }
-        rc = wm_dec_select_rows(ctx, buf, buf + (size_t)n * Tmax, n, Tmax);
-        if (rc) break;
-        e = hipMemcpyAsync(out_argmax + r0, ctx->amax, n * sizeof(int), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(out_p_probe + r0, ctx->pc, n * sizeof(float), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(out_ts_forced + r0, ctx->ts.forced, n * sizeof(int), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(h2.data(), ctx->part2, (size_t)n * SEL_SP * sizeof(float), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) { ctx->err = std::string("wm_select_rows: ") + hipGetErrorString(e); rc = WM_ERR_HIP; break; }
-        for (int r = 0; r < n; ++r) {
-            float hs = 0.f;
-            for (int k = 0; k < SEL_SP; ++k) hs += h2[(size_t)r * SEL_SP + k];     // (k_accept's order)
-            out_entropy[r0 + r] = -hs;
-        }
+    wm_tap_stage s{ctx, "wm_select_rows", Tmax, WM_TAP_ROWS};
+    if (int rc = s.reserve()) return rc;
+    const int L0 = lens[0];         // quirk, kept: cur_len of the one "stream" (L[0]) is row 0's length, uploaded once per call, not per group
+    WM_TAP_HIP(s, hipMemcpyAsync(ctx->L, &L0, sizeof(int), hipMemcpyHostToDevice, st));
+    std::vector<float> h2((size_t)R * SEL_SP);
+    if (int rc = wm_tap_groups(s, R, logits, prefixes, lens, [&](int r0, int n) {
+            WM_TAP_HIP(s, hipMemcpyAsync(ctx->cand + 1, probe_tokens + r0, n * sizeof(int), hipMemcpyHostToDevice, st));
+            if (int rc = wm_dec_select_rows(ctx, s.pre, s.len, n, Tmax)) return rc;
+            WM_TAP_HIP(s, hipMemcpyAsync(out_argmax + r0, ctx->amax, n * sizeof(int), hipMemcpyDeviceToHost, st));
+            WM_TAP_HIP(s, hipMemcpyAsync(out_p_probe + r0, ctx->pc, n * sizeof(float), hipMemcpyDeviceToHost, st));
+            WM_TAP_HIP(s, hipMemcpyAsync(out_ts_forced + r0, ctx->ts.forced, n * sizeof(int), hipMemcpyDeviceToHost, st));
+            WM_TAP_HIP(s, hipMemcpyAsync(h2.data() + (size_t)r0 * SEL_SP, ctx->part2, (size_t)n * SEL_SP * sizeof(float), hipMemcpyDeviceToHost, st));
+            return WM_OK;
+        })) return rc;
+    for (int r = 0; r < R; ++r) {
+        float hs = 0.f;
+        for (int k = 0; k < SEL_SP; ++k) hs += h2[(size_t)r * SEL_SP + k];     // (k_accept's order)
+        out_entropy[r] = -hs;
     }
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(buf);
-    return rc;
+    return WM_OK;
 }
 
 // Sampling parity taps: caller-given rows through k_sample1 / k_sample_fin — with a filter: k_sample1 / k_filter_prep / k_filter_row — (include/wm.h),
@@ -822,8 +810,7 @@ static int wm_sample_rows_impl(wm_ctx* ctx, const char* who_, const wm_gen_param
         ctx->err = who + ": bad arguments"; return WM_ERR_ARG; }
     if (int rc = wm_sampling_check(ctx, who_, sp)) return rc;
     if (f) { if (int rc = wm_filter_check(ctx, who_, f)) return rc; }
-    for (int r = 0; r < R; ++r)
-        if (lens[r] < 1 || lens[r] > std::min(Tmax, ctx->Tmax)) { ctx->err = who + ": lens must be in [1, min(Tmax, n_tgt)]"; return WM_ERR_ARG; }
+    if (int rc = wm_tap_check_lens(ctx, who_, lens, R, Tmax, true)) return rc;
     WM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     GenDev g{}; TsDev ts{};
@@ -835,42 +822,29 @@ static int wm_sample_rows_impl(wm_ctx* ctx, const char* who_, const wm_gen_param
     wm_scalars_swap swap(ctx, g, ts);
     const SampDev sd = wm_sampling_dev(ctx, sp->temperature, sp->seed, f);
     const bool flt = wm_filter_on(sd);
-    int* buf = nullptr;
-    WM_HIP(hipMalloc(reinterpret_cast<void**>(&buf), ((size_t)15 * Tmax + 15) * sizeof(int)));
-    ts.rp_ids = buf; ts.rp_stride = Tmax; ts.rp_len = buf + (size_t)15 * Tmax;      // repetition rules: the rows' own prefixes
-    int rc = WM_OK;
-    std::vector<int4> recs(15);
-    for (int r0 = 0; r0 < R && rc == WM_OK; r0 += 15) {
-        const int n = std::min(15, R - r0);
+    wm_tap_stage s{ctx, who_, Tmax, WM_TAP_ROWS};
+    if (int rc = s.reserve()) return rc;
+    ts.rp_ids = s.pre; ts.rp_stride = Tmax; ts.rp_len = s.len;       // repetition rules: the rows' own prefixes
+    // outputs no kernel writes (rules off, filter off)
+    if (!wm_rules_on(ts)) std::fill(out_forced, out_forced + R, 0);
+    if (!flt && out_thr) std::fill(out_thr, out_thr + R, -INFINITY);
+    if (!flt && out_kept) std::fill(out_kept, out_kept + R, -1);
+    std::vector<int4> recs(WM_TAP_ROWS);
+    return wm_tap_groups(s, R, logits, prefixes, lens, [&](int r0, int n) {
         for (int r = 0; r < n && ts.on; ++r) {          // the row's record at its prefix length, where k_cand_fin puts stream 0's verify rows
-            int4 s0 = make_int4(0, 0, -1, 0);
-            const int32_t* pre = prefixes + (size_t)(r0 + r) * Tmax;
-            for (int t = std::max(g.begin, 0); t < lens[r0 + r]; ++t) s0 = ts_fold(s0, pre[t], ts.tb);
-            recs[r] = ts_record(s0, lens[r0 + r], g.begin, ts.tb, g.V, ts.mit);
+            const int len = lens[r0 + r];
+            recs[r] = ts_record(ts_fold_ids(make_int4(0, 0, -1, 0), prefixes + (size_t)(r0 + r) * Tmax, g.begin, len, ts.tb), len, g.begin, ts.tb, g.V, ts.mit);
         }
-        hipError_t e = hipMemcpyAsync(buf, prefixes + (size_t)r0 * Tmax, (size_t)n * Tmax * sizeof(int), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(buf + (size_t)15 * Tmax, lens + r0, n * sizeof(int), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(ctx->samp_keys, keys + r0, n * sizeof(uint64_t), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && ts.on) e = hipMemcpyAsync(ts.ver, recs.data(), n * sizeof(int4), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpy2DAsync(ctx->logits, (size_t)ctx->Vpad * sizeof(float), logits + (size_t)r0 * ctx->V,
-                                                  (size_t)ctx->V * sizeof(float), (size_t)ctx->V * sizeof(float), n, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) { ctx->err = std::string(who + ": ") + hipGetErrorString(e); rc = WM_ERR_HIP; break; }
-        rc = wm_sample_launch(ctx, g, ts, sd, buf + (size_t)15 * Tmax, n, 0, 1);
-        if (rc) break;
-        e = hipMemcpyAsync(out_token + r0, ctx->amax, n * sizeof(int), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(out_value + r0, sd.val, n * sizeof(float), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && wm_rules_on(ts)) e = hipMemcpyAsync(out_forced + r0, ts.forced, n * sizeof(int), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && flt && out_thr) e = hipMemcpyAsync(out_thr + r0, sd.thr, n * sizeof(float), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && flt && out_kept) e = hipMemcpyAsync(out_kept + r0, sd.kept, n * sizeof(int), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);          // (the host staging of this chunk is reused by the next)
-        if (e != hipSuccess) { ctx->err = std::string(who + ": ") + hipGetErrorString(e); rc = WM_ERR_HIP; break; }
-        if (!wm_rules_on(ts)) std::fill(out_forced + r0, out_forced + r0 + n, 0);
-        if (!flt && out_thr) std::fill(out_thr + r0, out_thr + r0 + n, -INFINITY);
-        if (!flt && out_kept) std::fill(out_kept + r0, out_kept + r0 + n, -1);
-    }
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(buf);
-    return rc;
+        WM_TAP_HIP(s, hipMemcpyAsync(ctx->samp_keys, keys + r0, n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        if (ts.on) WM_TAP_HIP(s, hipMemcpyAsync(ts.ver, recs.data(), n * sizeof(int4), hipMemcpyHostToDevice, st));
+        if (int rc = wm_sample_launch(ctx, g, ts, sd, s.len, n, 0, 1)) return rc;
+        WM_TAP_HIP(s, hipMemcpyAsync(out_token + r0, ctx->amax, n * sizeof(int), hipMemcpyDeviceToHost, st));
+        WM_TAP_HIP(s, hipMemcpyAsync(out_value + r0, sd.val, n * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (wm_rules_on(ts)) WM_TAP_HIP(s, hipMemcpyAsync(out_forced + r0, ts.forced, n * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (flt && out_thr) WM_TAP_HIP(s, hipMemcpyAsync(out_thr + r0, sd.thr, n * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (flt && out_kept) WM_TAP_HIP(s, hipMemcpyAsync(out_kept + r0, sd.kept, n * sizeof(int), hipMemcpyDeviceToHost, st));
+        return WM_OK;
+    });
 }
 extern "C" int wm_sample_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* tsp, const wm_sample_params* sp, int R,
                               const float* logits, const int32_t* prefixes, int Tmax, const int32_t* lens, const uint64_t* keys,

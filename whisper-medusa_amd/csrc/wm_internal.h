@@ -340,6 +340,7 @@ struct wm_ctx {
 
     // ---- token timestamps (wm_align.hip): workspace of the last wm_token_timestamps call, allocated on first use ----
     struct wm_align_state* align = nullptr;
+    DevBuf<int> tap_buf;            // parity taps: a row group's prefixes and lengths (wm_tap_stage below); grows on first use, freed with the context
     struct wm_score_state* score = nullptr;     // token log-probabilities (wm_score.hip): row descriptors, slice partials and outputs, allocated on first use
     bool replay = false;            // a teacher-forced replay pass is being enqueued: the cross-q launch must leave its fp32 rows in qbuf (no WM_FUSE_CQ)
 };
@@ -425,6 +426,79 @@ struct wm_scalars_swap {
     wm_scalars_swap(const wm_scalars_swap&) = delete;
     ~wm_scalars_swap() { ctx->gp = gp; ctx->ts = ts; }
 };
-// timestamp parity tap (wm_select_rows): R <= 15 rows already in ctx->logits, probe tokens in cand[1 .. R], cur_len in L[0];
+// timestamp parity tap (wm_select_rows): R <= WM_TAP_ROWS rows already in ctx->logits, probe tokens in cand[1 .. R], cur_len in L[0];
 // prefixes DEV [R][Tmax], lengths DEV [R]
 int wm_dec_select_rows(wm_ctx* ctx, const int* pre_dev, const int* len_dev, int R, int Tmax);
+
+// ---- parity taps: one row-group driver --------------------------------------------------------------------------------------
+// Rows per group of a tap.  15, not 16: wm_dec_select_rows treats a group as ONE stream of R + 1 rows with the probe tokens in cand[1 .. R], and a
+// stream's pass carries at most 16 rows.  (wm_score_rows / wm_topk_rows take ctx->Rcap rows per group: what the logits scratch holds.)
+constexpr int WM_TAP_ROWS = 15;
+
+// n caller-given rows [n][V] (HOST) -> rows [0, n) of ctx->logits at the Vpad stride
+static inline hipError_t wm_tap_upload_logits(wm_ctx* ctx, const float* rows, int n)
+{
+    return hipMemcpy2DAsync(ctx->logits, (size_t)ctx->Vpad * sizeof(float), rows, (size_t)ctx->V * sizeof(float), (size_t)ctx->V * sizeof(float), n,
+                            hipMemcpyHostToDevice, ctx->stream);
+}
+// The one range check of a tap's lens: every lens[r] in [1, Tmax], or in [1, min(Tmax, n_tgt)] with cap_n_tgt.  also_ok / also: a second condition
+// of the call reported in the same sentence (wm_select_rows: its probe tokens)
+static inline int wm_tap_check_lens(wm_ctx* ctx, const char* who, const int32_t* lens, int R, int Tmax, bool cap_n_tgt, bool also_ok = true, const char* also = "")
+{
+    const int hi = cap_n_tgt ? std::min(Tmax, ctx->Tmax) : Tmax;
+    bool ok = also_ok;
+    for (int r = 0; r < R; ++r) ok = ok && lens[r] >= 1 && lens[r] <= hi;
+    if (ok) return WM_OK;
+    ctx->err = std::string(who) + ": lens must be in [1, " + (cap_n_tgt ? "min(Tmax, n_tgt)" : "Tmax") + "]" + also;
+    return WM_ERR_ARG;
+}
+// timestamp state of the sampled tokens ids[from:to] (from < 0: 0) on top of `st` (host: wm_decode_begin_ts and the taps)
+static inline int4 ts_fold_ids(int4 st, const int32_t* ids, int from, int to, int tb)
+{
+    for (int t = std::max(from, 0); t < to; ++t) st = ts_fold(st, ids[t], tb);
+    return st;
+}
+
+// The staging of one tap call: the call's name for its HIP errors, the group capacity, and the device copy of a group's prefixes and lengths in
+// ctx->tap_buf — ONE layout: [cap][Tmax] ids, behind them [cap] lengths, behind those `extra` ints of the tap's own.
+struct wm_tap_stage {
+    wm_ctx* ctx; const char* who; int Tmax, cap;
+    int *pre = nullptr, *len = nullptr, *extra = nullptr;
+    int fail(hipError_t e) const
+    {
+        if (e == hipSuccess) return WM_OK;
+        ctx->err = std::string(who) + ": " + hipGetErrorString(e);
+        return WM_ERR_HIP;
+    }
+    int reserve(size_t n_extra = 0)         // (a tap without prefixes, wm_lang_pick_rows, does not call it: pre / len stay null)
+    {
+        if (int rc = fail(ctx->tap_buf.reserve((size_t)cap * Tmax + cap + n_extra))) return rc;
+        pre = ctx->tap_buf; len = pre + (size_t)cap * Tmax; extra = len + cap;
+        return WM_OK;
+    }
+    // rows [r0, r0 + n) of the call -> rows [0, n) of ctx->logits, pre and len (prefixes / lens NULL: none)
+    hipError_t upload(int r0, int n, const float* logits, const int32_t* prefixes, const int32_t* lens) const
+    {
+        hipError_t e = wm_tap_upload_logits(ctx, logits + (size_t)r0 * ctx->V, n);
+        if (e == hipSuccess && prefixes) e = hipMemcpyAsync(pre, prefixes + (size_t)r0 * Tmax, (size_t)n * Tmax * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess && lens) e = hipMemcpyAsync(len, lens + r0, n * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
+        return e;
+    }
+};
+#define WM_TAP_HIP(stage, expr) do { if (int _rc = (stage).fail(expr)) return _rc; } while (0)
+// The one loop over a tap's row groups: upload a group, body(r0, n) — the tap's own uploads, launches and downloads, enqueued; returns WM_OK or
+// its error —, then the stream is awaited, because the next group reuses the staging (the device buffers and the body's host vectors).  Stops at
+// the first error; returns with the stream idle.
+template <class Body>
+static int wm_tap_groups(const wm_tap_stage& s, int R, const float* logits, const int32_t* prefixes, const int32_t* lens, Body body)
+{
+    int rc = WM_OK;
+    for (int r0 = 0; r0 < R && rc == WM_OK; r0 += s.cap) {
+        const int n = std::min(s.cap, R - r0);
+        rc = s.fail(s.upload(r0, n, logits, prefixes, lens));
+        if (rc == WM_OK) rc = body(r0, n);
+        if (rc == WM_OK) rc = s.fail(hipStreamSynchronize(s.ctx->stream));
+    }
+    if (rc) (void)hipStreamSynchronize(s.ctx->stream);
+    return rc;
+}

@@ -106,19 +106,10 @@ extern "C" int wm_lang_pick_rows(wm_ctx* ctx, int R, const float* logits, const 
     if (int rc = lang_ids_upload(ctx, "wm_lang_pick_rows", lang_ids, n)) return rc;
     hipStream_t st = ctx->stream;
     wm_decode_invalidate(ctx);
-    const int CH = 15;
-    int rc = WM_OK;
-    for (int r0 = 0; r0 < R && rc == WM_OK; r0 += CH) {
-        const int nr = std::min(CH, R - r0);
-        hipError_t e = hipMemcpy2DAsync(ctx->logits, (size_t)ctx->Vpad * sizeof(float), logits + (size_t)r0 * ctx->V, (size_t)ctx->V * sizeof(float),
-                                        (size_t)ctx->V * sizeof(float), nr, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) { ctx->err = std::string("wm_lang_pick_rows: ") + hipGetErrorString(e); rc = WM_ERR_HIP; break; }
-        rc = lang_pick_launch(ctx, nr, n);
-        if (rc) break;
-        e = hipMemcpyAsync(out + r0, ctx->lang_out, nr * sizeof(int), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);          // (the staging of this chunk is reused by the next)
-        if (e != hipSuccess) { ctx->err = std::string("wm_lang_pick_rows: ") + hipGetErrorString(e); rc = WM_ERR_HIP; break; }
-    }
-    (void)hipStreamSynchronize(st);
-    return rc;
+    const wm_tap_stage s{ctx, "wm_lang_pick_rows", 0, WM_TAP_ROWS};       // rows alone: no prefixes, no lengths
+    return wm_tap_groups(s, R, logits, nullptr, nullptr, [&](int r0, int nr) {
+        if (int rc = lang_pick_launch(ctx, nr, n)) return rc;
+        WM_TAP_HIP(s, hipMemcpyAsync(out + r0, ctx->lang_out, nr * sizeof(int), hipMemcpyDeviceToHost, st));
+        return WM_OK;
+    });
 }

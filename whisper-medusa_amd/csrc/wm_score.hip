@@ -27,7 +27,7 @@
 struct wm_score_state {
     DevBuf<int4> desc, rec, sst;    // [rows] {logits row, cur_len (< 0: raw row), target (< 0: skip), out index}, records; [maxB] fold state
     DevBuf<float> p1, p1t, out;     // [rows][SEL_SP][4] text / timestamp partials; outputs
-    DevBuf<int> lens, npr, ibuf;    // [maxB] each; tap: prefixes + lengths + targets
+    DevBuf<int> lens, npr;          // [maxB] each
     DevBuf<int> rpf;                // [rows] repetition rules: the target's bits (k_score1 -> k_score2)
     DevBuf<float> cv, tlp;          // alternatives: [rows][SEL_SP][WM_TOPK_MAX] slice candidates' values; [outputs][k] log-probabilities
     DevBuf<int> ci, cn, tid, trk;   // their ids, [rows][SEL_SP] counts of elements ahead of the target; [outputs][k] ids, [outputs] ranks
@@ -39,7 +39,7 @@ void wm_score_free(wm_ctx* ctx)
     ctx->score = nullptr;
 }
 
-static int score_reserve(wm_ctx* ctx, size_t rows, size_t nout, size_t nb, size_t nibuf)
+static int score_reserve(wm_ctx* ctx, size_t rows, size_t nout, size_t nb)
 {
     if (!ctx->score) ctx->score = new wm_score_state();
     wm_score_state* sc = ctx->score;
@@ -47,7 +47,6 @@ static int score_reserve(wm_ctx* ctx, size_t rows, size_t nout, size_t nb, size_
     WM_HIP(sc->p1.reserve(rows * SEL_SP * 4)); WM_HIP(sc->p1t.reserve(rows * SEL_SP * 4));
     WM_HIP(sc->out.reserve(nout)); WM_HIP(sc->rpf.reserve(rows));
     WM_HIP(sc->lens.reserve(nb)); WM_HIP(sc->npr.reserve(nb)); WM_HIP(sc->sst.reserve(nb));
-    WM_HIP(sc->ibuf.reserve(nibuf));
     return WM_OK;
 }
 static int topk_reserve(wm_ctx* ctx, size_t rows, size_t nout)
@@ -457,7 +456,7 @@ static int score_tokens(wm_ctx* ctx, const char* who_c, const wm_gen_params* gp,
     WM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     if (int rc = score_setup(ctx, gp, tsp, who_c, &c.g, &c.ts)) return rc;
-    if (int rc = score_reserve(ctx, (size_t)B * 17, (size_t)B * Tmax + B, (size_t)B, 0)) return rc;
+    if (int rc = score_reserve(ctx, (size_t)B * 17, (size_t)B * Tmax + B, (size_t)B)) return rc;
     if (topk > 0) if (int rc = topk_reserve(ctx, (size_t)B * 17, (size_t)B * Tmax)) return rc;
     wm_score_state* sc = ctx->score;
     // the replay overwrites the decode state (ids, kvlen, self K/V, the processors' tables): begin again afterwards
@@ -522,40 +521,34 @@ static int score_rows(wm_ctx* ctx, const char* who_c, const wm_gen_params* gp, c
     if (!gp || R < 1 || !logits || !prefixes || Tmax < 1 || !lens || !targets || (topk ? !top_ids || !top_logprobs || !ranks : !out_logprob)) {
         ctx->err = who + ": bad arguments"; return WM_ERR_ARG;
     }
-    for (int r = 0; r < R; ++r) {
-        if (lens[r] < 1 || lens[r] > Tmax || lens[r] > ctx->Tmax) { ctx->err = who + ": lens must be in [1, min(Tmax, n_tgt)]"; return WM_ERR_ARG; }
+    if (int rc = wm_tap_check_lens(ctx, who_c, lens, R, Tmax, true)) return rc;
+    for (int r = 0; r < R; ++r)
         if (targets[r] < 0 || targets[r] >= ctx->V) { ctx->err = who + ": target outside the vocabulary (row " + std::to_string(r) + ")"; return WM_ERR_ARG; }
-    }
     WM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     GenDev g{}; TsDev ts{};
     if (int rc = score_setup(ctx, gp, tsp, who_c, &g, &ts)) return rc;
     wm_decode_invalidate(ctx);       // (the processors' tables are the tap's now)
-    const int G = ctx->Rcap;                   // rows per group: what the logits scratch holds
-    if (int rc = score_reserve(ctx, (size_t)G, (size_t)G, 0, (size_t)G * Tmax + 2 * G)) return rc;
+    const int G = ctx->Rcap;                   // rows per group: what the logits scratch holds (not WM_TAP_ROWS)
+    if (int rc = score_reserve(ctx, (size_t)G, (size_t)G, 0)) return rc;
     if (topk > 0) if (int rc = topk_reserve(ctx, (size_t)G, (size_t)G)) return rc;
     wm_score_state* sc = ctx->score;
-    for (int r0 = 0; r0 < R; r0 += G) {
-        const int n = std::min(G, R - r0);
-        int* pre = sc->ibuf; int* len = pre + (size_t)G * Tmax; int* tgt = len + G;
-        WM_HIP(hipMemcpyAsync(pre, prefixes + (size_t)r0 * Tmax, (size_t)n * Tmax * sizeof(int), hipMemcpyHostToDevice, st));
-        WM_HIP(hipMemcpyAsync(len, lens + r0, n * sizeof(int), hipMemcpyHostToDevice, st));
-        WM_HIP(hipMemcpyAsync(tgt, targets + r0, n * sizeof(int), hipMemcpyHostToDevice, st));
-        WM_HIP(hipMemcpy2DAsync(ctx->logits, (size_t)ctx->Vpad * sizeof(float), logits + (size_t)r0 * ctx->V, (size_t)ctx->V * sizeof(float),
-                                (size_t)ctx->V * sizeof(float), n, hipMemcpyHostToDevice, st));
-        ts.rp_ids = pre; ts.rp_stride = Tmax;           // repetition rules: the rows' own prefixes
-        hipLaunchKernelGGL(k_score_tap_build, dim3((n + 63) / 64), dim3(64), 0, st, pre, len, tgt, n, Tmax, g, ts, sc->desc, sc->rec);
-        WM_HIP(hipGetLastError());
+    wm_tap_stage s{ctx, who_c, Tmax, G};
+    if (int rc = s.reserve(G)) return rc;           // extra: the group's targets
+    ts.rp_ids = s.pre; ts.rp_stride = Tmax;         // repetition rules: the rows' own prefixes
+    return wm_tap_groups(s, R, logits, prefixes, lens, [&](int r0, int n) {
+        WM_TAP_HIP(s, hipMemcpyAsync(s.extra, targets + r0, n * sizeof(int), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_score_tap_build, dim3((n + 63) / 64), dim3(64), 0, st, s.pre, s.len, s.extra, n, Tmax, g, ts, sc->desc, sc->rec);
+        WM_TAP_HIP(s, hipGetLastError());
         if (int rc = score_launch(ctx, g, ts, n, topk)) return rc;
         if (topk > 0) {
-            WM_HIP(hipMemcpyAsync(top_ids + (size_t)r0 * topk, sc->tid, (size_t)n * topk * sizeof(int), hipMemcpyDeviceToHost, st));
-            WM_HIP(hipMemcpyAsync(top_logprobs + (size_t)r0 * topk, sc->tlp, (size_t)n * topk * sizeof(float), hipMemcpyDeviceToHost, st));
-            WM_HIP(hipMemcpyAsync(ranks + r0, sc->trk, n * sizeof(int), hipMemcpyDeviceToHost, st));
+            WM_TAP_HIP(s, hipMemcpyAsync(top_ids + (size_t)r0 * topk, sc->tid, (size_t)n * topk * sizeof(int), hipMemcpyDeviceToHost, st));
+            WM_TAP_HIP(s, hipMemcpyAsync(top_logprobs + (size_t)r0 * topk, sc->tlp, (size_t)n * topk * sizeof(float), hipMemcpyDeviceToHost, st));
+            WM_TAP_HIP(s, hipMemcpyAsync(ranks + r0, sc->trk, n * sizeof(int), hipMemcpyDeviceToHost, st));
         } else
-            WM_HIP(hipMemcpyAsync(out_logprob + r0, sc->out, n * sizeof(float), hipMemcpyDeviceToHost, st));
-        WM_HIP(hipStreamSynchronize(st));
-    }
-    return WM_OK;
+            WM_TAP_HIP(s, hipMemcpyAsync(out_logprob + r0, sc->out, n * sizeof(float), hipMemcpyDeviceToHost, st));
+        return WM_OK;
+    });
 }
 
 extern "C" int wm_score_rows(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestamp_params* tsp, int R, const float* logits,

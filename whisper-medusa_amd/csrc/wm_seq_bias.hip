@@ -181,8 +181,7 @@ extern "C" int wm_seq_bias_rows(wm_ctx* ctx, const wm_seq_bias_params* sb, int R
 {
     if (!ctx) return WM_ERR_ARG;
     if (!sb || R < 1 || !logits || !prefixes || Tmax < 1 || !lens || !out) { ctx->err = "wm_seq_bias_rows: bad arguments"; return WM_ERR_ARG; }
-    for (int r = 0; r < R; ++r)
-        if (lens[r] < 1 || lens[r] > Tmax) { ctx->err = "wm_seq_bias_rows: lens must be in [1, Tmax]"; return WM_ERR_ARG; }
+    if (int rc = wm_tap_check_lens(ctx, "wm_seq_bias_rows", lens, R, Tmax, false)) return rc;
     SeqBiasTable t;
     if (int rc = seq_bias_lower(ctx, "wm_seq_bias_rows", sb, &t)) return rc;
     WM_HIP(hipSetDevice(ctx->device));
@@ -190,28 +189,17 @@ extern "C" int wm_seq_bias_rows(wm_ctx* ctx, const wm_seq_bias_params* sb, int R
     wm_seq_bias_state* S = nullptr;
     if (int rc = seq_bias_state(ctx, &S)) return rc;
     wm_decode_invalidate(ctx);
+    wm_tap_stage s{ctx, "wm_seq_bias_rows", Tmax, WM_TAP_ROWS};
+    if (int rc = s.reserve()) return rc;
     if (int rc = seq_bias_upload(ctx, *S, t)) return rc;
     const SeqBiasDev d = seq_bias_dev(*S, t.ngroups());
-    const int CH = 15;
-    int* buf = nullptr;
-    WM_HIP(hipMalloc(reinterpret_cast<void**>(&buf), ((size_t)CH * Tmax + CH) * sizeof(int)));
-    int rc = WM_OK;
-    for (int r0 = 0; r0 < R && rc == WM_OK; r0 += CH) {
-        const int n = std::min(CH, R - r0);
-        hipError_t e = hipMemcpyAsync(buf, prefixes + (size_t)r0 * Tmax, (size_t)n * Tmax * sizeof(int), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(buf + (size_t)CH * Tmax, lens + r0, n * sizeof(int), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpy2DAsync(ctx->logits, (size_t)ctx->Vpad * sizeof(float), logits + (size_t)r0 * ctx->V,
-                                                  (size_t)ctx->V * sizeof(float), (size_t)ctx->V * sizeof(float), n, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) { ctx->err = std::string("wm_seq_bias_rows: ") + hipGetErrorString(e); rc = WM_ERR_HIP; break; }
-        rc = wm_seq_bias_launch(ctx, d, buf, Tmax, buf + (size_t)CH * Tmax, Tmax, n);
-        if (rc) break;
-        e = hipMemcpy2DAsync(out + (size_t)r0 * ctx->V, (size_t)ctx->V * sizeof(float), ctx->logits, (size_t)ctx->Vpad * sizeof(float),
-                             (size_t)ctx->V * sizeof(float), n, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);          // (the staging of this chunk is reused by the next)
-        if (e != hipSuccess) { ctx->err = std::string("wm_seq_bias_rows: ") + hipGetErrorString(e); rc = WM_ERR_HIP; break; }
-    }
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(buf);
-    if (S->set) { if (int rc2 = seq_bias_upload(ctx, *S, S->table)) return rc ? rc : rc2; }      // the context's own table back in place
+    const int rc = wm_tap_groups(s, R, logits, prefixes, lens, [&](int r0, int n) {
+        if (int rc = wm_seq_bias_launch(ctx, d, s.pre, Tmax, s.len, Tmax, n)) return rc;
+        WM_TAP_HIP(s, hipMemcpy2DAsync(out + (size_t)r0 * ctx->V, (size_t)ctx->V * sizeof(float), ctx->logits, (size_t)ctx->Vpad * sizeof(float),
+                                       (size_t)ctx->V * sizeof(float), n, hipMemcpyDeviceToHost, st));
+        return WM_OK;
+    });
+    // quirk, kept: the tap borrowed the device tables, so the context's own sticky table goes back in place — on the error path too
+    if (S->set) { if (int rc2 = seq_bias_upload(ctx, *S, S->table)) return rc ? rc : rc2; }
     return rc;
 }

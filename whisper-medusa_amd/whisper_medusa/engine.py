@@ -216,6 +216,22 @@ def _i32arr(v: Sequence[int]):
     return a
 
 
+def _ip(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _fp(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _u64p(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+
+def _keys64(keys: Sequence[int]) -> np.ndarray:
+    return np.ascontiguousarray([int(k) & (2 ** 64 - 1) for k in keys], dtype=np.uint64)
+
+
 class Engine:
     """One context = one GPU.  ``blob`` is the packed parameter tensor (uint8, on that GPU)."""
 
@@ -392,8 +408,8 @@ class Engine:
         if stream_keys is None:
             sp = WmSampleParams(float(temperature), int(seed) & (2 ** 64 - 1), None, int(n_keys or 0))
         else:
-            keys = np.ascontiguousarray([int(k) & (2 ** 64 - 1) for k in stream_keys], dtype=np.uint64)
-            sp = WmSampleParams(float(temperature), int(seed) & (2 ** 64 - 1), keys.ctypes.data_as(C.POINTER(C.c_uint64)), len(keys))
+            keys = _keys64(stream_keys)
+            sp = WmSampleParams(float(temperature), int(seed) & (2 ** 64 - 1), _u64p(keys), len(keys))
         self._check(self.lib.wm_set_sampling(self.h, C.byref(sp)), "wm_set_sampling")
 
     def _set_sampling(self, gp: GenParams, B: int) -> None:
@@ -502,31 +518,21 @@ class Engine:
     def lang_pick_rows(self, logits: np.ndarray, lang_ids: Sequence[int]) -> np.ndarray:
         """Language-pick parity tap (wm_lang_pick_rows): rows ``logits [R, V]`` through k_lang_pick alone.  Returns numpy int32 [R]: the id of
         ``lang_ids`` with the largest value in the row, among equal values the smallest id."""
-        x = np.ascontiguousarray(logits, dtype=np.float32)
-        if x.ndim != 2 or x.shape[1] != self.cfg.vocab_size:
-            raise ValueError("lang_pick_rows: logits must be [R, vocab]")
+        x, R, _, _, _ = self._tap_rows("lang_pick_rows", logits)
         ids = np.ascontiguousarray([int(t) for t in lang_ids], dtype=np.int32)
-        out = np.zeros(x.shape[0], dtype=np.int32)
-        i32p = C.POINTER(C.c_int32)
+        out = np.zeros(R, dtype=np.int32)
         self._kv_stamp = object()
-        self._check(self.lib.wm_lang_pick_rows(self.h, x.shape[0], x.ctypes.data_as(C.POINTER(C.c_float)), ids.ctypes.data_as(i32p), len(ids),
-                                               out.ctypes.data_as(i32p)), "wm_lang_pick_rows")
+        self._check(self.lib.wm_lang_pick_rows(self.h, R, _fp(x), _ip(ids), len(ids), _ip(out)), "wm_lang_pick_rows")
         return out
 
     def seq_bias_rows(self, entries, logits: np.ndarray, prefixes: Sequence[Sequence[int]]) -> np.ndarray:
         """Sequence-bias parity tap (wm_seq_bias_rows): rows ``logits [R, V]``, row r under ``prefixes[r]``, through k_seq_bias alone.  Returns the
         edited rows, numpy float32 [R, V]."""
-        x = np.ascontiguousarray(logits, dtype=np.float32)
-        R, V = x.shape
-        if V != self.cfg.vocab_size or len(prefixes) != R:
-            raise ValueError("seq_bias_rows: logits must be [R, vocab] with one prefix per row")
-        pre, lens, Tmax, _ = self._pack_ids(prefixes)
+        x, R, pre, lens, Tmax = self._tap_rows("seq_bias_rows", logits, prefixes)
         out = np.zeros_like(x)
         sb, _keep = self._seq_bias_struct(entries)
-        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
         self._kv_stamp = object()
-        self._check(self.lib.wm_seq_bias_rows(self.h, C.byref(sb), R, x.ctypes.data_as(f32p), pre.ctypes.data_as(i32p), Tmax, lens.ctypes.data_as(i32p),
-                                              out.ctypes.data_as(f32p)), "wm_seq_bias_rows")
+        self._check(self.lib.wm_seq_bias_rows(self.h, C.byref(sb), R, _fp(x), _ip(pre), Tmax, _ip(lens), _fp(out)), "wm_seq_bias_rows")
         return out
 
     def beam_result(self, clip: int, rank: int):
@@ -563,18 +569,13 @@ class Engine:
                  beam_idx=np.zeros((S, G * n), np.int32), steps=np.zeros(G, np.int32), fin_ids=np.zeros((G, n, Tmax), np.int32),
                  fin_len=np.zeros((G, n), np.int32), fin_score=np.zeros((G, n), np.float32), fin_set=np.zeros((G, n), np.int32),
                  run_ids=np.zeros((G * n, Tmax), np.int32), run_len=np.zeros(G * n, np.int32), run_score=np.zeros(G * n, np.float32))
-        g, _keep = self._gen_struct(gp)
-        self._set_repeat_rules(gp)
-        ts = self._ts_struct(gp) if gp.timestamps else None
+        g, ts, _keep = self._proc_args(gp)
         bp = self._beam_struct(num_beams, length_penalty, early_stopping)
-        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
-        ip = lambda a: a.ctypes.data_as(i32p)      # noqa: E731
-        fp = lambda a: a.ctypes.data_as(f32p)      # noqa: E731
         self._kv_stamp = object()
-        self._check(self.lib.wm_beam_rows(self.h, C.byref(g), C.byref(ts) if ts is not None else None, C.byref(bp), G, S, fp(x), ip(pre), Tmax, plen,
-                                          None if init is None else fp(init), fp(o["cand_val"]), ip(o["cand_beam"]), ip(o["cand_tok"]),
-                                          ip(o["beam_idx"]), ip(o["steps"]), ip(o["fin_ids"]), ip(o["fin_len"]), fp(o["fin_score"]), ip(o["fin_set"]),
-                                          ip(o["run_ids"]), ip(o["run_len"]), fp(o["run_score"])), "wm_beam_rows")
+        self._check(self.lib.wm_beam_rows(self.h, g, ts, C.byref(bp), G, S, _fp(x), _ip(pre), Tmax, plen,
+                                          None if init is None else _fp(init), _fp(o["cand_val"]), _ip(o["cand_beam"]), _ip(o["cand_tok"]),
+                                          _ip(o["beam_idx"]), _ip(o["steps"]), _ip(o["fin_ids"]), _ip(o["fin_len"]), _fp(o["fin_score"]), _ip(o["fin_set"]),
+                                          _ip(o["run_ids"]), _ip(o["run_len"]), _fp(o["run_score"])), "wm_beam_rows")
         return o
 
     def decode(self, gp: GenParams, B: int, max_iters: int = 1 << 30, on_iteration=None) -> List[List[int]]:
@@ -622,72 +623,67 @@ class Engine:
         npr = None if n_prompt is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n_prompt, dtype=np.int32), (B,)))
         return tok, lens, Tmax, npr
 
+    def _tap_rows(self, name: str, logits: np.ndarray, prefixes: Optional[Sequence[Sequence[int]]] = None, **per_row):
+        """The prelude of a row tap: ``logits [R, vocab]`` -> (contiguous float32 rows, R, the packed prefixes, their lengths, Tmax; ``_pack_ids``).
+        ``per_row``: what else comes one per row, under its word in the error text (``stream_key=keys``).  Without prefixes: None, None, 0."""
+        x = np.ascontiguousarray(logits, dtype=np.float32)
+        items = per_row if prefixes is None else dict(prefix=prefixes, **per_row)
+        if x.ndim != 2 or x.shape[1] != self.cfg.vocab_size or any(len(v) != x.shape[0] for v in items.values()):
+            words = " and ".join("one " + w.replace("_", " ") for w in items)
+            raise ValueError(f"{name}: logits must be [R, vocab]" + (f" with {words} per row" if items else ""))
+        pre, lens, Tmax = (None, None, 0) if prefixes is None else self._pack_ids(prefixes)[:3]
+        return x, x.shape[0], pre, lens, Tmax
+
+    def _proc_args(self, gp: GenParams, ts: Optional[bool] = None):
+        """The logits processors of a tap / scoring call: sets the context's repetition rules from ``gp``, then -> (byref wm_gen_params, byref
+        wm_timestamp_params or None, what the two point into: keep it alive over the call).  ``ts``: pass the timestamp struct; None = ``gp.timestamps``
+        (the one exception is select_rows)."""
+        g, keep = self._gen_struct(gp)
+        self._set_repeat_rules(gp)
+        t = self._ts_struct(gp) if (gp.timestamps if ts is None else ts) else None
+        return C.byref(g), None if t is None else C.byref(t), (g, t, keep)
+
     def select_rows(self, gp: GenParams, logits: np.ndarray, prefixes: Sequence[Sequence[int]], probe_tokens: Sequence[int]) -> dict:
         """Timestamp parity tap (wm_select_rows): rows ``logits [R, V]`` as verify rows with the given prefixes, through the decode loop's
         state fold and select kernels.  Returns numpy arrays argmax, p_probe, entropy, ts_forced (the log-softmax decision masked all text)."""
-        x = np.ascontiguousarray(logits, dtype=np.float32)
-        R, V = x.shape
-        if V != self.cfg.vocab_size or len(prefixes) != R or len(probe_tokens) != R:
-            raise ValueError("select_rows: logits must be [R, vocab] with one prefix and one probe token per row")
-        pre, lens, Tmax, _ = self._pack_ids(prefixes)
+        x, R, pre, lens, Tmax = self._tap_rows("select_rows", logits, prefixes, probe_token=probe_tokens)
         probe = np.ascontiguousarray(probe_tokens, dtype=np.int32)
         am = np.zeros(R, np.int32); pp = np.zeros(R, np.float32); H = np.zeros(R, np.float32); fo = np.zeros(R, np.int32)
-        g, _keep = self._gen_struct(gp)
-        self._set_repeat_rules(gp)
         # (the repetition rules alone: no timestamp argument; otherwise the timestamp rules as ever)
-        ts = self._ts_struct(gp) if (gp.timestamps or not gp.repeat_rules) else None
-        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        g, ts, _keep = self._proc_args(gp, ts=gp.timestamps or not gp.repeat_rules)
         self._kv_stamp = object()
-        self._check(self.lib.wm_select_rows(self.h, C.byref(g), C.byref(ts) if ts is not None else None, R, x.ctypes.data_as(f32p), pre.ctypes.data_as(i32p), Tmax,
-                                            lens.ctypes.data_as(i32p), probe.ctypes.data_as(i32p), am.ctypes.data_as(i32p),
-                                            pp.ctypes.data_as(f32p), H.ctypes.data_as(f32p), fo.ctypes.data_as(i32p)), "wm_select_rows")
+        self._check(self.lib.wm_select_rows(self.h, g, ts, R, _fp(x), _ip(pre), Tmax, _ip(lens), _ip(probe), _ip(am), _fp(pp), _fp(H), _ip(fo)),
+                    "wm_select_rows")
         return dict(argmax=am, p_probe=pp, entropy=H, ts_forced=fo)
 
     def sample_rows(self, gp: GenParams, logits: np.ndarray, prefixes: Sequence[Sequence[int]], keys: Sequence[int], temperature: float,
                     seed: int) -> dict:
         """Sampling parity tap (wm_sample_rows): rows ``logits [R, V]``, row r under its own prefix at position ``len(prefixes[r])`` with stream
         key ``keys[r]``, through k_sample1 / k_sample_fin.  Returns numpy arrays token, value (the winner's v / T + g), ts_forced."""
-        x = np.ascontiguousarray(logits, dtype=np.float32)
-        R, V = x.shape
-        if V != self.cfg.vocab_size or len(prefixes) != R or len(keys) != R:
-            raise ValueError("sample_rows: logits must be [R, vocab] with one prefix and one stream key per row")
-        pre, lens, Tmax, _ = self._pack_ids(prefixes)
-        k64 = np.ascontiguousarray([int(k) & (2 ** 64 - 1) for k in keys], dtype=np.uint64)
+        x, R, pre, lens, Tmax = self._tap_rows("sample_rows", logits, prefixes, stream_key=keys)
+        k64 = _keys64(keys)
         tok = np.zeros(R, np.int32); val = np.zeros(R, np.float32); fo = np.zeros(R, np.int32)
-        g, _keep = self._gen_struct(gp)
-        self._set_repeat_rules(gp)
-        ts = self._ts_struct(gp) if gp.timestamps else None
+        g, ts, _keep = self._proc_args(gp)
         sp = WmSampleParams(float(temperature), int(seed) & (2 ** 64 - 1), None, 0)
-        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
         self._kv_stamp = object()
-        self._check(self.lib.wm_sample_rows(self.h, C.byref(g), C.byref(ts) if ts is not None else None, C.byref(sp), R, x.ctypes.data_as(f32p),
-                                            pre.ctypes.data_as(i32p), Tmax, lens.ctypes.data_as(i32p), k64.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                            tok.ctypes.data_as(i32p), val.ctypes.data_as(f32p), fo.ctypes.data_as(i32p)), "wm_sample_rows")
+        self._check(self.lib.wm_sample_rows(self.h, g, ts, C.byref(sp), R, _fp(x), _ip(pre), Tmax, _ip(lens), _u64p(k64), _ip(tok), _fp(val), _ip(fo)),
+                    "wm_sample_rows")
         return dict(token=tok, value=val, ts_forced=fo)
 
     def filter_rows(self, gp: GenParams, logits: np.ndarray, prefixes: Sequence[Sequence[int]], keys: Sequence[int], temperature: float,
                     seed: int, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0) -> dict:
         """Filter parity tap (wm_filter_rows): ``sample_rows`` with the top-k / top-p / min-p filter, through k_sample1 / k_filter_prep /
         k_filter_row.  Returns numpy arrays thr (the row's threshold; -inf: nothing cut), kept (ids at or above it), ts_forced, token, value."""
-        x = np.ascontiguousarray(logits, dtype=np.float32)
-        R, V = x.shape
-        if V != self.cfg.vocab_size or len(prefixes) != R or len(keys) != R:
-            raise ValueError("filter_rows: logits must be [R, vocab] with one prefix and one stream key per row")
-        pre, lens, Tmax, _ = self._pack_ids(prefixes)
-        k64 = np.ascontiguousarray([int(k) & (2 ** 64 - 1) for k in keys], dtype=np.uint64)
+        x, R, pre, lens, Tmax = self._tap_rows("filter_rows", logits, prefixes, stream_key=keys)
+        k64 = _keys64(keys)
         tok = np.zeros(R, np.int32); val = np.zeros(R, np.float32); fo = np.zeros(R, np.int32)
         thr = np.zeros(R, np.float32); kept = np.zeros(R, np.int32)
-        g, _keep = self._gen_struct(gp)
-        self._set_repeat_rules(gp)
-        ts = self._ts_struct(gp) if gp.timestamps else None
+        g, ts, _keep = self._proc_args(gp)
         sp = WmSampleParams(float(temperature), int(seed) & (2 ** 64 - 1), None, 0)
         f = WmSampleFilter(int(top_k), float(top_p), float(min_p))
-        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
         self._kv_stamp = object()
-        self._check(self.lib.wm_filter_rows(self.h, C.byref(g), C.byref(ts) if ts is not None else None, C.byref(sp), C.byref(f), R,
-                                            x.ctypes.data_as(f32p), pre.ctypes.data_as(i32p), Tmax, lens.ctypes.data_as(i32p),
-                                            k64.ctypes.data_as(C.POINTER(C.c_uint64)), thr.ctypes.data_as(f32p), kept.ctypes.data_as(i32p),
-                                            fo.ctypes.data_as(i32p), tok.ctypes.data_as(i32p), val.ctypes.data_as(f32p)), "wm_filter_rows")
+        self._check(self.lib.wm_filter_rows(self.h, g, ts, C.byref(sp), C.byref(f), R, _fp(x), _ip(pre), Tmax, _ip(lens), _u64p(k64), _fp(thr), _ip(kept),
+                                            _ip(fo), _ip(tok), _fp(val)), "wm_filter_rows")
         return dict(thr=thr, kept=kept, ts_forced=fo, token=tok, value=val)
 
     # ---- token-level timestamps (include/wm.h wm_token_timestamps) ---------------------------------
@@ -755,35 +751,22 @@ class Engine:
         want_ns = no_speech_token_id is not None and int(no_speech_token_id) >= 0
         nsp = np.zeros(B, dtype=np.float32)
         ms = C.c_float(0)
-        g, _keep = self._gen_struct(gp)
-        ts = self._ts_struct(gp) if gp.timestamps else None
+        g, ts, _keep = self._proc_args(gp)
         sp = WmScoreParams(int(no_speech_token_id) if want_ns else -1, int(sot_index))
-        self._set_repeat_rules(gp)
-        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
         self._kv_stamp = object()
-        self._check(self.lib.wm_score_tokens(self.h, C.byref(g), C.byref(ts) if ts is not None else None, C.byref(sp), B, tok.ctypes.data_as(i32p), Tmax,
-                                             lens.ctypes.data_as(i32p), npr.ctypes.data_as(i32p), out.ctypes.data_as(f32p),
-                                             nsp.ctypes.data_as(f32p) if want_ns else None, C.byref(ms)), "wm_score_tokens")
+        self._check(self.lib.wm_score_tokens(self.h, g, ts, C.byref(sp), B, _ip(tok), Tmax, _ip(lens), _ip(npr), _fp(out),
+                                             _fp(nsp) if want_ns else None, C.byref(ms)), "wm_score_tokens")
         return out, (nsp if want_ns else None), ms.value
 
     def score_rows(self, gp: GenParams, logits: np.ndarray, prefixes: Sequence[Sequence[int]], targets: Sequence[int]) -> np.ndarray:
         """Scoring parity tap (wm_score_rows): rows ``logits [R, V]``, each under its own prefix and length, through the scoring kernels only.
         Returns numpy float32 [R]: log_softmax(processed row)[target], -inf for a masked target."""
-        x = np.ascontiguousarray(logits, dtype=np.float32)
-        R, V = x.shape
-        if V != self.cfg.vocab_size or len(prefixes) != R or len(targets) != R:
-            raise ValueError("score_rows: logits must be [R, vocab] with one prefix and one target per row")
-        pre, lens, Tmax, _ = self._pack_ids(prefixes)
+        x, R, pre, lens, Tmax = self._tap_rows("score_rows", logits, prefixes, target=targets)
         tgt = np.ascontiguousarray(targets, dtype=np.int32)
         out = np.zeros(R, np.float32)
-        g, _keep = self._gen_struct(gp)
-        self._set_repeat_rules(gp)
-        ts = self._ts_struct(gp) if gp.timestamps else None
-        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        g, ts, _keep = self._proc_args(gp)
         self._kv_stamp = object()
-        self._check(self.lib.wm_score_rows(self.h, C.byref(g), C.byref(ts) if ts is not None else None, R, x.ctypes.data_as(f32p),
-                                           pre.ctypes.data_as(i32p), Tmax, lens.ctypes.data_as(i32p), tgt.ctypes.data_as(i32p),
-                                           out.ctypes.data_as(f32p)), "wm_score_rows")
+        self._check(self.lib.wm_score_rows(self.h, g, ts, R, _fp(x), _ip(pre), Tmax, _ip(lens), _ip(tgt), _fp(out)), "wm_score_rows")
         return out
 
     # ---- token alternatives (include/wm.h wm_score_tokens_topk; DESIGN.md §2g) -------------------------
@@ -803,39 +786,25 @@ class Engine:
         want_ns = no_speech_token_id is not None and int(no_speech_token_id) >= 0
         nsp = np.zeros(B, dtype=np.float32)
         ms = C.c_float(0)
-        g, _keep = self._gen_struct(gp)
-        ts = self._ts_struct(gp) if gp.timestamps else None
+        g, ts, _keep = self._proc_args(gp)
         sp = WmScoreParams(int(no_speech_token_id) if want_ns else -1, int(sot_index))
-        self._set_repeat_rules(gp)
-        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
         self._kv_stamp = object()
-        self._check(self.lib.wm_score_tokens_topk(self.h, C.byref(g), C.byref(ts) if ts is not None else None, C.byref(sp), B, tok.ctypes.data_as(i32p),
-                                                  Tmax, lens.ctypes.data_as(i32p), npr.ctypes.data_as(i32p), k, out.ctypes.data_as(f32p),
-                                                  nsp.ctypes.data_as(f32p) if want_ns else None, tid.ctypes.data_as(i32p), tlp.ctypes.data_as(f32p),
-                                                  rk.ctypes.data_as(i32p), C.byref(ms)), "wm_score_tokens_topk")
+        self._check(self.lib.wm_score_tokens_topk(self.h, g, ts, C.byref(sp), B, _ip(tok), Tmax, _ip(lens), _ip(npr), k, _fp(out),
+                                                  _fp(nsp) if want_ns else None, _ip(tid), _fp(tlp), _ip(rk), C.byref(ms)), "wm_score_tokens_topk")
         return out, (nsp if want_ns else None), tid, tlp, rk, ms.value
 
     def topk_rows(self, gp: GenParams, logits: np.ndarray, prefixes: Sequence[Sequence[int]], targets: Sequence[int], top_k: int):
         """Alternatives parity tap (wm_topk_rows): the rows of ``score_rows`` through the scoring and the top-k kernels.  Returns numpy
         (int32 [R, top_k] ids, float32 [R, top_k] log-probabilities, int32 [R] ranks)."""
-        x = np.ascontiguousarray(logits, dtype=np.float32)
-        R, V = x.shape
-        if V != self.cfg.vocab_size or len(prefixes) != R or len(targets) != R:
-            raise ValueError("topk_rows: logits must be [R, vocab] with one prefix and one target per row")
-        pre, lens, Tmax, _ = self._pack_ids(prefixes)
+        x, R, pre, lens, Tmax = self._tap_rows("topk_rows", logits, prefixes, target=targets)
         tgt = np.ascontiguousarray(targets, dtype=np.int32)
         k = int(top_k)
         tid = np.full((R, max(k, 1)), -1, dtype=np.int32)
         tlp = np.full((R, max(k, 1)), -np.inf, dtype=np.float32)
         rk = np.zeros(R, dtype=np.int32)
-        g, _keep = self._gen_struct(gp)
-        self._set_repeat_rules(gp)
-        ts = self._ts_struct(gp) if gp.timestamps else None
-        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        g, ts, _keep = self._proc_args(gp)
         self._kv_stamp = object()
-        self._check(self.lib.wm_topk_rows(self.h, C.byref(g), C.byref(ts) if ts is not None else None, R, x.ctypes.data_as(f32p),
-                                          pre.ctypes.data_as(i32p), Tmax, lens.ctypes.data_as(i32p), tgt.ctypes.data_as(i32p), k,
-                                          tid.ctypes.data_as(i32p), tlp.ctypes.data_as(f32p), rk.ctypes.data_as(i32p)), "wm_topk_rows")
+        self._check(self.lib.wm_topk_rows(self.h, g, ts, R, _fp(x), _ip(pre), Tmax, _ip(lens), _ip(tgt), k, _ip(tid), _fp(tlp), _ip(rk)), "wm_topk_rows")
         return tid, tlp, rk
 
     def tokens(self, stream: int) -> List[int]:
