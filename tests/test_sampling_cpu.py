@@ -175,8 +175,8 @@ def _run_fallback(temps, verdicts, B=4, sc_req=True, ids=None, seeks=None):
     feats = torch.arange(B, dtype=torch.float32)[:, None, None].expand(B, 2, 3).contiguous()
     gp = GenParams(prompt=[1], eos_token_id=2, pad_token_id=2)
     samp = dict(seed=99, ids=ids, seeks=seeks, temps=list(temps), fallback=True)
-    out = m._decode_with_fallback(eng, feats, gp, samp, {} if sc_req else None, encoded=False)
-    return m, eng, out
+    *out, beams, m.last_stats = m._decode_with_fallback(eng, feats, gp, samp, {} if sc_req else None, encoded=False)
+    return m, eng, tuple(out)
 
 
 def test_fallback_loop_follows_hf():

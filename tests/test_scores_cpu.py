@@ -11,7 +11,8 @@ import scores_ref as R
 from helpers import MedusaConfig, synth, clip_for, ROOT
 from oracle.whisper_medusa_oracle import Oracle, log_mel
 from whisper_medusa import scores as S
-from whisper_medusa.api import WhisperMedusaModel
+from whisper_medusa.api import WhisperMedusaModel, ResolvedCall, ShortResult
+from whisper_medusa.config import GenParams
 
 
 # ---- scores.py against transformers' static methods ---------------------------------------------------------------------------------------
@@ -73,19 +74,18 @@ def test_longform_skipped_window_leaves_nothing():
     lps = [[0.0] * P + [-0.1 * (i + 1)] * (len(w) - P) for i, w in enumerate(wins)]
 
     def stub(skip):
-        def inner(feats, **kw):
-            assert feats.shape[0] == 3 and "_sc_req" in kw
+        def inner(feats, call, language=None, **kw):
+            assert feats.shape[0] == 3 and call.sc_req is req and language == "en"
             rows = [list(w) for w in wins]
             lp = [list(x) for x in lps]
             for j in skip:
                 rows[j] = prompt + [eos]; lp[j] = [0.0] * (P + 1)
             T = max(len(r) for r in rows)
-            m._last_prompt = list(prompt)
-            m.last_stats = {"ms_token_logprobs": 1.0}
-            m._last_sc = dict(token_logprobs=torch.tensor([x + [0.0] * (T - len(x)) for x in lp]), avg_logprob=torch.tensor([-0.1, -0.2, -0.3]),
-                              compression_ratio=torch.ones(3), no_speech_prob=torch.tensor([0.1, 0.9, 0.1]),
-                              skipped=torch.tensor([j in skip for j in range(3)]), _want=True)
-            return torch.tensor([r + [eos] * (T - len(r)) for r in rows])
+            sc = dict(token_logprobs=torch.tensor([x + [0.0] * (T - len(x)) for x in lp]), avg_logprob=torch.tensor([-0.1, -0.2, -0.3]),
+                      compression_ratio=torch.ones(3), no_speech_prob=torch.tensor([0.1, 0.9, 0.1]),
+                      skipped=torch.tensor([j in skip for j in range(3)]), _want=True)
+            return ShortResult(rows, GenParams(prompt=list(prompt), eos_token_id=eos, pad_token_id=cfg.pad_token_id),
+                               {"ms_token_logprobs": 1.0}, scores=sc)
         return inner
 
     F = cfg.n_mel_frames
@@ -93,8 +93,8 @@ def test_longform_skipped_window_leaves_nothing():
     req = dict(want=True, no_speech_threshold=0.6, logprob_threshold=None, compression_ratio_threshold=None)
     outs = {}
     for name, skip in (("all", ()), ("mid", (1,))):
-        m.generate = stub(skip)
-        outs[name] = m._generate_longform(feats, dict(language="en", return_timestamps=True, return_segments=True, _sc_req=req, chunk_longform=True))
+        m._generate_short = stub(skip)
+        outs[name] = m._generate_longform(feats, ResolvedCall(sc_req=req, return_timestamps=True, return_segments=True), "en", False)
     full, mid = outs["all"], outs["mid"]
     gen = lambda w: [t for t in w[P:] if t != eos]      # noqa: E731
     assert full["sequences"][0].tolist() == prompt + gen(wins[0]) + gen(wins[1]) + gen(wins[2]) + [eos]

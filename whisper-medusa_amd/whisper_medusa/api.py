@@ -15,7 +15,7 @@ fact 2); ``extract_features(wav)`` computes the log-mel on the GPU (the referenc
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, field, replace
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -116,6 +116,11 @@ _LOWERABLE_PROCESSORS = ("SuppressTokensLogitsProcessor", "SuppressTokensAtBegin
 _LOWERABLE_CRITERIA = ("MaxLengthCriteria", "EosTokenCriteria")
 
 
+def _needs_host_processors(logits_processor) -> bool:
+    """Is a logits processor given that the engine cannot lower (lower_processors keeps it for the host loop)?"""
+    return any(type(p_).__name__ not in _LOWERABLE_PROCESSORS for p_ in (logits_processor or []))
+
+
 def _as_int_list(x) -> List[int]:
     if x is None:
         return []
@@ -154,9 +159,7 @@ def lower_processors(gp: GenParams, logits_processor, stopping_criteria) -> GenP
             # any other processor is a Python callable on the logits (the reference hands the list to HF, model.py:1106-1116): it runs on
             # the host between the engine's passes (WhisperMedusaModel._decode_host_processors: the reference's own loop structure,
             # one stream at a time, logits copied out after every pass).  Order as in HF: the defaults above first, custom ones after.
-            host = getattr(gp, "_host_processors", None) or []
-            host.append(proc)
-            gp._host_processors = host
+            gp._host_processors = (gp._host_processors or []) + [proc]
     for crit in (stopping_criteria or []):
         name = type(crit).__name__
         if name == "MaxLengthCriteria":
@@ -167,9 +170,7 @@ def lower_processors(gp: GenParams, logits_processor, stopping_criteria) -> GenP
         else:
             # anything else is evaluated on the host after every iteration (generate(): the per-iteration path the streamer uses),
             # exactly where the reference calls it (model.py:786: once per Medusa iteration, on the ids emitted so far)
-            host = getattr(gp, "_host_criteria", None) or []
-            host.append(crit)
-            gp._host_criteria = host
+            gp._host_criteria = (gp._host_criteria or []) + [crit]
     return gp
 
 
@@ -269,6 +270,79 @@ def _resolve_checkpoint(name_or_path, revision=None, cache_dir=None, local_files
     except Exception as e:
         raise OSError(f"{path!r} is neither a checkpoint directory nor a hub repository that could be resolved "
                       f"({type(e).__name__}: {e})") from e
+
+
+# ---- ragged per-stream rows -> tensors, and the slices of a row that belong to its segments ----------------------------------------------------
+def _stack_rows(rows, fill, dtype, T: Optional[int] = None) -> torch.Tensor:
+    """Ragged rows (lists, arrays or 1-D tensors) -> [len(rows), T or the longest]; behind a row's end ``fill``, or with ``fill=None`` the
+    row's own last value.  Built where the rows live (tensor rows: their device; anything else: the CPU)."""
+    dev = rows[0].device if isinstance(rows[0], torch.Tensor) else None
+    t = torch.full((len(rows), max(len(r) for r in rows) if T is None else T), 0 if fill is None else fill, dtype=dtype, device=dev)
+    for i, r in enumerate(rows):
+        t[i, : len(r)] = torch.as_tensor(r, dtype=dtype)
+        if fill is None and len(r):
+            t[i, len(r):] = t[i, len(r) - 1]
+    return t
+
+
+def _ids_tensor(rows, pad: int) -> torch.Tensor:
+    """Token id rows -> LongTensor, right-padded with ``pad``."""
+    return _stack_rows(rows, pad, torch.long)
+
+
+def _ts_tensor(rows, T: Optional[int] = None) -> torch.Tensor:
+    """Per-stream token timestamps -> float32 [B, T] next to the padded ids: positions after a stream's end repeat its last value."""
+    return _stack_rows(rows, None, torch.float32, T)
+
+
+def _lp_tensor(rows, T: Optional[int] = None) -> torch.Tensor:
+    """Per-stream token log-probabilities -> float32 [B, T] next to the padded ids: 0 after a stream's end."""
+    return _stack_rows(rows, 0.0, torch.float32, T)
+
+
+def _segment_slices(segments, prompt_len: int, name: str, row) -> None:
+    """Every segment of one output row gets, as ``name``, the slice of ``row`` (values per position of that output row) under its own tokens."""
+    o = prompt_len
+    for sg in segments:
+        n = int(sg["tokens"].numel())
+        sg[name] = row[o: o + n]
+        o += n
+
+
+@dataclass
+class ResolvedCall:
+    """What generate() has made of its arguments, once per public call, for the route that decodes it: the request dicts of
+    the features that ride on the short-form decode (None: not asked for) and the resolved scalars."""
+    samp: Optional[dict] = None              # seeded sampling / temperature fallback (_sampling_request)
+    bias: Optional[list] = None              # sequence bias entries (_bias_request)
+    beam: Optional[dict] = None              # beam search (_beam_request)
+    sc_req: Optional[dict] = None            # scoring pass: token log-probabilities, thresholds, alternatives
+    tt_req: Optional[dict] = None            # token timestamps (_token_ts_request)
+    rep_pen: float = 1.0
+    rep_g: int = 0
+    return_timestamps: bool = False
+    time_precision: float = 0.02
+    task: Optional[str] = None
+    prompt_ids: Optional[torch.Tensor] = None
+    temperature: Union[None, float, Sequence[float]] = None
+    logits_processor: Optional[list] = None
+    stopping_criteria: Optional[list] = None
+    return_dict_in_generate: Optional[bool] = None
+    return_segments: bool = False
+    opts: dict = field(default_factory=dict)     # the call's other keywords as given: max_new_tokens, max_length, vanilla, posterior_*, streamer, ..
+
+
+@dataclass
+class ShortResult:
+    """What one short-form decode (_generate_short) hands to its route; nothing of it travels through the model's attributes."""
+    seqs: List[List[int]]                            # per stream: prompt + generated ids (beams: num_return_sequences rows per clip, clip-major)
+    gp: GenParams                                    # the parameters it ran under (``prompt`` / ``prompts``: the decoder prompts)
+    stats: dict
+    token_timestamps: Optional[torch.Tensor] = None  # [B, T] next to the padded ids
+    scores: Optional[dict] = None                    # _score_pack's fields (with the fallback fields, where both were asked for)
+    sequences_scores: Optional[torch.Tensor] = None  # beam search
+    fallback: Optional[dict] = None                  # fallback_temperature / fallback_attempts
+    fallback_beams: Optional[dict] = None            # clip -> hypotheses of its beam-search attempt
 
 
 class WhisperMedusaModel:
@@ -674,15 +748,14 @@ class WhisperMedusaModel:
                                       "are asked for: sampling_top_k= / sampling_top_p= / sampling_min_p= (DESIGN.md §2k), e.g. sampling_top_k=50")
         if self.config.is_tree:
             raise NotImplementedError("sampling (sampling_seed) is not supported with a candidate tree (medusa_choices with top-k > 1)")
-        if logits_processor and any(type(p_).__name__ not in _LOWERABLE_PROCESSORS for p_ in logits_processor):
+        if _needs_host_processors(logits_processor):
             raise NotImplementedError("sampling (sampling_seed) is not supported on the host processor path (logits_processor=)")
         if kwargs.get("streamer") is not None:
             raise NotImplementedError("streamer= is not supported with sampling (sampling_seed): a fallback attempt would take streamed tokens back")
         if kwargs.get("chunk_longform"):
             raise NotImplementedError("chunk_longform is not supported with sampling (sampling_seed); use sequential_longform")
         ids = kwargs.get("sampling_stream_ids")
-        return dict(seed=int(seed), ids=None if ids is None else [int(v) for v in ids], seeks=kwargs.get("_sampling_seeks"), temps=temps,
-                    fallback=ladder)
+        return dict(seed=int(seed), ids=None if ids is None else [int(v) for v in ids], seeks=None, temps=temps, fallback=ladder)
 
     @staticmethod
     def sampling_stream_key(stream_id: int, seek_frames: int, attempt: int) -> int:
@@ -692,14 +765,9 @@ class WhisperMedusaModel:
     @staticmethod
     def _sampled_gp(gp: GenParams, T: float, seed: int, keys: List[int], flt: tuple = (0, 1.0, 0.0)) -> GenParams:
         """``gp`` for one sampled attempt: the engine's plain decode path with the (filtered) draw in place of the arg-max."""
-        import dataclasses
-        g = dataclasses.replace(gp, vanilla=True, accept_mode=ACCEPT_GREEDY, temperature=0.0, sampling_temperature=float(T),
-                                sampling_seed=int(seed), sampling_keys=list(keys), num_beams=1,     # (HF: a sampled retry runs with one beam)
-                                sampling_top_k=int(flt[0]), sampling_top_p=float(flt[1]), sampling_min_p=float(flt[2]))
-        for k, v in vars(gp).items():           # (what generate() hangs on the object: _time_precision)
-            if k.startswith("_"):
-                setattr(g, k, v)
-        return g
+        return replace(gp, vanilla=True, accept_mode=ACCEPT_GREEDY, temperature=0.0, sampling_temperature=float(T),
+                       sampling_seed=int(seed), sampling_keys=list(keys), num_beams=1,     # (HF: a sampled retry runs with one beam)
+                       sampling_top_k=int(flt[0]), sampling_top_p=float(flt[1]), sampling_min_p=float(flt[2]))
 
     # ---- beam search on the plain decode path (engine: csrc/wm_beam.hip; DESIGN.md §2i) ------------------------------------------------------
     BEAM_MAX = 8
@@ -789,7 +857,7 @@ class WhisperMedusaModel:
                                       "accept kernels do not know the bias)")
         if cfg.is_tree:
             raise NotImplementedError(f"{names} is not supported with a candidate tree (medusa_choices with top-k > 1)")
-        if (logits_processor and any(type(p_).__name__ not in _LOWERABLE_PROCESSORS for p_ in logits_processor)) or \
+        if _needs_host_processors(logits_processor) or \
                 (stopping_criteria and any(type(c_).__name__ not in _LOWERABLE_CRITERIA for c_ in stopping_criteria)):
             raise NotImplementedError(f"{names} is not supported on the host processor path (logits_processor= / stopping_criteria=); pass HF's "
                                       "SequenceBiasLogitsProcessor there instead")
@@ -820,8 +888,8 @@ class WhisperMedusaModel:
 
     def _beam_decode(self, eng, feats, gp: GenParams, encoded: bool):
         """Beam search over the clips ``feats`` in groups of max_batch // num_beams, each group encoded and decoded in turn (B clips need
-        B * num_beams streams).  Returns every clip's best finished hypothesis; all of them — [(ids, score)] * num_beams per clip, best first —
-        stay in ``self._last_beam``.  Ends with ALL clips resident (one more encoder pass when there was more than one group), so that the
+        B * num_beams streams).  Returns (every clip's best finished hypothesis, all of them — [(ids, score)] * num_beams per clip, best first —,
+        the summed statistics).  Ends with ALL clips resident (one more encoder pass when there was more than one group), so that the
         requests that replay the final ids find the state an ordinary decode leaves."""
         B, n = feats.shape[0], int(gp.num_beams)
         per = max(eng.max_batch // n, 1)
@@ -841,15 +909,15 @@ class WhisperMedusaModel:
         if per < B:
             eng.encode(feats)
         stats["beam_groups"] = -(-B // per)
-        self._last_beam, self._last_beam_stats = hyps, stats
-        return [h[0][0] for h in hyps]
+        return [h[0][0] for h in hyps], hyps, stats
 
     def _decode_with_fallback(self, eng, feats, gp: GenParams, samp: dict, sc_req: Optional[dict], encoded: bool):
         """HF ``generate_with_fallback``: attempt i decodes the streams still flagged at temps[i] — 0: the configured path, > 0: the sampled plain
         decode —, scores them (the existing scoring pass, at temperature 1 on the processed rows, as HF's _retrieve_avg_logprobs undoes the
         temperature) and gates them.  A stream is final when it needs no fallback, was skipped by the no-speech gate, or the temperatures are
         exhausted (the last attempt is kept).  Flagged streams are re-encoded as a sub-batch.  Without thresholds nothing is ever flagged.
-        Returns (seqs, infos or None, kept temperature, attempts per stream, ms of the scoring passes)."""
+        Returns (seqs, infos or None, kept temperature, attempts per stream, ms of the scoring passes, the hypotheses of every clip whose
+        temperature-0 attempt was a beam search, the summed statistics)."""
         B = feats.shape[0]
         ids = samp["ids"] if samp["ids"] is not None else list(range(B))
         seeks = samp["seeks"] if samp["seeks"] is not None else [0] * B
@@ -864,10 +932,9 @@ class WhisperMedusaModel:
             gp_i = gp if T == 0.0 else self._sampled_gp(gp, T, samp["seed"], [self.sampling_stream_key(ids[b], seeks[b], i) for b in todo],
                                                              samp.get("filter", (0, 1.0, 0.0)))
             gp_i = gp_i.for_streams(todo)       # (per-stream prompts follow their streams into the sub-batch)
-            if int(getattr(gp_i, "num_beams", 1) or 1) > 1:      # HF generate_with_fallback: num_beams stays exactly when the attempt does not sample
-                out = self._beam_decode(eng, feats if len(todo) == B else feats[todo], gp_i, True)
-                for j, b in enumerate(todo):
-                    beams[b] = self._last_beam[j]
+            if gp_i.num_beams > 1:      # HF generate_with_fallback: num_beams stays exactly when the attempt does not sample
+                out, hyps, _ = self._beam_decode(eng, feats if len(todo) == B else feats[todo], gp_i, True)
+                beams.update(zip(todo, hyps))
             else:
                 out = eng.decode(gp_i, len(todo))
             n_dec += 1
@@ -887,9 +954,7 @@ class WhisperMedusaModel:
             if not todo:
                 break
         stats["fallback_decodes"] = n_dec - 1
-        self.last_stats = stats
-        self._fallback_beams = beams
-        return seqs, (infos if sc_req is not None else None), kept, att, ms_sc
+        return seqs, (infos if sc_req is not None else None), kept, att, ms_sc, beams, stats
 
     @torch.no_grad()
     def generate(self, input_features: Optional[torch.Tensor] = None, generation_config=None, logits_processor=None,
@@ -999,7 +1064,7 @@ class WhisperMedusaModel:
             if self.config.is_tree:
                 raise NotImplementedError("repetition_penalty / no_repeat_ngram_size are not supported with a candidate tree "
                                           "(medusa_choices with top-k > 1)")
-            if logits_processor and any(type(p_).__name__ not in _LOWERABLE_PROCESSORS for p_ in logits_processor):
+            if _needs_host_processors(logits_processor):
                 raise NotImplementedError("repetition_penalty / no_repeat_ngram_size are not supported on the host processor path "
                                           "(logits_processor=); pass the HF processor objects there instead")
         if return_timestamps:
@@ -1025,18 +1090,14 @@ class WhisperMedusaModel:
                 # the reference's refusal (model.py:1201-1205) stays where nothing can score the clip: the detection is the engine's scoring pass
                 raise NotImplementedError("no_speech_detection is not supported with medusa without the HIP engine's scoring pass: "
                                           "call model.to('cuda') first (no_speech_threshold)")
-            if logits_processor and any(type(p_).__name__ not in _LOWERABLE_PROCESSORS for p_ in logits_processor):
+            if _needs_host_processors(logits_processor):
                 raise NotImplementedError(("top_logprobs / " if top_logprobs is not None else "") +
                                           "token log-probabilities / quality gating are not supported on the host processor path (logits_processor=)")
             sc_req = dict(want=bool(return_token_logprobs) or top_logprobs is not None, no_speech_threshold=no_speech_threshold,
                           logprob_threshold=logprob_threshold, compression_ratio_threshold=compression_ratio_threshold, top_k=top_logprobs)
-        sc_side = kwargs.pop("_sc_req", None)       # called by the language / long-form wrappers: plain tensor back, scores in self._last_sc
-        if sc_side is not None:
-            sc_req = sc_side
-        sc_side = sc_side is not None
         # model.py:1153-1156 raises for num_beams > 1; with vanilla=True the engine runs HF's _beam_search on its plain decode path
         beam = self._beam_request(kwargs, temperature, logits_processor, stopping_criteria,
-                                  side=sc_req is not None or bool(return_token_timestamps) or kwargs.get("_tt_req") is not None)
+                                  side=sc_req is not None or bool(return_token_timestamps))
         if prefix_allowed_tokens_fn:
             raise NotImplementedError("prefix_allowed_tokens_fn is not supported by the HIP engine")
         tt_req = None
@@ -1045,90 +1106,110 @@ class WhisperMedusaModel:
             # aligns them on the GPU
             tt_req = self._token_ts_request(kwargs.get("alignment_heads"), generation_config, kwargs.get("num_frames"), logits_processor,
                                             time_precision)
-        tt_side = kwargs.pop("_tt_req", None)       # called by the language / long-form wrappers: plain tensor back, timestamps in self._last_tt
-        if tt_side is not None:
-            tt_req = tt_side
-        tt_side = tt_side is not None
         if input_features is None:
             raise ValueError("input_features is required")
         if input_features.dim() != 3:
             raise ValueError("input_features must be [B, n_mels, frames]")
         # language=[...]: one language per clip (HF `language: str | list[str]`, _retrieve_init_tokens).  The entries become language
         # token strings; the long-form loops below take them as one language per recording, the short-form path as per-stream prompts of one length
-        lang_list = isinstance(language, (list, tuple))
-        if lang_list:
+        if isinstance(language, (list, tuple)):
             language = self._language_list(language, input_features.shape[0])
             if not self.config.is_multilingual:
-                language, lang_list = None, False       # ignored, as a scalar is (the prompt has no language slot)
+                language = None                         # ignored, as a scalar is (the prompt has no language slot)
+        call = ResolvedCall(samp=samp, bias=bias, beam=beam, sc_req=sc_req, tt_req=tt_req, rep_pen=rep_pen, rep_g=rep_g,
+                            return_timestamps=bool(return_timestamps), time_precision=time_precision, task=task, prompt_ids=prompt_ids,
+                            temperature=temperature, logits_processor=logits_processor, stopping_criteria=stopping_criteria,
+                            return_dict_in_generate=return_dict_in_generate, return_segments=return_segments, opts=kwargs)
+        # the route: every one of them decodes its <= 30 s windows through _generate_short
+        detect = bool(language is None and self.config.is_multilingual and kwargs.get("detect_language", True))
         if kwargs.get("sequential_longform"):
-            return self._generate_sequential(input_features, attention_mask, dict(kwargs, language=language, task=task, temperature=temperature,
-                                                                                  prompt_ids=prompt_ids, _sc_req=sc_req,
-                                                                                  return_dict_in_generate=return_dict_in_generate,
-                                                                                  return_segments=return_segments, time_precision=time_precision,
-                                                                                  time_precision_features=time_precision_features))
+            return self._generate_sequential(input_features, attention_mask, call, language, detect, time_precision_features)
         if input_features.shape[-1] > self.config.n_mel_frames:
             if not kwargs.get("chunk_longform"):
                 raise NotImplementedError("Longform generation is not supported yet")              # model.py:1213-1214
-            return self._generate_longform(input_features, dict(kwargs, language=language, task=task, temperature=temperature,
-                                                                prompt_ids=prompt_ids, logits_processor=logits_processor,
-                                                                stopping_criteria=stopping_criteria,
-                                                                return_timestamps=bool(return_timestamps), _tt_req=tt_req, _sc_req=sc_req,
-                                                                return_dict_in_generate=return_dict_in_generate,
-                                                                return_segments=return_segments, time_precision=time_precision))
-        if language is None and self.config.is_multilingual and kwargs.get("detect_language", True) and input_features.shape[0] >= 1 \
-                and not kwargs.get("_language_resolved") and kwargs.get("group_by_language", True) is False:
-            # group_by_language=False: encode, detect on the device, then THIS call goes on with the detected list and decodes
-            # from the encoder pass that is resident — one encode, one decode, whatever the mix of languages
+            return self._generate_longform(input_features, call, language, detect)
+        if detect and input_features.shape[0] >= 1 and kwargs.get("group_by_language", True) is False:
+            # group_by_language=False: encode, detect on the device, then decode from the encoder pass that is resident — one
+            # encode, one decode, whatever the mix of languages
             language = self._detect_language_on_device(input_features.to(self.device, torch.float32).contiguous())
             self.detected_languages = list(language)
-            lang_list = True
-            kwargs = dict(kwargs, _encoded_batch=input_features.shape[0])
-        if language is None and self.config.is_multilingual and kwargs.get("detect_language", True) and input_features.shape[0] >= 1 \
-                and not kwargs.get("_language_resolved"):
-            return self._generate_detecting_language(input_features, dict(kwargs, task=task, temperature=temperature, prompt_ids=prompt_ids,
-                                                                          return_dict_in_generate=return_dict_in_generate,
-                                                                          return_segments=return_segments, logits_processor=logits_processor,
-                                                                          stopping_criteria=stopping_criteria, _tt_req=tt_req, _tt_outer=tt_side,
-                                                                          _sc_req=sc_req, _sc_outer=sc_side,
-                                                                          return_timestamps=bool(return_timestamps), time_precision=time_precision))
+            res = self._generate_short(input_features, call, language=language, encoded=True)
+        elif detect and input_features.shape[0] >= 1:
+            return self._generate_detecting_language(input_features, call)
+        else:
+            res = self._generate_short(input_features, call, language=language)
+        out = self._outputs(res.seqs, res.gp, return_dict_in_generate, return_segments, res.token_timestamps, res.scores)
+        if isinstance(out, dict):
+            if res.fallback is not None and res.scores is None:
+                out.update(res.fallback)
+            if res.sequences_scores is not None:
+                out["sequences_scores"] = res.sequences_scores
+        return self._publish(res, out)
+
+    def _publish(self, res: "ShortResult", out):
+        """The attributes a public call leaves behind, from the (last) short-form result of its route; hands ``out`` through."""
+        self._last_prompt = list(res.gp.prompt)         # (per-stream prompts, gp.prompts, have this one's length: the representative row)
+        self.last_stats = res.stats
+        if res.fallback is not None:
+            self.last_fallback, self._fallback_beams = res.fallback, res.fallback_beams
+        if res.sequences_scores is not None:
+            self.last_sequences_scores = res.sequences_scores
+        return out
+
+    def _generate_short(self, input_features, call: "ResolvedCall", *, language, encoded: bool = False, stream_ids=None, seeks=None,
+                        num_frames=None) -> "ShortResult":
+        """Decode one batch of <= 30 s windows under the resolved call: what all four routes of generate() come down to.  ``language``: a
+        language token string / None, or one per clip (per-stream prompts).  ``encoded``: the caller has just encoded exactly this batch on the
+        model's own engine (language detection) — the decode starts from that pass while it is still resident.  ``stream_ids`` / ``seeks``: the
+        seeded sampling's stream keys follow their clips (global ids, the window's seek); ``num_frames``: likewise for the token timestamps.
+        Checks that depend on the batch live here; the call's arguments were checked once, in generate()."""
+        opts, samp, beam, bias, sc_req, tt_req = call.opts, call.samp, call.beam, call.bias, call.sc_req, call.tt_req
+        if tt_req is not None and num_frames is not None:
+            tt_req = dict(tt_req, num_frames=num_frames)
+        if samp is not None and (stream_ids is not None or seeks is not None):
+            samp = dict(samp, ids=stream_ids, seeks=seeks)
+        lang_list, streamer = isinstance(language, (list, tuple)), opts.get("streamer")
         B = input_features.shape[0]
-        if lang_list and kwargs.get("streamer") is not None:
+        if lang_list and streamer is not None:
             raise NotImplementedError("language=[...] / group_by_language=False (one language per clip) is not supported with streamer= "
                                       "(the streaming path is built around a single prompt)")
         if B > self._max_batch:
             self.set_max_batch(B)
         if beam is not None and beam["n"] > self._max_batch:        # (a wrapper may have resized the context since the request was read)
             raise ValueError(f"num_beams={beam['n']} exceeds max_batch={self._max_batch}: call set_max_batch first")
-        gp = self._gen_params(language, task, kwargs.get("exponential_decay_length_penalty"),
-                              kwargs.get("max_new_tokens"), kwargs.get("max_length"),
+        temperature = call.temperature
+        gp = self._gen_params(language, call.task, opts.get("exponential_decay_length_penalty"),
+                              opts.get("max_new_tokens"), opts.get("max_length"),
                               # (sampling: attempt 0 of a fallback schedule at temperature 0 is today's call with that tuple — exact-match
                               # acceptance —, every sampled attempt derives its own parameters from these: _sampled_gp)
                               (0.0 if samp["temps"][0] == 0.0 else None) if samp is not None else
                               temperature if not isinstance(temperature, (tuple, list)) else temperature[0],
-                              kwargs.get("vanilla", False), kwargs.get("posterior_threshold"),
-                              kwargs.get("posterior_alpha"), kwargs.get("suppress_tokens"),
-                              kwargs.get("begin_suppress_tokens"), prompt_ids, timestamps=bool(return_timestamps),
-                              repetition_penalty=rep_pen, no_repeat_ngram_size=rep_g)
-        gp._time_precision = float(time_precision)
+                              opts.get("vanilla", False), opts.get("posterior_threshold"),
+                              opts.get("posterior_alpha"), opts.get("suppress_tokens"),
+                              opts.get("begin_suppress_tokens"), call.prompt_ids, timestamps=call.return_timestamps,
+                              repetition_penalty=call.rep_pen, no_repeat_ngram_size=call.rep_g)
+        gp._time_precision = float(call.time_precision)
         if beam is not None:
             gp.num_beams, gp.length_penalty, gp.early_stopping = beam["n"], beam["length_penalty"], beam["early_stopping"]
         if bias is not None:
             gp.sequence_bias = bias
-        if logits_processor or stopping_criteria:
-            gp = lower_processors(gp, logits_processor, stopping_criteria)
-        if lang_list and (getattr(gp, "_host_criteria", None) or getattr(gp, "_host_processors", None)):
+        if call.logits_processor or call.stopping_criteria:
+            gp = lower_processors(gp, call.logits_processor, call.stopping_criteria)
+        host_crit = gp._host_criteria
+        on_host = bool(host_crit or gp._host_processors)
+        if lang_list and on_host:
             raise NotImplementedError("language=[...] / group_by_language=False (one language per clip) is not supported on the host processor path "
                                       "(logits_processor= / stopping_criteria= that the engine cannot lower: it is built around a single prompt)")
-        self._last_prompt = list(gp.prompt)         # (per-stream prompts, gp.prompts, have this one's length: the representative row)
         feats = input_features.to(self.device, torch.float32).contiguous()
-        n_ctx = self._micro_batches_for(B) if (kwargs.get("streamer") is None and not getattr(gp, "_host_criteria", None)
-                                               and not getattr(gp, "_host_processors", None)) else 1
-        # language detection has just encoded exactly this batch on the model's own engine: decoding there saves the pool's second
-        # encoder pass over the same clips (the automatic policy's gain at 2-3 clips is smaller than an encoder pass)
-        if self._micro_batches is None and kwargs.get("_encoded_batch") == B and getattr(self._engine, "_B", None) == B:
+        n_ctx = self._micro_batches_for(B) if (streamer is None and not on_host) else 1
+        # language detection has just encoded exactly this batch on the model's own engine (one language group, same order): its encoder
+        # output and cross-K/V are still resident — decoding there saves the pool's second encoder pass over the same clips (the automatic
+        # policy's gain at 2-3 clips is smaller than an encoder pass), and the decode below starts from it instead of encoding again
+        resident = encoded and getattr(self._engine, "_B", None) == B
+        if self._micro_batches is None and resident:
             n_ctx = 1
         if samp is not None:
-            if getattr(gp, "_host_criteria", None) or getattr(gp, "_host_processors", None):
+            if on_host:
                 raise NotImplementedError("sampling (sampling_seed) is not supported on the host processor path (logits_processor= / "
                                           "stopping_criteria= that the engine cannot lower)")
             n_ctx = 1           # the model's own engine: the micro-batch pool is not taught sampling
@@ -1136,23 +1217,19 @@ class WhisperMedusaModel:
             n_ctx = 1           # ... nor beams (the beams of a clip share one context), nor the sequence bias
         if n_ctx > 1 and B >= 2:
             pool = self._get_pool(n_ctx)
-            tsf = None
+            extra = {}
             if tt_req is not None:
-                tsf = lambda e, sq, lo: self._token_ts_run(e, sq, gp.for_streams(range(lo, lo + len(sq))), tt_req, lo)       # noqa: E731
-            extra = {"token_ts": tsf} if tsf is not None else {}
+                extra["token_ts"] = lambda e, sq, lo: self._token_ts_run(e, sq, gp.for_streams(range(lo, lo + len(sq))), tt_req, lo)   # noqa: E731
             if sc_req is not None:
                 extra["score"] = lambda e, sq, lo: self._score_run(e, sq, gp.for_streams(range(lo, lo + len(sq))), sc_req)    # noqa: E731
             seqs = pool.run(feats, gp, **extra)      # F1..F14 per micro-batch, concurrently
-            self.last_stats = pool.last_stats
-            tt = self._token_ts_tensor(pool.last_token_timestamps, seqs, gp) if tt_req is not None else None
+            tt = _ts_tensor(pool.last_token_timestamps).to(self.device) if tt_req is not None else None
             sc = self._score_pack(pool.last_scores, seqs, gp, sc_req) if sc_req is not None else None
-            return self._outputs(seqs, gp, return_dict_in_generate, return_segments, tt, tt_side, sc, sc_side)
+            return ShortResult(seqs, gp, pool.last_stats, tt, sc)
         eng = self.engine
-        streamer = kwargs.get("streamer")
-        host_crit = getattr(gp, "_host_criteria", None)
         if streamer is not None and B != 1:
             raise ValueError("streamer only supports batch size 1")        # HF streamers are batch-1
-        if getattr(gp, "_host_processors", None):
+        if gp._host_processors:
             if gp.repeat_rules:
                 raise NotImplementedError("repetition_penalty / no_repeat_ngram_size are not supported on the host processor path "
                                           "(logits_processor=); pass the HF processor objects there instead")
@@ -1161,42 +1238,33 @@ class WhisperMedusaModel:
             if sc_req is not None:
                 raise NotImplementedError(("top_logprobs / " if sc_req.get("top_k") else "") +
                                           "token log-probabilities / quality gating are not supported on the host processor path (logits_processor=)")
-            seqs = self._decode_host_processors(feats, gp, streamer, host_crit)
-            return self._outputs(seqs, gp, return_dict_in_generate, return_segments)
-        # language detection just encoded exactly these clips on this engine (one language group, same order): its encoder output and
-        # cross-K/V are still resident — decode from them instead of running the encoder a second time
+            seqs, stats = self._decode_host_processors(feats, gp, streamer, host_crit)
+            return ShortResult(seqs, gp, stats)
         # (beam search over more clips than max_batch // num_beams encodes group by group: _beam_decode)
-        if samp is None and not (kwargs.get("_encoded_batch") == B and getattr(eng, "_B", None) == B) \
-                and not (beam is not None and B * beam["n"] > eng.max_batch):
+        if samp is None and not resident and not (beam is not None and B * beam["n"] > eng.max_batch):
             eng.encode(feats)                                               # F1 + F2
         if samp is not None:
-            seqs, infos, kept, att, ms = self._decode_with_fallback(eng, feats, gp, samp, sc_req, kwargs.get("_encoded_batch") == B and
-                                                                    getattr(eng, "_B", None) == B)
+            seqs, infos, kept, att, ms, beams, stats = self._decode_with_fallback(eng, feats, gp, samp, sc_req, resident)
             fb = dict(fallback_temperature=torch.tensor(kept, dtype=torch.float32, device=self.device),
                       fallback_attempts=torch.tensor(att, dtype=torch.long, device=self.device))
-            self.last_fallback = fb
             sc = None
             if sc_req is not None:
-                self.last_stats["ms_token_logprobs"] = ms
+                stats["ms_token_logprobs"] = ms
                 sc = dict(self._score_pack(infos, seqs, gp, sc_req), **fb)
             tt = None
             if tt_req is not None:
                 if getattr(eng, "_B", None) != B:       # the last attempt left a sub-batch resident
                     eng.encode(feats)
                 rows, ms = self._token_ts_run(eng, seqs, gp, tt_req, 0)
-                self.last_stats["ms_token_timestamps"] = ms
-                tt = self._token_ts_tensor(rows, seqs, gp)
-            out = self._outputs(seqs, gp, return_dict_in_generate, return_segments, tt, tt_side, sc, sc_side)
-            if sc is None and isinstance(out, dict):
-                out.update(fb)
+                stats["ms_token_timestamps"] = ms
+                tt = _ts_tensor(rows).to(self.device)
+            ss = None
             if beam is not None:
                 # the score of a clip whose kept attempt is the beam search; NaN where a sampled retry was kept
-                ss = torch.tensor([self._fallback_beams[b][0][1] if (kept[b] == 0.0 and b in self._fallback_beams) else float("nan") for b in range(B)],
+                ss = torch.tensor([beams[b][0][1] if (kept[b] == 0.0 and b in beams) else float("nan") for b in range(B)],
                                   dtype=torch.float32, device=self.device)
-                self.last_sequences_scores = ss
-                if isinstance(out, dict):
-                    out["sequences_scores"] = ss
-            return out
+            return ShortResult(seqs, gp, stats, tt, sc, ss, fb, beams)
+        hyps = None
         if streamer is not None or host_crit:
             # one iteration per engine call: the streamer gets the tokens of every iteration (model.py:1034-1035 prompt, :758-759
             # tokens, :795-796 end); stopping criteria that are not static length / EOS rules are asked after every iteration with
@@ -1233,33 +1301,30 @@ class WhisperMedusaModel:
             if streamer is not None:
                 streamer.end()
         elif beam is not None:
-            seqs = self._beam_decode(eng, feats, gp, True)                  # (encoded above; more than one group encodes again)
+            seqs, hyps, stats = self._beam_decode(eng, feats, gp, True)    # (encoded above; more than one group encodes again)
         else:
             seqs = eng.decode(gp, B)                                        # F3..F14
-        self.last_stats = eng.stats() if beam is None else self._last_beam_stats
+        if hyps is None:
+            stats = eng.stats()
         sc = None
         if sc_req is not None:
             # scoring first: a skipped clip's row becomes prompt + EOS before anything else looks at it (two replays when token timestamps
             # are asked for in the same call)
             seqs, infos, ms = self._score_run(eng, seqs, gp, sc_req)
-            self.last_stats["ms_token_logprobs"] = ms
+            stats["ms_token_logprobs"] = ms
             sc = self._score_pack(infos, seqs, gp, sc_req)
         tt = None
         if tt_req is not None:
             rows, ms = self._token_ts_run(eng, seqs, gp, tt_req, 0)
-            self.last_stats["ms_token_timestamps"] = ms
-            tt = self._token_ts_tensor(rows, seqs, gp)
-        if beam is not None:
+            stats["ms_token_timestamps"] = ms
+            tt = _ts_tensor(rows).to(self.device)
+        ss = None
+        if hyps is not None:
             # HF: `sequences` [B * num_return_sequences, T], clip-major and best first, and `sequences_scores` with return_dict_in_generate
             r = beam["num_return_sequences"]
-            seqs = [h[k][0] for h in self._last_beam for k in range(r)] if r > 1 else seqs
-            ss = torch.tensor([h[k][1] for h in self._last_beam for k in range(r)], dtype=torch.float32, device=self.device)
-            self.last_sequences_scores = ss
-            out = self._outputs(seqs, gp, return_dict_in_generate, return_segments, tt, tt_side, sc, sc_side)
-            if isinstance(out, dict):
-                out["sequences_scores"] = ss
-            return out
-        return self._outputs(seqs, gp, return_dict_in_generate, return_segments, tt, tt_side, sc, sc_side)
+            seqs = [h[k][0] for h in hyps for k in range(r)] if r > 1 else seqs
+            ss = torch.tensor([h[k][1] for h in hyps for k in range(r)], dtype=torch.float32, device=self.device)
+        return ShortResult(seqs, gp, stats, tt, sc, ss)
 
     # ---- token log-probabilities, no-speech probability, quality gating (engine: csrc/wm_score.hip) --------------------------
     def _score_run(self, eng, seqs, gp: GenParams, req: dict):
@@ -1300,11 +1365,7 @@ class WhisperMedusaModel:
     def _score_pack(self, infos, seqs, gp: GenParams, req: dict) -> dict:
         """Per-stream infos -> the tensors of the dict output, next to _pad's ids (token_logprobs is 0 after a stream's end)."""
         T = max(len(self._own_end(s, gp)) for s in seqs)
-        t = torch.zeros(len(infos), T, dtype=torch.float32)
-        for i, f in enumerate(infos):
-            r = np.asarray(f["token_logprobs"], dtype=np.float32)
-            t[i, : len(r)] = torch.from_numpy(r)
-        sc = dict(token_logprobs=t.to(self.device),
+        sc = dict(token_logprobs=_lp_tensor([f["token_logprobs"] for f in infos], T).to(self.device),
                   avg_logprob=torch.tensor([f["avg_logprob"] for f in infos], dtype=torch.float32, device=self.device),
                   compression_ratio=torch.tensor([f["compression_ratio"] for f in infos], dtype=torch.float32, device=self.device),
                   # the streams' own ends (EOS included): with pad == eos a padded row alone cannot tell a stream's EOS from its padding
@@ -1366,16 +1427,6 @@ class WhisperMedusaModel:
         out, ms = eng.token_timestamps(own, len(gp.prompt), req["heads"], req["width"], req["time_precision"], nf)
         return [out[b, : len(s)].copy() for b, s in enumerate(own)], ms
 
-    def _token_ts_tensor(self, rows, seqs, gp: GenParams) -> torch.Tensor:
-        """float32 [B, T] next to _pad's ids: positions after a stream's end repeat its last value."""
-        T = max(len(self._own_end(s, gp)) for s in seqs)
-        t = torch.zeros(len(rows), T, dtype=torch.float32)
-        for i, r in enumerate(rows):
-            t[i, : len(r)] = torch.from_numpy(np.asarray(r, dtype=np.float32))
-            if len(r):
-                t[i, len(r):] = float(r[-1])
-        return t.to(self.device)
-
     # ---- arbitrary logits processors: the reference's loop with the passes on the engine --------------------------------------------
     @staticmethod
     def _static_processors(scores: torch.Tensor, cur_len: int, gp: GenParams) -> torch.Tensor:
@@ -1407,7 +1458,7 @@ class WhisperMedusaModel:
             ok = p_c > torch.minimum(torch.full_like(H, gp.posterior_threshold), torch.exp(-H) * gp.posterior_alpha)
         return int(torch.cumprod(ok.int(), dim=0).sum().item())
 
-    def _decode_host_processors(self, feats: torch.Tensor, gp: GenParams, streamer=None, host_crit=None) -> List[List[int]]:
+    def _decode_host_processors(self, feats: torch.Tensor, gp: GenParams, streamer=None, host_crit=None) -> Tuple[List[List[int]], dict]:
         """generate() with logits processors that are arbitrary Python callables (the reference hands ANY list to HF's machinery,
         model.py:1106-1116, and calls it on the base / Medusa logits and on the verify logits, :653-665, :689-694).  The engine's fused
         loop never lets logits leave the device, so this path runs the reference's loop structure (model.py:634-793) on the host, one
@@ -1474,21 +1525,14 @@ class WhisperMedusaModel:
             seqs.append(ids)
             if streamer is not None:
                 streamer.end()
-        self.last_stats = dict(iterations=n_iter, iterations_launched=n_iter, tokens_emitted=n_tok, accept_hist=hist, host_processors=len(procs))
-        return seqs
+        return seqs, dict(iterations=n_iter, iterations_launched=n_iter, tokens_emitted=n_tok, accept_hist=hist, host_processors=len(procs))
 
-    def _outputs(self, seqs, gp, return_dict_in_generate, return_segments, token_timestamps=None, tt_side=False, scores=None, sc_side=False):
+    def _outputs(self, seqs, gp, return_dict_in_generate, return_segments, token_timestamps=None, scores=None):
         """Default: the padded LongTensor.  ``return_dict_in_generate`` / ``return_segments``: the reference's dict form
         ``{"sequences": ..., ["segments": ...]}`` (model.py:1747-1779; one segment per clip, short-form only)."""
-        if tt_side:          # an inner call of the language / long-form wrappers: they wrap the outputs themselves
-            self._last_tt = token_timestamps
-            token_timestamps = None
-        if sc_side:
-            self._last_sc = scores
-            scores = None
         return self._wrap_outputs(self._pad(seqs, gp), [len(gp.prompt)] * len(seqs), gp.pad_token_id, gp.eos_token_id,
                                   return_dict_in_generate, return_segments, timestamps=gp.timestamps,
-                                  time_precision=getattr(gp, "_time_precision", 0.02), token_timestamps=token_timestamps, scores=scores)
+                                  time_precision=gp._time_precision, token_timestamps=token_timestamps, scores=scores)
 
     def _wrap_outputs(self, t, prompt_lens, pad, eos, return_dict_in_generate, return_segments, timestamps=False, time_precision=0.02,
                       token_timestamps=None, scores=None):
@@ -1507,15 +1551,10 @@ class WhisperMedusaModel:
             if "segments" not in out and return_segments:
                 out["segments"] = self._wrap_outputs(t, prompt_lens, pad, eos, False, True, timestamps, time_precision)["segments"]
             if "segments" in out:
-                for i, P in enumerate(prompt_lens):
-                    o = P
-                    for sg in out["segments"][i]:
-                        n = int(sg["tokens"].numel())
-                        sg["token_logprobs"] = fields["token_logprobs"][i, o: o + n]
-                        for name in _scores.TOPK_FIELDS:
-                            if name in fields:
-                                sg[name] = fields[name][i, o: o + n]
-                        o += n
+                for name in ("token_logprobs",) + _scores.TOPK_FIELDS:
+                    if name in fields:
+                        for i, P in enumerate(prompt_lens):
+                            _segment_slices(out["segments"][i], P, name, fields[name][i])
             out.update(fields)
             return out
         if token_timestamps is not None:
@@ -1525,11 +1564,7 @@ class WhisperMedusaModel:
             if return_segments:
                 segs = self._wrap_outputs(t, prompt_lens, pad, eos, False, True, timestamps, time_precision)["segments"]
                 for i, P in enumerate(prompt_lens):
-                    o = P
-                    for sg in segs[i]:
-                        n = int(sg["tokens"].numel())
-                        sg["token_timestamps"] = token_timestamps[i, o: o + n]
-                        o += n
+                    _segment_slices(segs[i], P, "token_timestamps", token_timestamps[i])
                 out["segments"] = segs
             return out
         if not return_dict_in_generate and not return_segments:
@@ -1552,17 +1587,7 @@ class WhisperMedusaModel:
 
     def _pad(self, seqs: List[List[int]], gp: GenParams) -> torch.Tensor:
         """G3: strip trailing pad/eos beyond the first EOS, right-pad to a tensor (model.py:1929-1973,1747-1762)."""
-        out = []
-        for s in seqs:
-            if gp.eos_token_id in s[len(gp.prompt):]:
-                j = s.index(gp.eos_token_id, len(gp.prompt))
-                s = s[: j + 1]
-            out.append(s)
-        T = max(len(s) for s in out)
-        t = torch.full((len(out), T), gp.pad_token_id, dtype=torch.long)
-        for i, s in enumerate(out):
-            t[i, : len(s)] = torch.tensor(s, dtype=torch.long)
-        return t.to(self.device)
+        return _ids_tensor([self._own_end(s, gp) for s in seqs], gp.pad_token_id).to(self.device)
 
     # ---- beyond the reference's generate(): language detection, long-form chunking, data-parallel sharding -------------
     @torch.no_grad()
@@ -1586,93 +1611,68 @@ class WhisperMedusaModel:
         best = z[:, ids].argmax(-1)
         return [toks[int(i)] for i in best]
 
-    def _generate_detecting_language(self, input_features, kw):
+    def _generate_detecting_language(self, input_features, call: "ResolvedCall"):
         langs = self.detect_language(input_features)
-        rdg, rseg = kw.pop("return_dict_in_generate", None), kw.pop("return_segments", False)
-        rts, tprec = bool(kw.get("return_timestamps")), kw.get("time_precision", 0.02)
         groups: Dict[str, List[int]] = {}
         for i, l in enumerate(langs):
             groups.setdefault(l, []).append(i)
-        rows: List[Optional[torch.Tensor]] = [None] * len(langs)
+        req, sreq, samp = call.tt_req, call.sc_req, call.samp
+        nret = call.beam["num_return_sequences"] if call.beam is not None else 1
+        rows: List[Optional[list]] = [None] * len(langs)
         plens = [0] * len(langs)
-        req, outer = kw.pop("_tt_req", None), kw.pop("_tt_outer", False)
-        sreq, souter = kw.pop("_sc_req", None), kw.pop("_sc_outer", False)
-        sids, sseeks = kw.pop("sampling_stream_ids", None), kw.pop("_sampling_seeks", None)      # (seeded sampling: they follow their clips into the groups)
         tts: List[Optional[torch.Tensor]] = [None] * len(langs)
         scs: List[Optional[dict]] = [None] * len(langs)
         ms_tt = ms_sc = 0.0
-        nret = int(kw.get("num_return_sequences") or 1) if (kw.get("vanilla") and kw.get("num_beams") not in (None, 1)) else 1
         bscores: Dict[int, torch.Tensor] = {}
+        nf = req["num_frames"] if req is not None else None
         for l, idx in groups.items():
-            # one group = every clip in its original order: the engine still holds the encoder pass detect_language() ran
-            reuse = {"_encoded_batch": len(langs)} if len(groups) == 1 else {}
-            if req is not None:         # per-stream num_frames follow their clips into the group
-                nf = req["num_frames"]
-                reuse["_tt_req"] = dict(req, num_frames=[nf[i] for i in idx] if isinstance(nf, list) else nf)
-            if sreq is not None:
-                reuse["_sc_req"] = sreq
-            if kw.get("sampling_seed") is not None:
-                reuse["sampling_stream_ids"] = [i if sids is None else int(sids[i]) for i in idx]
-                reuse["_sampling_seeks"] = None if sseeks is None else [sseeks[i] for i in idx]
-            out = self.generate(input_features[idx], language=l, _language_resolved=True, **reuse, **kw)
-            if req is not None:
-                ms_tt += self.last_stats.get("ms_token_timestamps", 0.0)
-            if sreq is not None:
-                ms_sc += self.last_stats.get("ms_token_logprobs", 0.0)
-            if kw.get("vanilla") and kw.get("num_beams") not in (None, 1):
-                bscores.update({i: self.last_sequences_scores[j * nret: (j + 1) * nret] for j, i in enumerate(idx)})
+            # one group = every clip in its original order: the engine still holds the encoder pass detect_language() ran.  Per-stream
+            # num_frames and the seeded sampling's stream ids follow their clips into the group
+            res = self._generate_short(input_features[idx], call, language=l, encoded=len(groups) == 1,
+                                       stream_ids=None if samp is None else [i if samp["ids"] is None else samp["ids"][i] for i in idx],
+                                       num_frames=[nf[i] for i in idx] if isinstance(nf, list) else None)
+            ms_tt += res.stats.get("ms_token_timestamps", 0.0)
+            ms_sc += res.stats.get("ms_token_logprobs", 0.0)
+            own = [self._own_end(s, res.gp) for s in res.seqs]
             for j, i in enumerate(idx):
-                rows[i] = out[j] if nret == 1 else out[j * nret: (j + 1) * nret]
-                plens[i] = len(self._last_prompt)
+                rows[i] = own[j * nret: (j + 1) * nret]     # (beam search with num_return_sequences: nret rows per clip)
+                plens[i] = len(res.gp.prompt)
+                if call.beam is not None:
+                    bscores[i] = res.sequences_scores[j * nret: (j + 1) * nret]
                 if req is not None:
-                    tts[i] = self._last_tt[j]
+                    tts[i] = res.token_timestamps[j]
                 if sreq is not None:
-                    scs[i] = {k: v[j] for k, v in self._last_sc.items() if not k.startswith("_")}
-        if nret > 1:            # beam search with num_return_sequences: every clip brings nret rows, clip-major
-            rows = [r_ for r in rows for r_ in r]
-            plens = [p_ for p_ in plens for _ in range(nret)]
-        T = max(r.numel() for r in rows)
-        t = torch.full((len(rows), T), self.config.pad_token_id, dtype=torch.long, device=self.device)
-        for i, r in enumerate(rows):
-            t[i, : r.numel()] = r
+                    scs[i] = {k: v[j] for k, v in res.scores.items() if not k.startswith("_")}
+        t = _ids_tensor([r_ for r in rows for r_ in r], self.config.pad_token_id).to(self.device)      # clip-major
+        plens = [p_ for p_ in plens for _ in range(nret)]
+        T = t.shape[1]
         self.detected_languages = langs
         tt = None
         if req is not None:
-            tt = torch.zeros(len(rows), T, dtype=torch.float32, device=self.device)
-            for i, r in enumerate(tts):
-                tt[i, : r.numel()] = r
-                tt[i, r.numel():] = r[-1]
-            self.last_stats["ms_token_timestamps"] = ms_tt
-            if outer:
-                self._last_tt = tt
-                tt = None
+            tt = _ts_tensor(tts, T)
+            res.stats["ms_token_timestamps"] = ms_tt
         sc = None
         if sreq is not None:
             # per-clip fields of the groups back in the clips' order; token_logprobs rows are 0 after a stream's end
             sc = {"_want": sreq["want"]}
             for k in scs[0]:
                 if k == "token_logprobs":
-                    sc[k] = torch.zeros(len(rows), T, dtype=torch.float32, device=self.device)
-                    for i, f in enumerate(scs):
-                        sc[k][i, : f[k].numel()] = f[k]
+                    sc[k] = _lp_tensor([f[k] for f in scs], T)
                 elif k in _scores.TOPK_FIELDS:      # [T_group(, k)] per clip: -1 / -inf / 0 behind the group's own length
                     if k == _scores.TOPK_FIELDS[0]:
                         sc.update(self._topk_stack(scs, T))
                 else:
                     sc[k] = torch.stack([f[k] for f in scs])
-            self.last_stats["ms_token_logprobs"] = ms_sc
-            if souter:
-                self._last_sc = sc
-                sc = None
-        out = self._wrap_outputs(t, plens, self.config.pad_token_id, self.config.eos_token_id, rdg, rseg, timestamps=rts,
-                                 time_precision=tprec, token_timestamps=tt, scores=sc)
+            res.stats["ms_token_logprobs"] = ms_sc
+        out = self._wrap_outputs(t, plens, self.config.pad_token_id, self.config.eos_token_id, call.return_dict_in_generate, call.return_segments,
+                                 timestamps=call.return_timestamps, time_precision=call.time_precision, token_timestamps=tt, scores=sc)
         if bscores:
-            self.last_sequences_scores = torch.cat([bscores[i] for i in range(len(langs))])
+            res.sequences_scores = torch.cat([bscores[i] for i in range(len(langs))])
             if isinstance(out, dict):
-                out["sequences_scores"] = self.last_sequences_scores
-        return out
+                out["sequences_scores"] = res.sequences_scores
+        return self._publish(res, out)
 
-    def _generate_longform(self, input_features, kw):
+    def _generate_longform(self, input_features, call: "ResolvedCall", language, detect: bool):
         """`chunk_longform=True`: clips longer than 30 s (the reference raises, model.py:1213-1214) are cut into 30 s windows,
         the windows of all clips are decoded as ONE batch of independent streams (that is what the engine's batch is), and
         each clip's windows are concatenated: prompt once, then the generated ids of every window without its EOS / padding.
@@ -1682,10 +1682,8 @@ class WhisperMedusaModel:
         With the scoring arguments every window is scored and gated on its own: a skipped window (no_speech_threshold) contributes no ids, no
         segments and no token timestamps to its clip and leaves the offsets of the following windows where they are."""
         cfg = self.config
-        kw.pop("chunk_longform", None)
-        rdg, sreq = kw.pop("return_dict_in_generate", None), kw.pop("_sc_req", None)
-        rseg, tprec = kw.pop("return_segments", False), kw.get("time_precision", 0.02)
-        rts = bool(kw.get("return_timestamps"))
+        rdg, sreq, req = call.return_dict_in_generate, call.sc_req, call.tt_req
+        rseg, tprec, rts = call.return_segments, call.time_precision, call.return_timestamps
         F = cfg.n_mel_frames
         B, _, T = input_features.shape
         n = -(-T // F)
@@ -1697,18 +1695,13 @@ class WhisperMedusaModel:
             x[..., T:] = input_features.to(self.device, torch.float32).amin(dim=(1, 2), keepdim=True)
         win = x.view(B, cfg.num_mel_bins, n, F).permute(0, 2, 1, 3).reshape(B * n, cfg.num_mel_bins, F).contiguous()
         # the language is detected ONCE per clip, on its first window, and every window of the clip is decoded in that language
-        # (clips of different languages go through generate() as separate groups, each with its own prompt)
-        if kw.get("language") is None and cfg.is_multilingual and kw.get("detect_language", True):
-            first = self.detect_language(win[::n])
-            kw["detect_language"] = False
-            langs = first
-        elif isinstance(kw.get("language"), (list, tuple)):
-            langs = list(kw["language"])            # language=[...]: one language per recording (generate() has checked and resolved them)
+        # (clips of different languages are decoded as separate groups, each with its own prompt); language=[...]: one language per
+        # recording (generate() has checked and resolved them)
+        if detect:
+            langs = self.detect_language(win[::n])
         else:
-            langs = [kw.get("language")] * B
-        kw.pop("language", None)
+            langs = list(language) if isinstance(language, (list, tuple)) else [language] * B
         rows, prompts = [None] * (B * n), [None] * B
-        req = kw.pop("_tt_req", None)
         if req is not None and req["num_frames"] is not None:
             raise NotImplementedError("num_frames= is not supported together with chunk_longform=True (the windows are fixed)")
         wtt = [None] * (B * n)
@@ -1717,96 +1710,67 @@ class WhisperMedusaModel:
         for l in sorted(set(langs), key=lambda v: (v is None, v or "")):
             clips = [b for b in range(B) if langs[b] == l]
             widx = [b * n + j for b in clips for j in range(n)]
-            o = self.generate(win[widx], language=l, **kw, **({"_tt_req": req} if req is not None else {}),
-                              **({"_sc_req": sreq} if sreq is not None else {}))
-            if req is not None:
-                ms_tt += self.last_stats.get("ms_token_timestamps", 0.0)
-            if sreq is not None:
-                ms_sc += self.last_stats.get("ms_token_logprobs", 0.0)
+            res = self._generate_short(win[widx], call, language=l)
+            o = self._pad(res.seqs, res.gp)
+            ms_tt += res.stats.get("ms_token_timestamps", 0.0)
+            ms_sc += res.stats.get("ms_token_logprobs", 0.0)
             for q, wi in enumerate(widx):
                 rows[wi] = o[q]
                 if req is not None:
-                    wtt[wi] = self._last_tt[q].cpu()
+                    wtt[wi] = res.token_timestamps[q].cpu()
                 if sreq is not None:
-                    wsc[wi] = {k: v[q].cpu() for k, v in self._last_sc.items() if not k.startswith("_")}
+                    wsc[wi] = {k: v[q].cpu() for k, v in res.scores.items() if not k.startswith("_")}
             for b in clips:
-                prompts[b] = list(self._last_prompt)
+                prompts[b] = list(res.gp.prompt)
         eos, pad = cfg.eos_token_id, cfg.pad_token_id
         seqs, all_tt, all_lp = [], [], []
         segs = [[] for _ in range(B)]
-        skipped = [[bool(wsc[b * n + j]["skipped"]) if sreq is not None and "skipped" in wsc[b * n + j] else False for j in range(n)] for b in range(B)]
         for b in range(B):
-            if rts and rseg:
-                for j in range(n):
-                    if skipped[b][j]:
-                        continue
-                    segs[b] += _timestamps.row_segments(rows[b * n + j].tolist(), len(prompts[b]), eos, cfg.timestamp_begin, F, tprec,
-                                                        time_offset=j * F * 0.01, result=rows[b * n + j])
             ids = list(prompts[b])
             P = len(ids)
             tts = [0.0] * P
             lps, last_eos_lp = [0.0] * P, 0.0
             for j in range(n):
-                if skipped[b][j]:
+                wi = b * n + j
+                if sreq is not None and "skipped" in wsc[wi] and bool(wsc[wi]["skipped"]):
                     continue
-                row = rows[b * n + j][P:].tolist()
-                for q, t in enumerate(row):
+                start = torch.tensor(j * F * 0.01, dtype=torch.float32)       # the window's start (float32 sum, as the tensors hold it)
+                if rts and rseg:
+                    ws = _timestamps.row_segments(rows[wi].tolist(), P, eos, cfg.timestamp_begin, F, tprec, time_offset=j * F * 0.01, result=rows[wi])
+                    if req is not None:     # each segment's slice of its own window's values (times offset like its start / end)
+                        _segment_slices(ws, P, "token_timestamps", wtt[wi] + start)
+                    if sreq is not None:
+                        _segment_slices(ws, P, "token_logprobs", wsc[wi]["token_logprobs"])
+                    segs[b] += ws
+                for q, t in enumerate(rows[wi][P:].tolist()):
                     if t == eos or t == pad:
                         if sreq is not None:      # the clip's one EOS takes the score of the last kept window's
-                            last_eos_lp = float(wsc[b * n + j]["token_logprobs"][P + q])
+                            last_eos_lp = float(wsc[wi]["token_logprobs"][P + q])
                         break
                     ids.append(t)
                     if sreq is not None:
-                        lps.append(float(wsc[b * n + j]["token_logprobs"][P + q]))
-                    if req is not None:       # the window's own value, offset by the window's start (float32 sum, as the tensor holds it)
-                        tts.append(float(wtt[b * n + j][P + q] + torch.tensor(j * F * 0.01, dtype=torch.float32)))
+                        lps.append(float(wsc[wi]["token_logprobs"][P + q]))
+                    if req is not None:       # the window's own value, offset by the window's start
+                        tts.append(float(wtt[wi][P + q] + start))
             seqs.append(ids + [eos])
             all_tt.append(tts + [tts[-1]])
             all_lp.append(lps + [last_eos_lp])
-            if (req is not None or sreq is not None) and rts and rseg:      # each segment's slice of its own window's values (times offset like its start / end)
-                k = 0
-                for j in range(n):
-                    if skipped[b][j]:
-                        continue
-                    o = P
-                    nseg = len(_timestamps.row_segments(rows[b * n + j].tolist(), P, eos, cfg.timestamp_begin, F, tprec))
-                    for sg in segs[b][k: k + nseg]:
-                        m = int(sg["tokens"].numel())
-                        if req is not None:
-                            sg["token_timestamps"] = wtt[b * n + j][o: o + m] + torch.tensor(j * F * 0.01, dtype=torch.float32)
-                        if sreq is not None:
-                            sg["token_logprobs"] = wsc[b * n + j]["token_logprobs"][o: o + m]
-                        o += m
-                    k += nseg
-        Tm = max(len(s_) for s_ in seqs)
-        t = torch.full((B, Tm), pad, dtype=torch.long, device=self.device)
-        for i, s_ in enumerate(seqs):
-            t[i, : len(s_)] = torch.tensor(s_, dtype=torch.long)
+        t = _ids_tensor(seqs, pad).to(self.device)
         fields = None
         if sreq is not None:
             # per clip: the kept tokens' scores, their average and the compression ratio of the assembled ids; per window [B, n]: the gate's inputs and verdicts
-            lp = torch.zeros(B, Tm, dtype=torch.float32)
-            for i, r in enumerate(all_lp):
-                lp[i, : len(r)] = torch.tensor(r, dtype=torch.float32)
-            Pb = [len(p_) for p_ in prompts]
-            fields = dict(token_logprobs=lp.to(self.device),
-                          avg_logprob=torch.tensor([_scores.avg_logprob(all_lp[i], Pb[i], len(seqs[i])) for i in range(B)], dtype=torch.float32, device=self.device),
-                          compression_ratio=torch.tensor([_scores.compression_ratio(seqs[i][Pb[i]:], cfg.vocab_size) for i in range(B)],
-                                                         dtype=torch.float32, device=self.device),
-                          lengths=torch.tensor([len(s_) for s_ in seqs], dtype=torch.long, device=self.device))
+            fields = self._clip_score_fields(all_lp, seqs, prompts)
             for k in ("no_speech_prob", "skipped", "needs_fallback"):
                 if k in wsc[0]:
                     fields[k] = torch.stack([wsc[i][k] for i in range(B * n)]).view(B, n).to(self.device)
             fields["window_avg_logprob"] = torch.stack([wsc[i]["avg_logprob"] for i in range(B * n)]).view(B, n).to(self.device)
             self.last_scores = fields
-            self.last_stats["ms_token_logprobs"] = ms_sc
+            res.stats["ms_token_logprobs"] = ms_sc
         if req is not None:
-            tt = torch.zeros(B, Tm, dtype=torch.float32)
-            for i, r in enumerate(all_tt):
-                tt[i, : len(r)] = torch.tensor(r, dtype=torch.float32)
-                tt[i, len(r):] = r[-1]
-            self.last_stats["ms_token_timestamps"] = ms_tt
-            out = GenerateEncoderDecoderOutput(t, token_timestamps=tt.to(self.device))
+            res.stats["ms_token_timestamps"] = ms_tt
+        self._publish(res, None)
+        if req is not None:
+            out = GenerateEncoderDecoderOutput(t, token_timestamps=_ts_tensor(all_tt).to(self.device))
             if rts and rseg:
                 out["segments"] = segs
             if fields is not None:
@@ -1850,21 +1814,18 @@ class WhisperMedusaModel:
             raise NotImplementedError("prompt_ids with sequential_longform needs prompt_condition_type='all-segments': every window of a "
                                       "clip is decoded under the same prompt (HF's default, 'first-segment', needs one prompt per stream)")
 
-    def _generate_sequential(self, input_features, attention_mask, kw):
+    def _generate_sequential(self, input_features, attention_mask, call: "ResolvedCall", language, detect: bool, tprec_f: float):
         """`sequential_longform=True`: Whisper's own long-form algorithm (openai/whisper ``transcribe``; HF ``WhisperGenerationMixin.generate``
         on more than one window of features), batched over recordings.  Every clip keeps a seek into its features; per round the windows of
         all unfinished clips are cut out at their seeks in one launch (``wm_gather_windows``: slice, then zero pad, HF ``_get_input_segment``)
-        and decoded as one batch through the short-form path — timestamps on, the same prompt for every window of a clip, the scoring
-        side-request when thresholds are given —; each clip then seeks to its window's last timestamp pair (the unfinished tail is decoded
+        and decoded as one batch through the short-form driver — timestamps on, the same prompt for every window of a clip, the scoring
+        request when thresholds are given —; each clip then seeks to its window's last timestamp pair (the unfinished tail is decoded
         again, whole, by the next window) or, with no pair / a single closing timestamp / a window the no-speech gate skipped, by the whole
         window (``timestamps.sequential_seek_loop``).  The language is detected once per clip, on its first window; clips of different
-        languages run as separate groups per round.  No conditioning on the previous window, no temperature fallback (both refused)."""
+        languages run as separate groups per round.  No conditioning on the previous window; the temperature fallback needs sampling_seed=."""
         cfg = self.config
-        for k in ("sequential_longform", "chunk_longform", "streamer", "alignment_heads"):
-            kw.pop(k, None)
-        rdg, sreq, rseg = kw.pop("return_dict_in_generate", None), kw.pop("_sc_req", None), kw.pop("return_segments", False)
-        tprec, tprec_f = kw.pop("time_precision", 0.02), kw.pop("time_precision_features", 0.01)
-        num_frames = kw.pop("num_frames", None)
+        rdg, sreq, rseg, tprec = call.return_dict_in_generate, call.sc_req, call.return_segments, call.time_precision
+        num_frames = call.opts.get("num_frames")
         F, eos, pad = cfg.n_mel_frames, cfg.eos_token_id, cfg.pad_token_id
         B, _, T = input_features.shape
         # per-clip lengths: HF's way (max_frames = attention_mask.sum(-1)), or num_frames=, else the whole tensor
@@ -1880,19 +1841,15 @@ class WhisperMedusaModel:
         if B > self._max_batch:
             self.set_max_batch(B)
         feats = input_features.to(self.device, torch.float32).contiguous()
-        detect = kw.get("language") is None and cfg.is_multilingual and kw.pop("detect_language", True)
-        langs: List[Optional[str]] = [None if detect else kw.get("language")] * B
-        if isinstance(kw.get("language"), (list, tuple)):
-            langs = list(kw["language"])            # language=[...]: one language per recording (generate() has checked and resolved them)
-        kw.pop("language", None)
-        kw.pop("detect_language", None)
+        # language=[...]: one language per recording (generate() has checked and resolved them)
+        langs: List[Optional[str]] = list(language) if isinstance(language, (list, tuple)) else [None if detect else language] * B
         prompts: List[Optional[List[int]]] = [None] * B
-        ms_sc = [0.0]
         # seeded sampling / temperature fallback: a window's stream key comes from its clip's id and its seek, not from the round
-        sampling = kw.get("sampling_seed") is not None
-        sids, n_fb = kw.pop("sampling_stream_ids", None), [0]
+        sampling = call.opts.get("sampling_seed") is not None
+        sids = call.opts.get("sampling_stream_ids")
         if sids is not None and len(sids) != B:
             raise ValueError(f"sampling_stream_ids needs one id per clip ({B}), got {len(sids)}")
+        done: List[ShortResult] = []            # the short-form results, in order
 
         def decode_round(clips, seeks, snf):
             win = self.engine.gather_windows(feats, clips, seeks, snf)
@@ -1904,20 +1861,17 @@ class WhisperMedusaModel:
             groups = sorted({langs[b] for b in clips}, key=lambda v: (v is None, v or ""))
             for l in groups:
                 widx = [q for q, b in enumerate(clips) if langs[b] == l]
-                reuse = {"_encoded_batch": len(clips)} if len(groups) == 1 and len(new) == len(clips) else {}
-                if sampling:
-                    reuse["sampling_stream_ids"] = [clips[q] if sids is None else int(sids[clips[q]]) for q in widx]
-                    reuse["_sampling_seeks"] = [int(seeks[q]) for q in widx]
-                o = self.generate(win[widx], language=l, _language_resolved=True, return_timestamps=True, time_precision=tprec,
-                                  **reuse, **kw, **({"_sc_req": sreq} if sreq is not None else {}))
-                P = len(self._last_prompt)
+                res = self._generate_short(win[widx], call, language=l, encoded=len(groups) == 1 and len(new) == len(clips),
+                                           stream_ids=[clips[q] if sids is None else int(sids[clips[q]]) for q in widx] if sampling else None,
+                                           seeks=[int(seeks[q]) for q in widx] if sampling else None)
+                done.append(res)
+                o = self._pad(res.seqs, res.gp)
+                P = len(res.gp.prompt)
                 rows = o.cpu()
-                n_fb[0] += self.last_stats.get("fallback_decodes", 0)
                 if sreq is not None:
-                    ms_sc[0] += self.last_stats.get("ms_token_logprobs", 0.0)
-                    sc = {k: v.cpu() for k, v in self._last_sc.items() if not k.startswith("_")}
+                    sc = {k: v.cpu() for k, v in res.scores.items() if not k.startswith("_")}
                 for j, q in enumerate(widx):
-                    prompts[clips[q]] = list(self._last_prompt)
+                    prompts[clips[q]] = list(res.gp.prompt)
                     rec = dict(ids=_timestamps.generated_ids(rows[j].tolist(), P, eos), skipped=False, result=o[j])
                     if sreq is not None:
                         rec["scores"] = {k: v[j] for k, v in sc.items()}
@@ -1929,26 +1883,21 @@ class WhisperMedusaModel:
                                                    F // cfg.max_source_positions)
         for b in range(B):
             if prompts[b] is None:      # a clip without a single frame: nothing was decoded, its row is the default prompt + EOS
-                prompts[b] = list(self._gen_params(langs[b], kw.get("task"), None, None, None, None, False, None, None, None, None,
-                                                   kw.get("prompt_ids"), timestamps=True).prompt)
+                prompts[b] = list(self._gen_params(langs[b], call.task, None, None, None, None, False, None, None, None, None,
+                                                   call.prompt_ids, timestamps=True).prompt)
         seqs = [_timestamps.assemble_sequence(prompts[b], windows[b], eos) for b in range(B)]
         segs = [[sg for w in windows[b] for sg in w["segments"]] for b in range(B)]
-        Tm = max(len(s_) for s_ in seqs)
-        t = torch.full((B, Tm), pad, dtype=torch.long, device=self.device)
-        for i, s_ in enumerate(seqs):
-            t[i, : len(s_)] = torch.tensor(s_, dtype=torch.long)
+        t = _ids_tensor(seqs, pad).to(self.device)
         if detect:
             self.detected_languages = list(langs)
-        stats = dict(getattr(self, "last_stats", None) or {})
+        stats = dict(done[-1].stats) if done else {}
         stats["longform_windows"] = [len(w) for w in windows]
         if sampling:
-            stats["fallback_decodes"] = n_fb[0]
-        self.last_stats = stats
+            stats["fallback_decodes"] = sum(r.stats.get("fallback_decodes", 0) for r in done)
         fields = None
         if sreq is not None:
             # per clip: the kept tokens' scores (a window's kept segments are a prefix of its ids), their average and the compression ratio of the
             # assembled ids; per window, ragged (clips take different numbers of windows): the gate's inputs and verdicts
-            lp = torch.zeros(B, Tm, dtype=torch.float32)
             all_lp = []
             for b in range(B):
                 P = len(prompts[b])
@@ -1962,20 +1911,9 @@ class WhisperMedusaModel:
                     k = P + len(w["ids"])                       # the window's own EOS, where it emitted one
                     last_eos = float(wl[k]) if k < int(w["scores"]["lengths"]) else 0.0
                     if rseg:
-                        o = P
-                        for sg in w["segments"]:
-                            m = int(sg["tokens"].numel())
-                            sg["token_logprobs"] = wl[o: o + m]
-                            o += m
-                r.append(last_eos)
-                all_lp.append(r)
-                lp[b, : len(r)] = torch.tensor(r, dtype=torch.float32)
-            Pb = [len(p_) for p_ in prompts]
-            fields = dict(token_logprobs=lp.to(self.device),
-                          avg_logprob=torch.tensor([_scores.avg_logprob(all_lp[i], Pb[i], len(seqs[i])) for i in range(B)], dtype=torch.float32, device=self.device),
-                          compression_ratio=torch.tensor([_scores.compression_ratio(seqs[i][Pb[i]:], cfg.vocab_size) for i in range(B)],
-                                                         dtype=torch.float32, device=self.device),
-                          lengths=torch.tensor([len(s_) for s_ in seqs], dtype=torch.long, device=self.device))
+                        _segment_slices(w["segments"], P, "token_logprobs", wl)
+                all_lp.append(r + [last_eos])
+            fields = self._clip_score_fields(all_lp, seqs, prompts)
             any_w = next((w for ws in windows for w in ws), None)
             for k in ("no_speech_prob", "skipped", "needs_fallback"):
                 if any_w is not None and k in any_w["scores"]:
@@ -1987,7 +1925,10 @@ class WhisperMedusaModel:
                 fields["window_attempts"] = [torch.stack([w["scores"]["fallback_attempts"] for w in ws]) if ws else torch.zeros(0, dtype=torch.long)
                                              for ws in windows]
             self.last_scores = fields
-            self.last_stats["ms_token_logprobs"] = ms_sc[0]
+            stats["ms_token_logprobs"] = sum(r.stats.get("ms_token_logprobs", 0.0) for r in done)
+        if done:
+            self._publish(done[-1], None)
+        self.last_stats = stats
         if fields is not None and (sreq["want"] or rdg):
             out = GenerateEncoderDecoderOutput(t, **fields)
             if rseg or rdg:
@@ -1998,6 +1939,17 @@ class WhisperMedusaModel:
         if rseg:
             return dict({"sequences": t, "segments": segs}, **(fields or {}))
         return t
+
+    def _clip_score_fields(self, all_lp, seqs, prompts) -> dict:
+        """The per-clip score fields of a long-form result: the kept tokens' log-probabilities ``all_lp`` next to the assembled ids ``seqs``,
+        their average, the compression ratio of the ids behind each clip's prompt, and the rows' lengths."""
+        dev, n = self.device, range(len(seqs))
+        Pb = [len(p_) for p_ in prompts]
+        return dict(token_logprobs=_lp_tensor(all_lp, max(len(s_) for s_ in seqs)).to(dev),
+                    avg_logprob=torch.tensor([_scores.avg_logprob(all_lp[i], Pb[i], len(seqs[i])) for i in n], dtype=torch.float32, device=dev),
+                    compression_ratio=torch.tensor([_scores.compression_ratio(seqs[i][Pb[i]:], self.config.vocab_size) for i in n],
+                                                   dtype=torch.float32, device=dev),
+                    lengths=torch.tensor([len(s_) for s_ in seqs], dtype=torch.long, device=dev))
 
     @torch.no_grad()
     def generate_sharded(self, input_features: torch.Tensor, **kw) -> torch.Tensor:
@@ -2032,20 +1984,15 @@ class WhisperMedusaModel:
             if scoring:     # every rank's per-stream score fields travel like its ids (ragged Python lists)
                 local_sc = [(s_, {k: v[j].tolist() for k, v in self.last_scores.items()}) for j, s_ in enumerate(mine)]
         seqs = _dist.gather_token_lists(local)
-        pad = self.config.pad_token_id
-        T = max(len(s_) for s_ in seqs)
-        t = torch.full((len(seqs), T), pad, dtype=torch.long, device=self.device)
-        for i, s_ in enumerate(seqs):
-            t[i, : len(s_)] = torch.tensor(s_, dtype=torch.long)
+        t = _ids_tensor(seqs, self.config.pad_token_id).to(self.device)
+        T = t.shape[1]
         if not scoring:
             return t
         infos = _dist.gather_token_lists(local_sc)
         fields = {}
         for k in infos[0]:
             if k == "token_logprobs":
-                fields[k] = torch.zeros(B, T, dtype=torch.float32, device=self.device)
-                for i, f in enumerate(infos):
-                    fields[k][i, : len(f[k])] = torch.tensor(f[k], dtype=torch.float32)
+                fields[k] = _lp_tensor([f[k] for f in infos], T).to(self.device)
             elif k in _scores.TOPK_FIELDS:
                 if k == _scores.TOPK_FIELDS[0]:
                     fields.update(self._topk_stack([{n_: torch.tensor(f[n_]) for n_ in _scores.TOPK_FIELDS} for f in infos], T))

@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import json
 import os
-from dataclasses import dataclass, field, asdict
+from dataclasses import dataclass, field, asdict, replace
 from typing import List, Optional, Sequence, Tuple, Union
 
 HEAD_DIM = 64  # every Whisper size uses 64-wide attention heads
@@ -370,6 +370,12 @@ class GenParams:
     # the rows differ in the language token).  `prompt` stays a valid representative — row 0 — for every scalar derived from it.  None = off
     prompts: Optional[List[List[int]]] = None
 
+    # Host side only (never lowered into wm_gen_params): the processors / criteria lower_processors() keeps for the host loop, and the seconds
+    # per timestamp token the segments of this call are cut with
+    _host_processors: Optional[list] = None
+    _host_criteria: Optional[list] = None
+    _time_precision: float = 0.02
+
     def prompt_of(self, b: int) -> List[int]:
         """The decoder prompt of stream ``b`` of this decode."""
         return self.prompt if not self.prompts else self.prompts[b]
@@ -379,11 +385,8 @@ class GenParams:
         when there are none)."""
         if not self.prompts:
             return self
-        import copy
-        g = copy.copy(self)             # (keeps what generate() hangs on the object: _time_precision)
-        g.prompts = [list(self.prompts[b]) for b in idx]
-        g.prompt = list(g.prompts[0])
-        return g
+        rows = [list(self.prompts[b]) for b in idx]
+        return replace(self, prompts=rows, prompt=list(rows[0]))
 
     @property
     def repeat_rules(self) -> bool:
