@@ -335,6 +335,35 @@ typedef struct wm_seq_bias_params {
 } wm_seq_bias_params;
 int wm_set_sequence_bias(wm_ctx* ctx, const wm_seq_bias_params* sb /* NULL = off */);
 
+/* Constrained decoding on the plain decode path (additive to ABI v9; csrc/wm_constraint.hip).  Stands in for HF
+ * generate(prefix_allowed_tokens_fn=...) — PrefixConstrainedLogitsProcessor (transformers generation/logits_process.py), the interface this replaces —
+ * in the one form a decode loop whose logits never leave the device can run: the callback that walks a FIXED LIST of token sequences (a trie).  The
+ * reference builds no such processor (model.py:1168-1207).  A table is a non-empty set S of distinct sequences of 1..WM_CONSTRAINT_MAX_LEN ids in
+ * [0, vocab); eos stands inside none of them and closes every one implicitly.  For a row with prefix ids[:len], P = wm_gen_params.prompt_len (one for
+ * all streams, also under wm_set_stream_prompts), g = ids[P:len], t = len - P, the allowed set A(g) is
+ *   every s[t] of the s in S with len(s) > t and s[:t] == g; plus eos when some s == g (a sequence that is a prefix of another gives both); eos alone
+ *   when no s starts with g (the function is total: HF's processor raises on an empty list instead),
+ * and the row is edited IN PLACE: x[v] stays for v in A(g), every other element becomes -inf.  Allowed elements are not rewritten, so the row equals
+ * HF's scores + mask as fp32 values on rows without +inf / NaN.  Nothing is kept per stream: the set is derived from the row's own ids on every step
+ * (two binary searches over the sorted table, ceil(log2(n + 1)) dependent loads whatever t is), so beam reorders, finished streams and the tap need
+ * nothing.  HF's order puts the processor behind sequence bias, repetition penalty, no-repeat n-grams and bad words and before the suppress lists; a
+ * -inf mask commutes with all of them, so the engine applies it to the raw row right behind the sequence bias — under beams behind the log-softmax
+ * normaliser, where the bias goes.  It does not commute with the exponential decay on eos (-inf + inf p is NaN in HF too): refused.
+ * Sticky on the context until cleared (NULL), like wm_set_sequence_bias; read by wm_decode_begin / wm_decode_begin_ts only (the scoring and alignment
+ * replays do not know the mask).  The tables live in device memory allocated once at their maximum size: a captured graph stays valid across tables
+ * with the same number of sequences.  WM_ERR_ARG (wm_last_error names the cause) from wm_set_constraint: n outside [1, WM_CONSTRAINT_MAX], a length
+ * outside [1, WM_CONSTRAINT_MAX_LEN], an id outside [0, vocab), two identical sequences; from wm_decode_begin*, which know eos, the path and the lists:
+ * wm_gen_params.vanilla == 0, a candidate-tree context, timestamp rules on (a timestamp is never in the set: the rules would force a row of -inf),
+ * the exponential decay on, eos inside a sequence, an id of a sequence in the suppress list, a first id in the begin-suppress list. */
+#define WM_CONSTRAINT_MAX 16384    /* sequences */
+#define WM_CONSTRAINT_MAX_LEN 32   /* ids per sequence, the closing eos not counted */
+typedef struct wm_constraint_params {
+    const int32_t* tokens;   /* HOST, the sequences' ids back to back */
+    const int32_t* lens;     /* HOST [n], 1..WM_CONSTRAINT_MAX_LEN */
+    int32_t n;
+} wm_constraint_params;
+int wm_set_constraint(wm_ctx* ctx, const wm_constraint_params* c /* NULL = off */);
+
 /* Per-stream decoder prompts of ONE common length (additive to ABI v9).  Stands in for the rows HF's
  * WhisperGenerationMixin._retrieve_init_tokens builds for generate(language=[...]) — one row of init tokens per clip, which differ in the language
  * token alone — and which the reference never builds (model.py:1519-1537 takes one language).  prompts: HOST int32 [B][P], copied; clip b of the next
@@ -506,6 +535,16 @@ int wm_seq_bias_rows(wm_ctx* ctx, const wm_seq_bias_params* sb, int R,
                      const float* logits /* HOST [R][vocab] */,
                      const int32_t* prefixes /* HOST [R][Tmax] */, int Tmax, const int32_t* lens /* [R] */,
                      float* out /* HOST [R][vocab] */);
+/* Constraint parity tap (HF PrefixConstrainedLogitsProcessor.__call__ on caller-given rows): the kernel alone, no model.  R rows (HOST float32
+ * [R][vocab]) through k_constraint under the sequences of c (checked and sorted as wm_set_constraint does; the context's own sticky table is
+ * back in place afterwards), row r under prefix prefixes[r][0 .. lens[r]) (HOST int32 [R][Tmax]) whose first prompt_len ids are the decoder prompt;
+ * out (HOST float32 [R][vocab]) = the masked rows, n_allowed[r] (may be NULL) = |A| of row r.  WM_ERR_ARG (wm_last_error names the cause) for a bad
+ * c, eos outside the vocabulary or inside a sequence, R < 1, lens outside [1, Tmax] or below prompt_len.  Overwrites ctx->logits of the decode state
+ * (begin again afterwards).  Any R >= 1 (worked in groups of WM_TAP_ROWS, csrc/wm_internal.h). */
+int wm_constraint_rows(wm_ctx* ctx, const wm_constraint_params* c, int eos, int prompt_len, int R,
+                       const float* logits /* HOST [R][vocab] */,
+                       const int32_t* prefixes /* HOST [R][Tmax] */, int Tmax, const int32_t* lens /* [R] */,
+                       float* out /* HOST [R][vocab] */, int32_t* n_allowed /* HOST [R], may be NULL */);
 /* Language-pick parity tap (HF detect_language's mask + argmax on caller-given rows): k_lang_pick alone, no model.  R rows (HOST float32 [R][vocab])
  * under the candidates lang_ids (HOST int32 [n]); out (HOST int32 [R]) as wm_detect_language defines it.  WM_ERR_ARG (wm_last_error names the cause)
  * as wm_detect_language's for lang_ids / n, and for R < 1 or a null pointer.  Overwrites ctx->logits of the decode state (begin again afterwards).

@@ -493,6 +493,7 @@ int wm_beam_step(wm_ctx* ctx, const GenDev& gp, const TsDev& ts, const BeamDev& 
     // sequence bias (wm_set_sequence_bias): HF runs its processors on log_softmax(raw), so the normaliser above is the unbiased row's; the rows
     // are edited in place before the kernels below subtract it.  (The taps run with the context's scalars swapped: ctx->sbias is a decode's.)
     if (kv && ctx->sbias.on) { if (int rc = wm_seq_bias_launch(ctx, ctx->sbias, ctx->ids, gp.Tids, ctx->L, gp.Tids, rows)) return rc; }
+    if (kv && ctx->cons.on) { if (int rc = wm_constraint_launch(ctx, ctx->cons, gp, ctx->ids, gp.Tids, ctx->L, gp.Tids, rows)) return rc; }     // (wm_set_constraint: the same place)
     if (ts.on) {
         k_beam_region<<<dim3(SEL_SP, rows), dim3(256), rp_bytes, st>>>(ctx->logits, gp, ctx->supmask, ctx->exppen, ctx->L, ts, bd, ctx->done);
         WM_HIP(hipGetLastError());

@@ -1885,6 +1885,11 @@ int wm_dec_iteration(wm_ctx* ctx, int Mper_base)
                 rc = wm_seq_bias_launch(ctx, ctx->sbias, ctx->ids + (size_t)b0 * gp.Tids, gp.Tids, ctx->L + b0, gp.Tids, nb);
                 if (rc) return rc;
             }
+            // constraint (wm_set_constraint; wm_constraint.hip): a -inf mask commutes with the bias and with everything below, so it goes right behind it
+            if (ctx->cons.on && !ctx->beam.on) {
+                rc = wm_constraint_launch(ctx, ctx->cons, gp, ctx->ids + (size_t)b0 * gp.Tids, gp.Tids, ctx->L + b0, gp.Tids, nb);
+                if (rc) return rc;
+            }
             if (ctx->beam.on) {     // beam search (wm_set_beam; wm_beam.hip): select, bookkeeping and reorder stand in for the arg-max and the accept below
                 return wm_beam_step(ctx, gp, ts, ctx->beam, true);
             }

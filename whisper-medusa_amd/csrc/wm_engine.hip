@@ -42,6 +42,7 @@ extern "C" void wm_destroy(wm_ctx* ctx)
     wm_score_free(ctx);
     wm_beam_free(ctx);
     wm_seq_bias_free(ctx);
+    wm_constraint_free(ctx);
     if (ctx->ev0) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) hipEventDestroy(ctx->ev1);
     if (ctx->own_stream && ctx->stream) hipStreamDestroy(ctx->stream);
@@ -504,6 +505,8 @@ extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm
     }
     SeqBiasDev sbd{};                      // sequence bias (wm_set_sequence_bias): the sticky table's device form, after what only a decode can check
     if (int rc = wm_seq_bias_begin(ctx, "wm_decode_begin", gp, &sbd)) return rc;
+    ConstraintDev cd{};                    // constraint (wm_set_constraint): the same for the sticky table of allowed sequences
+    if (int rc = wm_constraint_begin(ctx, "wm_decode_begin", gp, tsp, &cd)) return rc;
     // the processors' tables and the scalars of this decode
     GenDev g{}; TsDev ts{};
     if (int rc = wm_proc_setup(ctx, "wm_decode_begin", gp, tsp, &g, &ts)) return rc;
@@ -521,11 +524,11 @@ extern "C" int wm_decode_begin_ts(wm_ctx* ctx, const wm_gen_params* gp, const wm
     BeamDev bd{};
     if (beam) { if (int rc = wm_beam_begin(ctx, ctx->beam_set, G, g, true, nullptr, P, &bd)) return rc; }
     // the captured graphs: this decode's slot keeps its graphs when they were captured with the same key; the other slot is not touched
-    const DecGraphKey key = wm_dec_graph_key(g, B, ts, sd, sbd, bd);
+    const DecGraphKey key = wm_dec_graph_key(g, B, ts, sd, sbd, cd, bd);
     DecGraphSlot& slot = beam ? ctx->graphs_beam : ctx->graphs_plain;
     if (!(key == slot.key)) { slot.drop(); slot.key = key; }
     ctx->fuse = fuse; ctx->host_carry = host_carry; ctx->dev_carry = dev_carry; ctx->step_flow = step_flow;
-    ctx->gp = g; ctx->Bdec = B; ctx->ts = ts; ctx->samp = sd; ctx->sbias = sbd; ctx->beam = bd; ctx->beam_clips = beam ? G : 0;       // (the context's scalars are this decode's from here on)
+    ctx->gp = g; ctx->Bdec = B; ctx->ts = ts; ctx->samp = sd; ctx->sbias = sbd; ctx->cons = cd; ctx->beam = bd; ctx->beam_clips = beam ? G : 0;       // (the context's scalars are this decode's from here on)
     hipStream_t st = ctx->stream;           // uploads
     if (sd.on) WM_HIP(hipMemcpyAsync(ctx->samp_keys, ctx->samp_set_keys.data(), B * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     std::vector<int> ids((size_t)B * Tids, gp->pad_token_id), L(B, P), zero(B, 0);

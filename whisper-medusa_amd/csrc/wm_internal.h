@@ -112,6 +112,16 @@ struct SeqBiasDev {
     const int* etok;                // [entries][WM_SEQ_BIAS_MAX_LEN] the entry's first m - 1 ids
 };
 
+// Constrained decoding on the plain decode path (wm_set_constraint; csrc/wm_constraint.hip).  Passed by value to k_constraint, which
+// masks the fp32 logits rows in place right behind k_seq_bias; nothing else reads it.  The two copies of the sorted table belong to
+// wm_constraint_state (allocated once at their maximum size: the addresses never change); `on` and `n` ride in the launch, so they are part of
+// DecGraphKey (below).
+struct ConstraintDev {
+    int on, n;                      // sequences
+    const int* rowmaj;              // [n][WM_CONSTRAINT_MAX_LEN + 1] the sorted sequences, each closed by -2 and padded with -1
+    const int* colmaj;              // [WM_CONSTRAINT_MAX_LEN + 1][n] the same, transposed
+};
+
 // What a captured decode graph was captured with: every scalar its launches carry by value.  wm_decode_begin_ts keeps the graphs of a slot (below)
 // exactly when the decode's key equals the slot's.  A new scalar passed by value to a captured launch is added HERE (the struct and
 // wm_dec_graph_key) and nowhere else.  Buffer pointers stay out: every buffer the launches name is allocated once per context, at its max_batch size,
@@ -122,14 +132,16 @@ struct DecGraphKey {
     int ts_on, tb, nots, mit, rp; float rp_pen; int rp_g;               // TsDev
     int samp_on; float inv_t; unsigned seed_lo, seed_hi;                // SampDev (all zero while sampling is off)
     int top_k; float top_p, min_p;                                      // SampDev's filter (all zero while sampling is off; off: 0, 1, 0)
-    int sb_on, ngroups;                                                 // SeqBiasDev (an even number of words: no tail padding)
+    int sb_on, ngroups;                                                 // SeqBiasDev
+    int cons_on, cons_n;                                                // ConstraintDev (an even number of words: no tail padding)
 };
-static_assert(sizeof(GenDev) == 19 * 4 && sizeof(DecGraphKey) == sizeof(void*) + sizeof(GenDev) + 23 * 4, "DecGraphKey must have no padding");
+static_assert(sizeof(GenDev) == 19 * 4 && sizeof(DecGraphKey) == sizeof(void*) + sizeof(GenDev) + 25 * 4, "DecGraphKey must have no padding");
 static inline bool operator==(const DecGraphKey& a, const DecGraphKey& b) { return std::memcmp(&a, &b, sizeof(DecGraphKey)) == 0; }
-static inline DecGraphKey wm_dec_graph_key(const GenDev& g, int B, const TsDev& ts, const SampDev& sd, const SeqBiasDev& sbd, const BeamDev& bd)
+static inline DecGraphKey wm_dec_graph_key(const GenDev& g, int B, const TsDev& ts, const SampDev& sd, const SeqBiasDev& sbd, const ConstraintDev& cd,
+                                           const BeamDev& bd)
 {
     DecGraphKey k{};
-    k.g = g; k.B = B; k.sb_on = sbd.on; k.ngroups = sbd.ngroups;
+    k.g = g; k.B = B; k.sb_on = sbd.on; k.ngroups = sbd.ngroups; k.cons_on = cd.on; k.cons_n = cd.n;
     k.ts_on = ts.on; k.tb = ts.tb; k.nots = ts.nots; k.mit = ts.mit; k.rp = ts.rp; k.rp_pen = ts.rp_pen; k.rp_g = ts.rp_g;
     if (sd.on) { k.samp_on = sd.on; k.inv_t = sd.inv_t; k.seed_lo = sd.seed_lo; k.seed_hi = sd.seed_hi; k.top_k = sd.top_k; k.top_p = sd.top_p; k.min_p = sd.min_p; }
     if (bd.on) { k.beam_on = bd.on; k.n = bd.n; k.G = bd.G; k.es = bd.es; k.lp_pos = bd.lp_pos; k.rows_cap = bd.rows_cap; k.sh_kv = bd.sh_kv; }
@@ -301,7 +313,7 @@ struct wm_ctx {
     int* tap_tok = nullptr;
     int* done = nullptr;                   // [0] = all streams finished, [1] = number of finished streams
     bool use_done = false;
-    // gp / ts / samp / sbias / beam: the scalars of the decode or call in flight, nothing else (the graphs' keys live in the slots below)
+    // gp / ts / samp / sbias / cons / beam: the scalars of the decode or call in flight, nothing else (the graphs' keys live in the slots below)
     GenDev gp{};
     TsDev ts{};                            // timestamp rules (ts.on = 0: off); buffers allocated in wm_create
     wm_repeat_params rep{1.0f, 0};         // wm_set_repeat_rules: sticky until cleared (neutral = off)
@@ -322,6 +334,9 @@ struct wm_ctx {
     // wm_set_sequence_bias: sticky until cleared.  seq_bias_state: the device tables and the host copy of what the caller set; sbias: this decode's
     struct wm_seq_bias_state* seq_bias_state = nullptr;
     SeqBiasDev sbias{};
+    // wm_set_constraint: sticky until cleared.  cons_state: the device tables and the host copy of what the caller set; cons: this decode's
+    struct wm_constraint_state* cons_state = nullptr;
+    ConstraintDev cons{};
     // wm_set_stream_prompts: sticky until cleared.  The rows [sp_B][sp_P] of the clips' prompts (empty: off, every stream starts from wm_gen_params.prompt);
     // wm_decode_begin_ts checks them against its decode and seeds ctx->ids / ctx->ts.st from them.  Nothing on the device: no launch carries them
     std::vector<int32_t> sp_rows; int sp_B = 0, sp_P = 0;
@@ -401,6 +416,14 @@ int wm_seq_bias_begin(wm_ctx* ctx, const char* who, const wm_gen_params* gp, Seq
 // k_seq_bias over `nrows` rows of ctx->logits: row r under the prefix ids + r * ids_stride of lens[r] ids (DEV; clamped to [0, len_cap])
 int wm_seq_bias_launch(wm_ctx* ctx, const SeqBiasDev& sb, const int* ids, int ids_stride, const int* lens, int len_cap, int nrows);
 void wm_seq_bias_free(wm_ctx* ctx);
+// implemented in wm_constraint.hip (constrained decoding on the plain decode path; include/wm.h wm_set_constraint)
+// the device form of the context's sticky table for a decode that begins: on = 0 when none is set.  Checks what only the decode knows (the path, the
+// candidate tree, the timestamp rules, the exponential decay, eos and the suppress lists against the sequences; errors under `who`).
+int wm_constraint_begin(wm_ctx* ctx, const char* who, const wm_gen_params* gp, const wm_timestamp_params* tsp, ConstraintDev* out);
+// k_constraint over `nrows` rows of ctx->logits: row r under the prefix ids + r * ids_stride of lens[r] ids (DEV; clamped to [0, len_cap]), of which
+// the first gp.P are the decoder prompt
+int wm_constraint_launch(wm_ctx* ctx, const ConstraintDev& cd, const GenDev& gp, const int* ids, int ids_stride, const int* lens, int len_cap, int nrows);
+void wm_constraint_free(wm_ctx* ctx);
 // implemented in wm_align.hip
 void wm_align_free(wm_ctx* ctx);
 // implemented in wm_score.hip

@@ -23,6 +23,7 @@ import torch
 
 from .config import MedusaConfig, GenParams, ACCEPT_TYPICAL, ACCEPT_GREEDY, language_token
 from .engine import Engine, SEQ_BIAS_MAX as _SEQ_BIAS_MAX, SEQ_BIAS_MAX_LEN as _SEQ_BIAS_MAX_LEN
+from .engine import CONSTRAINT_MAX as _CONSTRAINT_MAX, CONSTRAINT_MAX_LEN as _CONSTRAINT_MAX_LEN
 from . import engine as _engine_mod
 from . import weights as _weights
 from . import synth as _synth
@@ -248,6 +249,43 @@ def hotword_entries(hotwords, boost: float, tokenizer) -> List[Tuple[Tuple[int, 
     return list(out.items())
 
 
+# ---- constrained decoding: a closed set of token sequences (engine: csrc/wm_constraint.hip) ------------------------------------
+def allowed_sequence_entries(allowed_sequences, eos_token_id: int, vocab_size: int) -> List[Tuple[int, ...]]:
+    """``generate(allowed_sequences=)`` -> [ids, ..] in the caller's order: a non-empty list of non-empty lists of token ids, none of them eos
+    (every sequence is closed by eos implicitly).  Duplicates collapse (first place kept)."""
+    a = allowed_sequences
+    if isinstance(a, (str, bytes)) or not isinstance(a, (list, tuple)) or len(a) == 0:
+        raise ValueError(f"`allowed_sequences` has to be a non-empty list of lists of token ids, but is {a!r}")
+    if any(isinstance(q, (str, bytes)) or not isinstance(q, (list, tuple)) or len(q) == 0 or any(not _is_int(t) or t < 0 for t in q) for q in a):
+        raise ValueError(f"Each element of `allowed_sequences` has to be a non-empty list of non-negative integers, but is {a!r}")
+    bad = [int(t) for q in a for t in q if t >= vocab_size]
+    if bad:
+        raise ValueError(f"The model vocabulary size is {vocab_size}, but `allowed_sequences` holds the token ids {bad}")
+    if any(int(t) == int(eos_token_id) for q in a for t in q):
+        raise ValueError(f"`allowed_sequences`: eos_token_id ({int(eos_token_id)}) must not stand inside a sequence: every sequence is closed "
+                         "by eos implicitly")
+    return list(dict.fromkeys(tuple(int(t) for t in q) for q in a))
+
+
+def allowed_phrase_entries(phrases, tokenizer) -> List[Tuple[int, ...]]:
+    """``generate(allowed_phrases=)`` as a pure function: every phrase is encoded as ``p`` and as ``" " + p`` (no special tokens), like
+    ``hotword_entries``; each encoding is one allowed sequence.  Duplicates collapse (first place kept); a phrase that encodes to nothing is
+    refused.  ``tokenizer``: anything with ``encode(text, add_special_tokens=False) -> ids``."""
+    if isinstance(phrases, str) or not isinstance(phrases, (list, tuple)) or len(phrases) == 0 or any(not isinstance(p, str) or not p for p in phrases):
+        raise ValueError(f"`allowed_phrases` has to be a non-empty list of non-empty strings, but is {phrases!r}")
+    if tokenizer is None or not hasattr(tokenizer, "encode"):
+        raise ValueError("`allowed_phrases` needs a tokenizer (tokenizer=, or a model built with its processor): something with "
+                         "encode(text, add_special_tokens=False)")
+    out: Dict[Tuple[int, ...], None] = {}
+    for p in phrases:
+        for text in (p, " " + p):
+            ids = tuple(int(t) for t in tokenizer.encode(text, add_special_tokens=False))
+            if not ids:
+                raise ValueError(f"`allowed_phrases`: {text!r} encodes to no token")
+            out.setdefault(ids)
+    return list(out)
+
+
 def _resolve_checkpoint(name_or_path, revision=None, cache_dir=None, local_files_only=False) -> str:
     """A checkpoint directory as it is; anything else is taken as a hub repo id and resolved with huggingface_hub.snapshot_download
     (cached snapshot first; config, weights and tokenizer files only)."""
@@ -315,6 +353,7 @@ class ResolvedCall:
     the features that ride on the short-form decode (None: not asked for) and the resolved scalars."""
     samp: Optional[dict] = None              # seeded sampling / temperature fallback (_sampling_request)
     bias: Optional[list] = None              # sequence bias entries (_bias_request)
+    cons: Optional[list] = None              # allowed sequences (_constraint_request)
     beam: Optional[dict] = None              # beam search (_beam_request)
     sc_req: Optional[dict] = None            # scoring pass: token log-probabilities, thresholds, alternatives
     tt_req: Optional[dict] = None            # token timestamps (_token_ts_request)
@@ -886,6 +925,77 @@ class WhisperMedusaModel:
             raise ValueError(f"{names}: a bias has to be finite or -inf")
         return entries
 
+    # ---- constrained decoding on the plain decode path (engine: csrc/wm_constraint.hip) -----------------------------------------------
+    def _constraint_request(self, kwargs, samp, temperature, logits_processor, stopping_criteria, return_timestamps, side: dict):
+        """The constraint side of a generate() call: None unless ``allowed_sequences=`` or ``allowed_phrases=`` is given; else the sequences —
+        both merged in that order, duplicates collapsed — after their validation and after refusing, each by the argument's name, what the
+        constraint does not run with.  ``side``: name -> value of the requests that replay the final ids."""
+        given = [n for n in ("allowed_sequences", "allowed_phrases") if kwargs.get(n) is not None]
+        if not given:
+            return None
+        names = " / ".join(given)
+        cfg = self.config
+        merged: Dict[Tuple[int, ...], None] = {}
+        if kwargs.get("allowed_sequences") is not None:
+            merged.update(dict.fromkeys(allowed_sequence_entries(kwargs["allowed_sequences"], cfg.eos_token_id, cfg.vocab_size)))
+        if kwargs.get("allowed_phrases") is not None:
+            tok = kwargs.get("tokenizer")
+            if tok is None:
+                proc = getattr(self, "processor", None)
+                tok = getattr(proc, "tokenizer", None) or getattr(self, "tokenizer", None)
+            phr = [list(q) for q in allowed_phrase_entries(kwargs["allowed_phrases"], tok)]
+            merged.update(dict.fromkeys(allowed_sequence_entries(phr, cfg.eos_token_id, cfg.vocab_size)))
+        seqs = list(merged)
+        plain = bool(kwargs.get("vanilla")) or (samp is not None and not samp["fallback"] and samp["temps"][0] > 0.0)
+        if isinstance(temperature, (tuple, list)):
+            raise NotImplementedError(f"{names} is not supported with a tuple `temperature` (the fallback schedule scores its attempts in a replay "
+                                      "that does not know the mask)")
+        if not plain:
+            raise NotImplementedError(f"{names} runs on the plain decode path only: pass vanilla=True (the Medusa loop's select, candidate and "
+                                      "accept kernels do not know the mask)")
+        if cfg.is_tree:
+            raise NotImplementedError(f"{names} is not supported with a candidate tree (medusa_choices with top-k > 1)")
+        if return_timestamps:
+            raise NotImplementedError(f"{names} is not supported with return_timestamps=True (a timestamp is never in the allowed set: the "
+                                      "timestamp rules would force a row of -inf)")
+        if _needs_host_processors(logits_processor) or \
+                (stopping_criteria and any(type(c_).__name__ not in _LOWERABLE_CRITERIA for c_ in stopping_criteria)):
+            raise NotImplementedError(f"{names} is not supported on the host processor path (logits_processor= / stopping_criteria=); pass HF's "
+                                      "PrefixConstrainedLogitsProcessor there instead")
+        if kwargs.get("streamer") is not None:
+            raise NotImplementedError(f"{names} is not supported with streamer=")
+        if kwargs.get("chunk_longform"):
+            raise NotImplementedError(f"{names} is not supported with chunk_longform (short-form only)")
+        if kwargs.get("sequential_longform"):
+            raise NotImplementedError(f"{names} is not supported with sequential_longform (short-form only)")
+        if self._micro_batches not in (None, 1):
+            raise NotImplementedError(f"{names} is not supported with the micro-batch pool (set_micro_batches)")
+        for n, v in side.items():
+            if v is not None and v is not False:
+                raise NotImplementedError(f"{names} is not supported together with {n}: it replays the final ids through kernels that do not "
+                                          "know the mask")
+        if len(seqs) > _CONSTRAINT_MAX:
+            raise ValueError(f"{names}: {len(seqs)} sequences, the engine holds at most {_CONSTRAINT_MAX} (WM_CONSTRAINT_MAX)")
+        long = [q for q in seqs if len(q) > _CONSTRAINT_MAX_LEN]
+        if long:
+            raise ValueError(f"{names}: a sequence of {len(long[0])} tokens, the engine holds at most {_CONSTRAINT_MAX_LEN} per sequence "
+                             "(WM_CONSTRAINT_MAX_LEN)")
+        return seqs
+
+    @staticmethod
+    def _check_constraint_params(gp: GenParams) -> None:
+        """What the constraint cannot run with once the decode's parameters are known (the engine refuses the same at wm_decode_begin)."""
+        if gp.exp_decay is not None:
+            raise ValueError("allowed_sequences / allowed_phrases cannot run with the exponential decay length penalty "
+                             "(exponential_decay_length_penalty): on a masked eos HF's x + |x| p is NaN")
+        used = {t for q in gp.allowed_sequences for t in q}
+        sup = sorted(used & set(gp.suppress_tokens or []))
+        if sup:
+            raise ValueError(f"allowed_sequences / allowed_phrases: the token ids {sup} of the allowed sequences are in suppress_tokens")
+        first = sorted({q[0] for q in gp.allowed_sequences} & set(gp.begin_suppress_tokens or []))
+        if first:
+            raise ValueError(f"allowed_sequences / allowed_phrases: the token ids {first} start an allowed sequence and are in begin_suppress_tokens")
+
     def _beam_decode(self, eng, feats, gp: GenParams, encoded: bool):
         """Beam search over the clips ``feats`` in groups of max_batch // num_beams, each group encoded and decoded in turn (B clips need
         B * num_beams streams).  Returns (every clip's best finished hypothesis, all of them — [(ids, score)] * num_beams per clip, best first —,
@@ -1099,7 +1209,15 @@ class WhisperMedusaModel:
         beam = self._beam_request(kwargs, temperature, logits_processor, stopping_criteria,
                                   side=sc_req is not None or bool(return_token_timestamps))
         if prefix_allowed_tokens_fn:
-            raise NotImplementedError("prefix_allowed_tokens_fn is not supported by the HIP engine")
+            raise NotImplementedError("prefix_allowed_tokens_fn is not supported by the HIP engine (a Python callback cannot run in its decode "
+                                      "loop); for a fixed list of token sequences pass allowed_sequences= / allowed_phrases= with vanilla=True")
+        # HF PrefixConstrainedLogitsProcessor over a fixed list of sequences: one in-place mask of the logits row on the engine's plain decode
+        # path, right behind the sequence bias
+        cons = self._constraint_request(kwargs, samp, temperature, logits_processor, stopping_criteria, return_timestamps,
+                                        dict(return_token_logprobs=return_token_logprobs, top_logprobs=top_logprobs,
+                                             no_speech_threshold=no_speech_threshold, logprob_threshold=logprob_threshold,
+                                             compression_ratio_threshold=compression_ratio_threshold,
+                                             return_token_timestamps=return_token_timestamps))
         tt_req = None
         if return_token_timestamps:
             # HF WhisperGenerationMixin.generate -> _extract_token_timestamps (the reference raises); the engine replays the final ids and
@@ -1116,7 +1234,7 @@ class WhisperMedusaModel:
             language = self._language_list(language, input_features.shape[0])
             if not self.config.is_multilingual:
                 language = None                         # ignored, as a scalar is (the prompt has no language slot)
-        call = ResolvedCall(samp=samp, bias=bias, beam=beam, sc_req=sc_req, tt_req=tt_req, rep_pen=rep_pen, rep_g=rep_g,
+        call = ResolvedCall(samp=samp, bias=bias, cons=cons, beam=beam, sc_req=sc_req, tt_req=tt_req, rep_pen=rep_pen, rep_g=rep_g,
                             return_timestamps=bool(return_timestamps), time_precision=time_precision, task=task, prompt_ids=prompt_ids,
                             temperature=temperature, logits_processor=logits_processor, stopping_criteria=stopping_criteria,
                             return_dict_in_generate=return_dict_in_generate, return_segments=return_segments, opts=kwargs)
@@ -1195,6 +1313,9 @@ class WhisperMedusaModel:
             gp.sequence_bias = bias
         if call.logits_processor or call.stopping_criteria:
             gp = lower_processors(gp, call.logits_processor, call.stopping_criteria)
+        if call.cons is not None:
+            gp.allowed_sequences = call.cons
+            self._check_constraint_params(gp)
         host_crit = gp._host_criteria
         on_host = bool(host_crit or gp._host_processors)
         if lang_list and on_host:
@@ -1213,8 +1334,8 @@ class WhisperMedusaModel:
                 raise NotImplementedError("sampling (sampling_seed) is not supported on the host processor path (logits_processor= / "
                                           "stopping_criteria= that the engine cannot lower)")
             n_ctx = 1           # the model's own engine: the micro-batch pool is not taught sampling
-        if beam is not None or bias is not None:
-            n_ctx = 1           # ... nor beams (the beams of a clip share one context), nor the sequence bias
+        if beam is not None or bias is not None or call.cons is not None:
+            n_ctx = 1           # ... nor beams (the beams of a clip share one context), nor the sequence bias, nor the constraint
         if n_ctx > 1 and B >= 2:
             pool = self._get_pool(n_ctx)
             extra = {}

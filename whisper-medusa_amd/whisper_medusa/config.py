@@ -366,6 +366,10 @@ class GenParams:
     # in-place edit of the logits row; [(ids, bias), ..] in the caller's order, a bias finite or -inf.  None / empty = off; needs vanilla=True
     sequence_bias: Optional[List[Tuple[Tuple[int, ...], float]]] = None
 
+    # Constrained decoding on the plain decode path (wm_set_constraint): the closed set of token sequences the transcript is held to
+    # (HF PrefixConstrainedLogitsProcessor over a fixed list), each closed by eos implicitly.  None / empty = off; needs vanilla=True
+    allowed_sequences: Optional[List[Tuple[int, ...]]] = None
+
     # Per-stream prompts of one common length (wm_set_stream_prompts): row b is clip b's decoder prompt (generate(language=[...]):
     # the rows differ in the language token).  `prompt` stays a valid representative — row 0 — for every scalar derived from it.  None = off
     prompts: Optional[List[List[int]]] = None

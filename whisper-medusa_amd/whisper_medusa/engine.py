@@ -92,6 +92,13 @@ def seq_bias_groups(entries):
     return groups
 
 
+class WmConstraintParams(C.Structure):
+    _fields_ = [("tokens", C.POINTER(C.c_int32)), ("lens", C.POINTER(C.c_int32)), ("n", C.c_int32)]
+
+
+CONSTRAINT_MAX, CONSTRAINT_MAX_LEN = 16384, 32             # WM_CONSTRAINT_MAX / WM_CONSTRAINT_MAX_LEN (include/wm.h)
+
+
 class WmAlignParams(C.Structure):
     _fields_ = [("heads", C.POINTER(C.c_int32)), ("n_heads", C.c_int32), ("median_filter_width", C.c_int32), ("time_precision", C.c_float)]
 
@@ -115,7 +122,7 @@ EXPORTS = ["wm_create", "wm_destroy", "wm_last_error", "wm_abi_version", "wm_bui
            "wm_score_tokens", "wm_score_rows", "wm_set_repeat_rules", "wm_score_tokens_topk", "wm_topk_rows",
            "wm_logmel_long", "wm_gather_windows", "wm_set_sampling", "wm_sample_rows", "wm_set_sampling_filter", "wm_filter_rows",
            "wm_set_beam", "wm_get_beam_result", "wm_beam_rows", "wm_beam_reorder_kv",
-           "wm_set_sequence_bias", "wm_seq_bias_rows",
+           "wm_set_sequence_bias", "wm_seq_bias_rows", "wm_set_constraint", "wm_constraint_rows",
            "wm_set_stream_prompts", "wm_detect_language", "wm_lang_pick_rows"]
 
 LANG_MAX = 256                                             # WM_LANG_MAX (include/wm.h)
@@ -178,6 +185,8 @@ def load_library(path: Optional[str] = None, act_fp16: bool = False) -> C.CDLL:
     lib.wm_beam_reorder_kv.argtypes = [vp, i32, i32p, i32]
     lib.wm_set_sequence_bias.argtypes = [vp, C.POINTER(WmSeqBiasParams)]
     lib.wm_seq_bias_rows.argtypes = [vp, C.POINTER(WmSeqBiasParams), i32, f32p, i32p, i32, i32p, f32p]
+    lib.wm_set_constraint.argtypes = [vp, C.POINTER(WmConstraintParams)]
+    lib.wm_constraint_rows.argtypes = [vp, C.POINTER(WmConstraintParams), i32, i32, i32, f32p, i32p, i32, i32p, f32p, i32p]
     lib.wm_set_stream_prompts.argtypes = [vp, i32p, i32, i32]
     lib.wm_detect_language.argtypes = [vp, i32, i32p, i32, i32, i32p, f32p]
     lib.wm_lang_pick_rows.argtypes = [vp, i32, f32p, i32p, i32, i32p]
@@ -482,6 +491,44 @@ class Engine:
         """The context's sequence bias follows ``gp`` before every decode (wm_set_sequence_bias is sticky), like the repetition rules."""
         self.set_sequence_bias(getattr(gp, "sequence_bias", None) or None)
 
+    @staticmethod
+    def _constraint_struct(seqs):
+        """[ids, ..] -> (wm_constraint_params, the arrays it points into).  The checks are the library's (wm_set_constraint)."""
+        seqs = [tuple(int(t) for t in ids) for ids in seqs]
+        tok = np.ascontiguousarray([t for ids in seqs for t in ids] or [0], dtype=np.int32)
+        lens = np.ascontiguousarray([len(ids) for ids in seqs] or [0], dtype=np.int32)
+        i32p = C.POINTER(C.c_int32)
+        return WmConstraintParams(tok.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), len(seqs)), (tok, lens)
+
+    def set_constraint(self, seqs) -> None:
+        """wm_set_constraint: the closed set of token sequences the following plain decodes (``gp.vanilla``) are held to — HF's
+        PrefixConstrainedLogitsProcessor over a fixed list —, sticky until cleared (``seqs`` None).  Every sequence is closed by eos implicitly."""
+        if seqs is None:
+            self._check(self.lib.wm_set_constraint(self.h, None), "wm_set_constraint")
+            self._constraint_set = False
+            return
+        c, _keep = self._constraint_struct(seqs)
+        self._constraint_set = True             # (a refused table leaves the earlier one in place: the next decode without one clears it)
+        self._check(self.lib.wm_set_constraint(self.h, C.byref(c)), "wm_set_constraint")
+
+    def _set_constraint(self, gp: GenParams) -> None:
+        """The context's constraint follows ``gp`` before every decode (wm_set_constraint is sticky), like the sequence bias.  A context that never
+        had a table makes no call (like the sampling filter)."""
+        seqs = getattr(gp, "allowed_sequences", None) or None
+        if seqs is not None or getattr(self, "_constraint_set", False):
+            self.set_constraint(seqs)
+
+    def constraint_rows(self, seqs, eos: int, prompt_len: int, logits: np.ndarray, prefixes: Sequence[Sequence[int]]):
+        """Constraint parity tap (wm_constraint_rows): rows ``logits [R, V]``, row r under ``prefixes[r]`` (its first ``prompt_len`` ids the decoder
+        prompt), through k_constraint alone.  Returns (the masked rows, numpy float32 [R, V]; the number of allowed ids of every row, int32 [R])."""
+        x, R, pre, lens, Tmax = self._tap_rows("constraint_rows", logits, prefixes)
+        out, n_allowed = np.zeros_like(x), np.zeros(R, dtype=np.int32)
+        c, _keep = self._constraint_struct(seqs)
+        self._kv_stamp = object()
+        self._check(self.lib.wm_constraint_rows(self.h, C.byref(c), int(eos), int(prompt_len), R, _fp(x), _ip(pre), Tmax, _ip(lens), _fp(out), _ip(n_allowed)),
+                    "wm_constraint_rows")
+        return out, n_allowed
+
     def set_stream_prompts(self, prompts: Optional[Sequence[Sequence[int]]]) -> None:
         """wm_set_stream_prompts: one decoder prompt per clip for the following decodes, all of one length, sticky until cleared
         (``prompts`` None).  The shape is checked against the decode by wm_decode_begin*."""
@@ -586,6 +633,7 @@ class Engine:
         self._set_sampling(gp, B)
         self._set_beam(gp)
         self._set_sequence_bias(gp)
+        self._set_constraint(gp)
         self._set_stream_prompts(gp)
         self._kv_stamp = object()             # the decode loop rewrites the self-attention cache: forward()'s cache handles go stale
         if gp.timestamps:                     # WhisperTimeStampLogitsProcessor in the loop (include/wm.h wm_decode_begin_ts)
