@@ -476,6 +476,35 @@ int wm_score_tokens_topk(wm_ctx* ctx, const wm_gen_params* gp, const wm_timestam
 int wm_detect_language(wm_ctx* ctx, int B, const int32_t* lang_ids /* HOST [n] */, int n, int32_t start_token, int32_t* out /* HOST [B] */,
                        float* ms /* may be NULL */);
 
+/* ---- stitching overlapping long-form windows (additive to ABI v9; csrc/wm_merge.hip) ----
+ * Stands in for the merge of the Hugging Face ASR pipeline over strided chunks (pipelines/automatic_speech_recognition.py chunk_iter cuts them):
+ * transformers' _find_longest_common_sequence (models/whisper/tokenization_whisper.py), a Python loop over up to len(left) + len(right) shifts per
+ * boundary — one numpy compare per shift, a Python generator per shift with token timestamps.  Here: one kernel, one launch for all boundaries of
+ * all recordings of a call.
+ * Clip c owns the windows first[c] .. first[c + 1], in time order; W = first[C].  Window w holds the TEXT ids tokens[w][0 .. lens[w]) (prompt, EOS
+ * and padding already removed) and contributes tokens[w][keep[w][0] .. keep[w][1]) to its clip: the clip's text is those slices in order.
+ * Per clip, over its non-empty windows (lens[w] == 0: keep = (0, 0), and the window is no link of the chain — the left sequence carries over, as
+ * the pipeline's `if current_tokens:` has it): a = 0 for the first; left = that window from a on, L ids, right = the next window, R ids.  For
+ * every shift i in 1 .. L + R - 1: left_start = max(0, L - i), left_stop = min(L, L + R - i), right_start = max(0, i - L), right_stop = min(R, i);
+ * matches = the positions with equal ids — with times != NULL also time_left <= time_right, compared as the float32 values given —; score = the
+ * double (double)matches / i + (double)i / 10000.0 (two IEEE divisions, one addition: HF's Python floats).  A shift counts with matches > 1; the
+ * best score wins, among equal scores the smallest i; none counting: (L, L, 0, 0), a plain concatenation.  left_mid = (left_start + left_stop) / 2,
+ * right_mid = (right_start + right_stop) / 2: keep[w] = (a, a + left_mid), the next window starts at a = right_mid; the last non-empty window keeps
+ * (a, lens[w]).  A clip of one window keeps all of it; a clip may own no window.
+ * k_merge_windows: one block of 256 threads per clip walks the clip's chain with both sequences in LDS; the shifts of a boundary are spread over
+ * the threads, the best (score, i) is reduced by wave64 shuffles and one LDS round (no atomics; integer counts, so no order dependence).
+ * One upload, one launch, one download of 2 W ints on the context's stream, in a workspace of its own (allocated on first use, freed by
+ * wm_destroy).  Reads and writes nothing of the decode state: no wm_encode needed, the captured graphs and a decode in progress are untouched.
+ * *ms (may be NULL): hipEvent time of upload + kernel + download.
+ * WM_ERR_ARG (wm_last_error names the cause): a null pointer, C < 1, first not ascending from 0, W > WM_MERGE_WINDOWS_MAX, lens[w] outside
+ * [0, min(Tmax, WM_MERGE_LEN_MAX)]. */
+#define WM_MERGE_LEN_MAX      512     /* tokens per window */
+#define WM_MERGE_WINDOWS_MAX 4096     /* windows per call, all clips together */
+int wm_merge_windows(wm_ctx* ctx, int C, const int32_t* first /* HOST [C+1] */,
+                     const int32_t* tokens /* HOST [W][Tmax] */, int Tmax, const int32_t* lens /* HOST [W] */,
+                     const float* times /* HOST [W][Tmax] or NULL */,
+                     int32_t* keep /* HOST [W][2] */, float* ms /* may be NULL */);
+
 /* ---- parity taps (test-only views of intermediate state; no reference equivalent except
  * forward(), model.py:1223-1347) ---- */
 /* encoder output [B][n_ctx][d_model] as float32 to HOST */

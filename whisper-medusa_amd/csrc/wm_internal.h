@@ -342,6 +342,8 @@ struct wm_ctx {
     std::vector<int32_t> sp_rows; int sp_B = 0, sp_P = 0;
     // language detection (wm_lang.hip): the candidate ids [WM_LANG_MAX] and the picks [max(maxB, 16)] of k_lang_pick, allocated in wm_create
     int *lang_ids = nullptr, *lang_out = nullptr;
+    // wm_merge_windows (wm_merge.hip): its workspace and event pair, allocated on first use; nothing of the decode state
+    struct wm_merge_state* merge_state = nullptr;
     int Bdec = 0;
     bool began = false, first_done = false;
     long long iters = 0;
@@ -424,6 +426,8 @@ int wm_constraint_begin(wm_ctx* ctx, const char* who, const wm_gen_params* gp, c
 // the first gp.P are the decoder prompt
 int wm_constraint_launch(wm_ctx* ctx, const ConstraintDev& cd, const GenDev& gp, const int* ids, int ids_stride, const int* lens, int len_cap, int nrows);
 void wm_constraint_free(wm_ctx* ctx);
+// implemented in wm_merge.hip (stitching overlapping long-form windows; include/wm.h wm_merge_windows)
+void wm_merge_free(wm_ctx* ctx);
 // implemented in wm_align.hip
 void wm_align_free(wm_ctx* ctx);
 // implemented in wm_score.hip

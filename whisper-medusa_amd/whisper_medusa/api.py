@@ -1094,6 +1094,10 @@ class WhisperMedusaModel:
         ``sequential_longform=True`` with ``return_timestamps=True``: ``input_features [B, n_mels, T]`` of any length — per-clip
         lengths from ``attention_mask [B, T]`` or ``num_frames=`` — are transcribed by Whisper's sequential long-form loop.
 
+        ``chunk_longform=True, stride_length_s=s | (left, right)`` (the HF ASR pipeline's keyword): the windows of a long clip
+        overlap by the strides and their token lists are stitched on the device by HF's ``_find_longest_common_sequence``; ``window_keep
+        [B, n, 2]`` in the dict forms says which slice of every window's text was kept.  ``None``: the windows are cut at multiples of 30 s.
+
         ``language=[...]`` (HF ``language: str | list[str]``): one language per clip, decoded as ONE batch — one encoder pass, one
         decode, row b carrying clip b's language token.  ``language=None, group_by_language=False``: the languages are detected on the device
         (``Engine.detect_language``) and the batch is decoded from the same encoder pass, whatever the mix; the default ``True`` detects on the
@@ -1139,6 +1143,16 @@ class WhisperMedusaModel:
                 warnings.warn("generate(generation_config=...): the Medusa path does not honour " + ", ".join(ignored) +
                               " from a passed config (see INTEGRATION.md, 'generation_config fields'); pass processors / criteria explicitly",
                               UserWarning, stacklevel=2)
+        # stride_length_s: overlapping windows for chunk_longform, merged on the device; checked before every route's own refusals
+        stride = None
+        if kwargs.get("stride_length_s") is not None:
+            if not kwargs.get("chunk_longform") or kwargs.get("sequential_longform"):
+                raise ValueError("stride_length_s is only valid together with chunk_longform=True (overlapping windows of the chunked long-form "
+                                 "route; sequential_longform seeks by timestamps and has no strides)")
+            stride = self._stride_frames(kwargs["stride_length_s"])
+            if return_timestamps:
+                raise NotImplementedError("return_timestamps=True is not supported with stride_length_s: resolving strides by timestamp tokens is "
+                                          "another algorithm than the token merge (use return_token_timestamps, or chunk_longform without strides)")
         # Seeded sampling / temperature fallback: opt-in through `sampling_seed=` — the random stream is the engine's own
         # counter-based one, not torch's generator; without it every refusal below stands as it always has
         samp = self._sampling_request(temperature, kwargs, logits_processor)
@@ -1230,8 +1244,10 @@ class WhisperMedusaModel:
             raise ValueError("input_features must be [B, n_mels, frames]")
         # language=[...]: one language per clip (HF `language: str | list[str]`, _retrieve_init_tokens).  The entries become language
         # token strings; the long-form loops below take them as one language per recording, the short-form path as per-stream prompts of one length
+        # (generate_from_wav with stride_length_s hands in the windows of all recordings, cut in the sample domain, and how many each one owns)
+        counts = kwargs.get("_window_counts") if stride is not None else None
         if isinstance(language, (list, tuple)):
-            language = self._language_list(language, input_features.shape[0])
+            language = self._language_list(language, input_features.shape[0] if counts is None else len(counts))
             if not self.config.is_multilingual:
                 language = None                         # ignored, as a scalar is (the prompt has no language slot)
         call = ResolvedCall(samp=samp, bias=bias, cons=cons, beam=beam, sc_req=sc_req, tt_req=tt_req, rep_pen=rep_pen, rep_g=rep_g,
@@ -1242,9 +1258,14 @@ class WhisperMedusaModel:
         detect = bool(language is None and self.config.is_multilingual and kwargs.get("detect_language", True))
         if kwargs.get("sequential_longform"):
             return self._generate_sequential(input_features, attention_mask, call, language, detect, time_precision_features)
+        if counts is not None:
+            return self._generate_strided(input_features, [int(c) for c in counts], stride, call, language, detect)
         if input_features.shape[-1] > self.config.n_mel_frames:
             if not kwargs.get("chunk_longform"):
                 raise NotImplementedError("Longform generation is not supported yet")              # model.py:1213-1214
+            if stride is not None:
+                win, counts = self._strided_feature_windows(input_features, stride)
+                return self._generate_strided(win, counts, stride, call, language, detect)
             return self._generate_longform(input_features, call, language, detect)
         if detect and input_features.shape[0] >= 1 and kwargs.get("group_by_language", True) is False:
             # group_by_language=False: encode, detect on the device, then decode from the encoder pass that is resident — one
@@ -1906,6 +1927,196 @@ class WhisperMedusaModel:
             return dict({"sequences": t, "segments": segs}, **(fields or {}))
         return t
 
+    # ---- chunk long-form with overlapping windows: HF's strided chunks, merged on the device --------------------------
+    def _stride_frames(self, stride_length_s) -> Tuple[int, int]:
+        """``stride_length_s`` (HF pipeline: a float for both sides, or a pair (left, right)) as whole 10 ms frames."""
+        F = self.config.n_mel_frames
+        sides = tuple(stride_length_s) if isinstance(stride_length_s, (list, tuple)) else (stride_length_s, stride_length_s)
+        if len(sides) != 2 or any(isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)) for s in sides):
+            raise ValueError(f"`stride_length_s` has to be a float or a pair (left, right) of floats, but is {stride_length_s!r}")
+        frames = []
+        for s in sides:
+            f = float(s) * 100.0
+            if not np.isfinite(f) or f < 0 or abs(f - round(f)) > 1e-6:
+                raise ValueError(f"`stride_length_s`: each side has to be a whole number of 10 ms frames (>= 0), but is {s!r}")
+            frames.append(int(round(f)))
+        if frames[0] + frames[1] <= 0:
+            raise ValueError("`stride_length_s`: left + right has to be positive (without an overlap call chunk_longform=True alone)")
+        if frames[0] + frames[1] >= F:
+            raise ValueError(f"`stride_length_s`: left + right = {frames[0] + frames[1]} frames has to be less than the window of {F} frames")
+        return frames[0], frames[1]
+
+    @staticmethod
+    def _window_plan(T: int, F: int, left: int, right: int) -> List[int]:
+        """The start frame of every window over T frames (HF ``chunk_iter``): window j starts at j * (F - left - right), the last one is the
+        first that reaches T."""
+        step = F - left - right
+        starts = [0]
+        while starts[-1] + F < T:
+            starts.append(starts[-1] + step)
+        return starts
+
+    def _strided_feature_windows(self, input_features, stride: Tuple[int, int]):
+        """``input_features [B, n_mels, T > F]`` cut at the plan's seeks; frames behind T hold the clip's own minimum (the padding rule of
+        _generate_longform).  All clips share T, so all own the same number of windows."""
+        F = self.config.n_mel_frames
+        B, M, T = input_features.shape
+        starts = self._window_plan(T, F, *stride)
+        x = input_features.to(self.device, torch.float32)
+        xp = x.amin(dim=(1, 2), keepdim=True).expand(B, M, starts[-1] + F).clone()
+        xp[..., :T] = x
+        win = torch.stack([xp[..., s: s + F] for s in starts], dim=1).reshape(B * len(starts), M, F).contiguous()
+        return win, [len(starts)] * B
+
+    def _strided_wav_windows(self, wav, sampling_rate: int, stride: Tuple[int, int]):
+        """Every recording cut in the sample domain under its own length (ragged window counts); each window zero-padded to the model's window and
+        transformed on its own by wm_logmel, in groups of at most max_batch: HF's per-chunk features, the per-chunk ``max - 8`` clamp included."""
+        F = self.config.n_mel_frames
+        step = (F - stride[0] - stride[1]) * 160
+        if isinstance(wav, (list, tuple)):
+            clips = [np.asarray(w, dtype=np.float32) for w in wav]
+        else:
+            a = wav.detach().cpu().numpy() if isinstance(wav, torch.Tensor) else np.asarray(wav)
+            a = a.astype(np.float32)
+            clips = [a] if a.ndim == 1 else [r for r in a]
+        mono = []
+        for c in clips:
+            if c.ndim == 2 or sampling_rate != 16000:
+                t = torch.from_numpy(np.atleast_2d(c)[None]).to(self.device)
+                mono.append(self.engine.resample(t, sampling_rate, 16000)[0])
+            else:
+                mono.append(torch.from_numpy(c).to(self.device))
+        counts, cuts = [], []
+        for b, r in enumerate(mono):
+            starts = self._window_plan(-(-r.numel() // 160), F, *stride)
+            counts.append(len(starts))
+            cuts += [(b, j * step) for j in range(len(starts))]
+        feats = []
+        for g in range(0, len(cuts), self._max_batch):
+            grp = cuts[g: g + self._max_batch]
+            buf = torch.zeros(len(grp), F * 160, dtype=torch.float32, device=self.device)
+            for q, (b, s) in enumerate(grp):
+                m = min(mono[b].numel() - s, F * 160)
+                if m > 0:
+                    buf[q, :m] = mono[b][s: s + m]
+            feats.append(self.engine.logmel(buf))
+        return torch.cat(feats), counts
+
+    def _generate_strided(self, win, counts: List[int], stride: Tuple[int, int], call: "ResolvedCall", language, detect: bool):
+        """`chunk_longform=True, stride_length_s=..`: the overlapping windows ``win [sum(counts), n_mels, F]`` of all clips (clip b owns
+        ``counts[b]`` consecutive rows, window j starting at j * step frames) are decoded like _generate_longform's — language once per clip on its
+        first window, one batch per language group — stripped to their text ids and stitched by ONE ``engine.merge_windows`` call (HF's
+        _find_longest_common_sequence for every boundary of every clip).  Every per-token field follows the kept slices; a window
+        the gate skipped enters the merge as an empty window."""
+        cfg = self.config
+        rdg, sreq, req = call.return_dict_in_generate, call.sc_req, call.tt_req
+        F, B = cfg.n_mel_frames, len(counts)
+        step = F - stride[0] - stride[1]
+        if req is not None and req["num_frames"] is not None:
+            raise NotImplementedError("num_frames= is not supported together with chunk_longform=True (the windows are fixed)")
+        first = [0]
+        for c in counts:
+            first.append(first[-1] + c)
+        W, n = first[-1], max(counts)
+        if win.shape[0] != W or min(counts) < 1:
+            raise ValueError(f"strided long-form: {win.shape[0]} windows for the counts {counts}")
+        win = win.to(self.device, torch.float32)
+        if detect:
+            langs = self.detect_language(win[first[:-1]])
+        else:
+            langs = list(language) if isinstance(language, (list, tuple)) else [language] * B
+        rows, prompts = [None] * W, [None] * B
+        wtt = [None] * W
+        wsc: List[Optional[dict]] = [None] * W
+        ms_tt = ms_sc = 0.0
+        for l in sorted(set(langs), key=lambda v: (v is None, v or "")):
+            clips = [b for b in range(B) if langs[b] == l]
+            widx = [w for b in clips for w in range(first[b], first[b + 1])]
+            res = self._generate_short(win[widx], call, language=l)
+            ms_tt += res.stats.get("ms_token_timestamps", 0.0)
+            ms_sc += res.stats.get("ms_token_logprobs", 0.0)
+            for q, wi in enumerate(widx):
+                rows[wi] = self._own_end(res.seqs[q], res.gp)      # (up to its own EOS, if it emitted one)
+                if req is not None:
+                    wtt[wi] = res.token_timestamps[q].cpu()
+                if sreq is not None:
+                    wsc[wi] = {k: v[q].cpu() for k, v in res.scores.items() if not k.startswith("_")}
+            for b in clips:
+                prompts[b] = list(res.gp.prompt)
+        eos, pad = cfg.eos_token_id, cfg.pad_token_id
+        # every window's text ids (no prompt, EOS, padding) and, with token timestamps, their absolute times as float32
+        text: List[List[int]] = [[] for _ in range(W)]
+        times: List[List[float]] = [[] for _ in range(W)]
+        for b in range(B):
+            P = len(prompts[b])
+            for j in range(counts[b]):
+                wi = first[b] + j
+                if sreq is not None and "skipped" in wsc[wi] and bool(wsc[wi]["skipped"]):
+                    continue
+                gen = rows[wi][P:]
+                m = next((q for q, t in enumerate(gen) if t == eos or t == pad), len(gen))
+                text[wi] = gen[:m]
+                if req is not None:     # the window's own values, offset by the window's start (float32 sum, as the tensors hold it)
+                    times[wi] = (wtt[wi][P: P + m] + torch.tensor(j * step * 0.01, dtype=torch.float32)).tolist()
+        eng = self.engine
+        keeps = eng.merge_windows([text[first[b]: first[b + 1]] for b in range(B)],
+                                  [times[first[b]: first[b + 1]] for b in range(B)] if req is not None else None)
+        seqs, all_tt, all_lp = [], [], []
+        for b in range(B):
+            ids = list(prompts[b])
+            P = len(ids)
+            tts = [0.0] * P
+            lps, last_eos_lp = [0.0] * P, 0.0
+            for j in range(counts[b]):
+                wi = first[b] + j
+                if sreq is not None and "skipped" in wsc[wi] and bool(wsc[wi]["skipped"]):
+                    continue
+                lo, hi = keeps[b][j]
+                ids += text[wi][lo:hi]
+                if sreq is not None:
+                    lp = wsc[wi]["token_logprobs"]
+                    lps += [float(v) for v in lp[P + lo: P + hi]]
+                    if P + len(text[wi]) < len(rows[wi]):      # the clip's one EOS takes the score of the last kept window's
+                        last_eos_lp = float(lp[P + len(text[wi])])
+                if req is not None:
+                    tts += times[wi][lo:hi]
+            seqs.append(ids + [eos])
+            all_tt.append(tts + [tts[-1]])
+            all_lp.append(lps + [last_eos_lp])
+        t = _ids_tensor(seqs, pad).to(self.device)
+        window_keep = torch.full((B, n, 2), -1, dtype=torch.long)
+        for b in range(B):
+            window_keep[b, : counts[b]] = torch.tensor(keeps[b], dtype=torch.long).view(-1, 2)
+        window_keep = window_keep.to(self.device)
+        self.last_window_keep = window_keep
+
+        def per_window(k, fill):
+            # window-level fields stay [B, n]: NaN / False behind a clip's last window
+            out = torch.full((B, n), fill, dtype=wsc[0][k].dtype)
+            for b in range(B):
+                out[b, : counts[b]] = torch.stack([wsc[w][k] for w in range(first[b], first[b + 1])])
+            return out.to(self.device)
+
+        fields = None
+        if sreq is not None:
+            fields = self._clip_score_fields(all_lp, seqs, prompts)
+            for k in ("no_speech_prob", "skipped", "needs_fallback"):
+                if k in wsc[0]:
+                    fields[k] = per_window(k, False if wsc[0][k].dtype == torch.bool else float("nan"))
+            fields["window_avg_logprob"] = per_window("avg_logprob", float("nan"))
+            self.last_scores = fields
+            res.stats["ms_token_logprobs"] = ms_sc
+        if req is not None:
+            res.stats["ms_token_timestamps"] = ms_tt
+        res.stats["ms_merge"] = float(getattr(eng, "last_merge_ms", 0.0))
+        res.stats["longform_windows"] = list(counts)
+        self._publish(res, None)
+        if req is not None:
+            return GenerateEncoderDecoderOutput(t, token_timestamps=_ts_tensor(all_tt).to(self.device), window_keep=window_keep, **(fields or {}))
+        if rdg or (fields is not None and sreq["want"]):
+            return GenerateEncoderDecoderOutput(t, window_keep=window_keep, **(fields or {}))
+        return t
+
     # ---- sequential long-form: HF's seek loop around the short-form path (DESIGN.md §2f) ---------------------------------------------
     def _check_sequential(self, return_timestamps, condition_on_prev_tokens, temperature, return_token_timestamps, logits_processor,
                           stopping_criteria, streamer, prompt_ids, prompt_condition_type):
@@ -2131,6 +2342,10 @@ class WhisperMedusaModel:
             feats = self.extract_features(wav, kw.pop("sampling_rate", 16000), truncation=False)
             kw.setdefault("num_frames", self.last_num_frames)
             return self.generate(feats, **kw)
+        if kw.get("stride_length_s") is not None and kw.get("chunk_longform"):
+            # overlapping windows: cut in the sample domain, every recording under its own length, one log-mel per window
+            win, counts = self._strided_wav_windows(wav, kw.pop("sampling_rate", 16000), self._stride_frames(kw["stride_length_s"]))
+            return self.generate(win, _window_counts=counts, **kw)
         return self.generate(self.extract_features(wav), **kw)
 
     # ---- forward ----------------------------------------------------------------------------

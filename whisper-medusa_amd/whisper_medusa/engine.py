@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -123,9 +123,10 @@ EXPORTS = ["wm_create", "wm_destroy", "wm_last_error", "wm_abi_version", "wm_bui
            "wm_logmel_long", "wm_gather_windows", "wm_set_sampling", "wm_sample_rows", "wm_set_sampling_filter", "wm_filter_rows",
            "wm_set_beam", "wm_get_beam_result", "wm_beam_rows", "wm_beam_reorder_kv",
            "wm_set_sequence_bias", "wm_seq_bias_rows", "wm_set_constraint", "wm_constraint_rows",
-           "wm_set_stream_prompts", "wm_detect_language", "wm_lang_pick_rows"]
+           "wm_set_stream_prompts", "wm_detect_language", "wm_lang_pick_rows", "wm_merge_windows"]
 
 LANG_MAX = 256                                             # WM_LANG_MAX (include/wm.h)
+MERGE_LEN_MAX, MERGE_WINDOWS_MAX = 512, 4096               # WM_MERGE_LEN_MAX, WM_MERGE_WINDOWS_MAX
 
 _lib = {}
 
@@ -190,6 +191,7 @@ def load_library(path: Optional[str] = None, act_fp16: bool = False) -> C.CDLL:
     lib.wm_set_stream_prompts.argtypes = [vp, i32p, i32, i32]
     lib.wm_detect_language.argtypes = [vp, i32, i32p, i32, i32, i32p, f32p]
     lib.wm_lang_pick_rows.argtypes = [vp, i32, f32p, i32p, i32, i32p]
+    lib.wm_merge_windows.argtypes = [vp, i32, i32p, i32p, i32, i32p, f32p, i32p, f32p]
     lib.wm_decode_run.argtypes = [vp, i32, i32p]
     lib.wm_get_tokens.argtypes = [vp, i32, i32p, i32, i32p]
     lib.wm_get_stats.argtypes = [vp, C.POINTER(WmStats)]
@@ -571,6 +573,37 @@ class Engine:
         self._kv_stamp = object()
         self._check(self.lib.wm_lang_pick_rows(self.h, R, _fp(x), _ip(ids), len(ids), _ip(out)), "wm_lang_pick_rows")
         return out
+
+    def merge_windows(self, windows_per_clip, times_per_clip=None) -> List[List[Tuple[int, int]]]:
+        """wm_merge_windows: the slices that stitch the overlapping windows of every clip — transformers' ``_find_longest_common_sequence`` as one
+        kernel launch for all boundaries of all clips.  ``windows_per_clip[c][j]``: the text ids of clip c's window j (no prompt, EOS or padding; an
+        empty window is skipped by the chain); ``times_per_clip``: one absolute time per id in the same shape (float32), a match then also needs
+        the times in order.  Returns per clip ``[(a, b), ..]``: window j contributes ``ids[a:b]``.  Touches nothing of the decode state;
+        ``last_merge_ms`` holds the hipEvent time of upload + kernel + download."""
+        wins = [list(w) for clip in windows_per_clip for w in clip]
+        first = np.zeros(len(windows_per_clip) + 1, dtype=np.int32)
+        first[1:] = np.cumsum([len(clip) for clip in windows_per_clip])
+        W = len(wins)
+        Tmax = max([len(w) for w in wins] + [1])
+        tok = np.zeros((max(W, 1), Tmax), dtype=np.int32)
+        lens = np.zeros(max(W, 1), dtype=np.int32)
+        for w, ids in enumerate(wins):
+            tok[w, : len(ids)] = np.asarray(ids, dtype=np.int64)
+            lens[w] = len(ids)
+        tm = None
+        if times_per_clip is not None:
+            tms = [w for clip in times_per_clip for w in clip]
+            if [len(clip) for clip in times_per_clip] != [len(clip) for clip in windows_per_clip] or [len(w) for w in tms] != [len(w) for w in wins]:
+                raise ValueError("merge_windows: times_per_clip must have the shape of windows_per_clip")
+            tm = np.zeros((max(W, 1), Tmax), dtype=np.float32)
+            for w, t in enumerate(tms):
+                tm[w, : len(t)] = np.asarray(t, dtype=np.float32)
+        keep = np.zeros((max(W, 1), 2), dtype=np.int32)
+        ms = C.c_float(0)
+        self._check(self.lib.wm_merge_windows(self.h, len(windows_per_clip), _ip(first), _ip(tok), Tmax, _ip(lens), None if tm is None else _fp(tm),
+                                              _ip(keep), C.byref(ms)), "wm_merge_windows")
+        self.last_merge_ms = ms.value
+        return [[(int(keep[w, 0]), int(keep[w, 1])) for w in range(first[c], first[c + 1])] for c in range(len(windows_per_clip))]
 
     def seq_bias_rows(self, entries, logits: np.ndarray, prefixes: Sequence[Sequence[int]]) -> np.ndarray:
         """Sequence-bias parity tap (wm_seq_bias_rows): rows ``logits [R, V]``, row r under ``prefixes[r]``, through k_seq_bias alone.  Returns the
