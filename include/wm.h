@@ -505,6 +505,57 @@ int wm_merge_windows(wm_ctx* ctx, int C, const int32_t* first /* HOST [C+1] */,
                      const float* times /* HOST [W][Tmax] or NULL */,
                      int32_t* keep /* HOST [W][2] */, float* ms /* may be NULL */);
 
+/* ---- grouping token ids into words (additive to ABI v9; csrc/wm_words.hip, csrc/wm_words.h) ----
+ * Stands in for transformers' _combine_tokens_into_words (models/whisper/tokenization_whisper.py: _split_tokens_on_unicode, _split_tokens_on_spaces,
+ * _merge_punctuations), the grouping behind the ASR pipeline's return_timestamps="word": there one tokenizer.decode per token on a growing list and
+ * two list-rewriting passes, here one kernel launch for all rows of a call, on the bytes of the vocabulary.
+ * wm_set_word_table: the bytes of token t are bytes[offsets[t] .. offsets[t + 1]), t < n_tokens (= eos_token_id: text ids only).  Uploaded once; the
+ * context owns its device copy, a later call replaces it, wm_destroy frees it.  WM_ERR_ARG (wm_last_error names the cause): a null pointer, n_tokens
+ * outside [1, WM_WORDS_TOKENS_MAX], offsets not strictly ascending from 0 (every token has at least one byte), more than WM_WORDS_BYTES_MAX bytes.
+ * wm_word_spans: row r is the ids[first[r] .. first[r + 1]) (text ids, every one below the table's n_tokens; a row may be empty and has no cap on
+ * its length), under modes[r].  The words of a row are contiguous runs that partition it in order: n_words[r] and the ascending start indices
+ * word_first[first[r] + r + (0 .. n_words[r])], the last of them the row's length (row r owns len + 1 slots; those behind are zero).
+ *   Pieces: append the bytes of each token in turn; a piece closes behind token t when the bytes gathered since the last close are strict UTF-8
+ *   (what bytes.decode("utf-8") accepts).  Tokens left over at the end of the row are a last piece of their own.
+ *   Words, WM_WORDS_SPACES: a piece opens a new word if its first byte is 0x20, or strip(piece) is a substring of !"#$%&'()*+,-./:;<=>?@[\]^_`{|}~
+ *   (the empty string is one: a whitespace-only piece counts as punctuation), or there is no word yet; else it is appended to the last word.
+ *   strip is Python's: the code points with str.isspace() — U+0009-000D, 001C-0020, 0085, 00A0, 1680, 2000-200A, 2028, 2029, 202F, 205F, 3000 —
+ *   leave at both ends; on bytes, their UTF-8 encodings.  WM_WORDS_UNICODE (HF: chinese, japanese, thai, lao, myanmar, cantonese): every piece is
+ *   a word.
+ *   Prepend pass (HF: right to left, i = n - 2, j = n - 1): word i merges into word j when it starts with 0x20 and strip(word i) is a substring
+ *   of "'“¡¿([{- ; else j = i.  The last word is never tested.  Stated forwards: a maximal run of such words joins the word behind it.
+ *   Append pass (left to right, i = 0, j = 1): word j merges into word i when word i does not end in 0x20 and word j, unstripped, is a substring of
+ *   "'.。,，!！?？:：”)]}、 ; else i = j.  A slot the first pass emptied is the empty string and passes the test, as in HF; it changes no cut.
+ *   Substring tests are on UTF-8 bytes (equal to tests on code points for valid text).
+ * Equal to transformers for rows whose concatenated bytes are valid UTF-8 without U+FFFD; outside (a truncated character at the end of a row, a
+ * stray continuation byte: HF's replacement-character bookkeeping cuts elsewhere) the rules above are the contract.
+ * times (may be NULL): float32 (start, end) per id; word_times[first[r] + w] = (start of the word's first token, end of its last).  logprobs (may be
+ * NULL): float32 per id; word_logprobs[first[r] + w] = the float32 sum in ascending token order divided by the count in float32.  Entries behind a
+ * row's n_words are zero.
+ * k_word_spans: one block of 256 threads per row, the row in tiles of 1024 tokens: the threads gather every token's bytes from the table and
+ * summarise them into LDS (first bytes, the token as a map on the nine states of strict UTF-8), thread 0 walks the tile under carried state (the
+ * UTF-8 state, the open piece, word and prepend run with their streamed substring tests), then the threads fill times and log-probabilities, a word
+ * each.  No atomics, plain vector stores, nothing depends on an order of execution.
+ * One upload, one launch, one download on the context's stream, in a workspace and with an event pair of its own (allocated on first use, freed
+ * by wm_destroy).  Reads and writes nothing of the decode state: no wm_encode needed, no wm_decode_invalidate, the captured graphs and a decode in
+ * progress (between wm_decode_begin and wm_decode_run) are untouched.  *ms (may be NULL): hipEvent time of upload + kernel + download.
+ * WM_ERR_ARG (wm_last_error names the cause): a null pointer (times without word_times, logprobs without word_logprobs), R outside
+ * [1, WM_WORDS_ROWS_MAX], first not ascending from 0, first[R] > WM_WORDS_IDS_MAX, a mode that is neither constant, an id outside the table.
+ * WM_ERR_STATE: no table set. */
+#define WM_WORDS_SPACES  0
+#define WM_WORDS_UNICODE 1
+#define WM_WORDS_ROWS_MAX    65536          /* rows per call */
+#define WM_WORDS_IDS_MAX     (4 << 20)      /* ids per call, all rows together */
+#define WM_WORDS_TOKENS_MAX  (1 << 20)      /* vocabulary entries */
+#define WM_WORDS_BYTES_MAX   (64 << 20)     /* bytes of the vocabulary */
+int wm_set_word_table(wm_ctx* ctx, const uint8_t* bytes /* HOST [offsets[n_tokens]] */, const int32_t* offsets /* HOST [n_tokens+1] */, int n_tokens);
+int wm_word_spans(wm_ctx* ctx, int R, const int32_t* first /* HOST [R+1] */, const int32_t* ids /* HOST [first[R]] */,
+                  const int32_t* modes /* HOST [R] */, const float* times /* HOST [first[R]][2] or NULL */,
+                  const float* logprobs /* HOST [first[R]] or NULL */,
+                  int32_t* n_words /* HOST [R] */, int32_t* word_first /* HOST [first[R] + R] */,
+                  float* word_times /* HOST [first[R]][2]; may be NULL without times */,
+                  float* word_logprobs /* HOST [first[R]]; may be NULL without logprobs */, float* ms /* may be NULL */);
+
 /* ---- parity taps (test-only views of intermediate state; no reference equivalent except
  * forward(), model.py:1223-1347) ---- */
 /* encoder output [B][n_ctx][d_model] as float32 to HOST */

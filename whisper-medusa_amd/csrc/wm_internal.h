@@ -344,6 +344,8 @@ struct wm_ctx {
     int *lang_ids = nullptr, *lang_out = nullptr;
     // wm_merge_windows (wm_merge.hip): its workspace and event pair, allocated on first use; nothing of the decode state
     struct wm_merge_state* merge_state = nullptr;
+    // wm_set_word_table / wm_word_spans (wm_words.hip): the vocabulary's bytes, a workspace and an event pair of their own; nothing of the decode state
+    struct wm_words_state* words_state = nullptr;
     int Bdec = 0;
     bool began = false, first_done = false;
     long long iters = 0;
@@ -428,6 +430,8 @@ int wm_constraint_launch(wm_ctx* ctx, const ConstraintDev& cd, const GenDev& gp,
 void wm_constraint_free(wm_ctx* ctx);
 // implemented in wm_merge.hip (stitching overlapping long-form windows; include/wm.h wm_merge_windows)
 void wm_merge_free(wm_ctx* ctx);
+// implemented in wm_words.hip (grouping token ids into words; include/wm.h wm_set_word_table / wm_word_spans)
+void wm_words_free(wm_ctx* ctx);
 // implemented in wm_align.hip
 void wm_align_free(wm_ctx* ctx);
 // implemented in wm_score.hip

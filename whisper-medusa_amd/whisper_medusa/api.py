@@ -29,6 +29,7 @@ from . import weights as _weights
 from . import synth as _synth
 from . import timestamps as _timestamps
 from . import scores as _scores
+from . import words as _words
 
 
 class EngineKVCache:
@@ -1098,6 +1099,11 @@ class WhisperMedusaModel:
         overlap by the strides and their token lists are stitched on the device by HF's ``_find_longest_common_sequence``; ``window_keep
         [B, n, 2]`` in the dict forms says which slice of every window's text was kept.  ``None``: the windows are cut at multiples of 30 s.
 
+        ``return_word_timestamps=True, tokenizer=tok | word_table=WordTable`` (the HF ASR pipeline's ``return_timestamps="word"``):
+        implies ``return_token_timestamps=True`` and adds ``words`` to the dict output — per clip a list of ``{"text", "timestamp": (start, end),
+        "tokens": (first, stop)[, "probability"]}`` — grouped from the ids and the token timestamps by ONE HIP kernel launch per call, on every
+        route on which token timestamps work; with ``return_segments=True`` every segment carries its own ``words``.
+
         ``language=[...]`` (HF ``language: str | list[str]``): one language per clip, decoded as ONE batch — one encoder pass, one
         decode, row b carrying clip b's language token.  ``language=None, group_by_language=False``: the languages are detected on the device
         (``Engine.detect_language``) and the batch is decoded from the same encoder pass, whatever the mix; the default ``True`` detects on the
@@ -1143,6 +1149,22 @@ class WhisperMedusaModel:
                 warnings.warn("generate(generation_config=...): the Medusa path does not honour " + ", ".join(ignored) +
                               " from a passed config (see INTEGRATION.md, 'generation_config fields'); pass processors / criteria explicitly",
                               UserWarning, stacklevel=2)
+        # return_word_timestamps: the words of every clip with a start and an end, grouped on the device from the ids and the token
+        # timestamps of whatever route decodes the call; it implies return_token_timestamps, whose refusals all stand
+        words_req = self._words_request(kwargs, return_token_timestamps, return_token_logprobs)
+        out = self._generate_routes(input_features, generation_config, logits_processor, stopping_criteria, prefix_allowed_tokens_fn,
+                                    return_timestamps, task, language, prompt_ids, prompt_condition_type, condition_on_prev_tokens,
+                                    temperature, compression_ratio_threshold, logprob_threshold, no_speech_threshold, attention_mask,
+                                    time_precision, time_precision_features, True if words_req is not None else return_token_timestamps,
+                                    return_segments, return_dict_in_generate, return_token_logprobs, top_logprobs, kwargs)
+        return out if words_req is None else self._attach_words(out, words_req, language)
+
+    def _generate_routes(self, input_features, generation_config, logits_processor, stopping_criteria, prefix_allowed_tokens_fn,
+                         return_timestamps, task, language, prompt_ids, prompt_condition_type, condition_on_prev_tokens,
+                         temperature, compression_ratio_threshold, logprob_threshold, no_speech_threshold, attention_mask,
+                         time_precision, time_precision_features, return_token_timestamps, return_segments,
+                         return_dict_in_generate, return_token_logprobs, top_logprobs, kwargs):
+        """generate() behind its generation_config merge: the checks of every feature, the resolved call and the route that decodes it."""
         # stride_length_s (DESIGN.md §2o): overlapping windows for chunk_longform, merged on the device; checked before every route's own refusals
         stride = None
         if kwargs.get("stride_length_s") is not None:
@@ -1272,6 +1294,7 @@ class WhisperMedusaModel:
             # encode, one decode, whatever the mix of languages
             language = self._detect_language_on_device(input_features.to(self.device, torch.float32).contiguous())
             self.detected_languages = list(language)
+            self._clip_languages = list(language)
             res = self._generate_short(input_features, call, language=language, encoded=True)
         elif detect and input_features.shape[0] >= 1:
             return self._generate_detecting_language(input_features, call)
@@ -1284,6 +1307,51 @@ class WhisperMedusaModel:
             if res.sequences_scores is not None:
                 out["sequences_scores"] = res.sequences_scores
         return self._publish(res, out)
+
+    # ---- word timestamps (HF pipeline return_timestamps="word"; engine: csrc/wm_words.hip) ------------------------------------
+    def _words_request(self, kwargs, return_token_timestamps, return_token_logprobs) -> Optional[dict]:
+        """``return_word_timestamps=True[, tokenizer=, word_table=]`` of a generate() call; takes its own two keywords out of ``kwargs``."""
+        want, table = kwargs.pop("return_word_timestamps", None), kwargs.pop("word_table", None)
+        if not want:
+            return None
+        if return_token_timestamps is not None and not return_token_timestamps:
+            raise ValueError("return_word_timestamps=True is built on the token timestamps: return_token_timestamps=False contradicts it")
+        tok = kwargs.get("tokenizer")
+        if table is None and tok is None:
+            raise ValueError("return_word_timestamps=True needs the bytes of the vocabulary: pass tokenizer= (or word_table=)")
+        if table is None:
+            cache = self.__dict__.setdefault("_word_tables", {})
+            if id(tok) not in cache:
+                cache[id(tok)] = (tok, _words.WordTable.from_tokenizer(tok, self.config.eos_token_id))     # (the tokenizer stays alive with its key)
+            table = cache[id(tok)][1]
+        self._clip_languages = None
+        return dict(table=table, logprobs=bool(return_token_logprobs))
+
+    def _attach_words(self, out, req: dict, language):
+        """``out["words"]`` (and ``segments[b][k]["words"]``) of a finished call: ONE ``engine.word_spans`` call over the text rows of all clips."""
+        cfg, eng, table = self.config, self.engine, req["table"]
+        if getattr(eng, "_word_table", None) is not table:
+            eng.set_word_table(table.blob, table.offsets)
+            eng._word_table = table
+        seqs = out["sequences"].cpu().tolist()
+        langs = self._clip_languages
+        if langs is None:
+            langs = list(language) if isinstance(language, (list, tuple)) else [language] * len(seqs)
+        per = len(seqs) // max(len(langs), 1)                  # (beam search with num_return_sequences: rows per clip, clip-major)
+        modes = [_words.language_mode(langs[b // max(per, 1)] if cfg.is_multilingual else None) for b in range(len(seqs))]
+        lp = out["token_logprobs"].float().cpu().numpy() if req["logprobs"] and "token_logprobs" in out else None
+        P = len(self._last_prompt)
+        words = _words.collate(eng, table, seqs, out["token_timestamps"].float().cpu().numpy(), P, cfg.eos_token_id, modes, lp)
+        out["words"] = words
+        if "segments" in out and out["segments"] is not None:
+            for b, segs in enumerate(out["segments"]):
+                o = P
+                for sg in segs:
+                    n = int(sg["tokens"].numel())
+                    sg["words"] = [w for w in words[b] if o <= w["tokens"][0] < o + n]
+                    o += n
+        self.last_stats["ms_words"] = float(getattr(eng, "last_words_ms", 0.0))
+        return out
 
     def _publish(self, res: "ShortResult", out):
         """The attributes a public call leaves behind, from the (last) short-form result of its route; hands ``out`` through."""
@@ -1789,6 +1857,7 @@ class WhisperMedusaModel:
         plens = [p_ for p_ in plens for _ in range(nret)]
         T = t.shape[1]
         self.detected_languages = langs
+        self._clip_languages = list(langs)
         tt = None
         if req is not None:
             tt = _ts_tensor(tts, T)
@@ -1843,6 +1912,7 @@ class WhisperMedusaModel:
             langs = self.detect_language(win[::n])
         else:
             langs = list(language) if isinstance(language, (list, tuple)) else [language] * B
+        self._clip_languages = list(langs)
         rows, prompts = [None] * (B * n), [None] * B
         if req is not None and req["num_frames"] is not None:
             raise NotImplementedError("num_frames= is not supported together with chunk_longform=True (the windows are fixed)")
@@ -2025,6 +2095,7 @@ class WhisperMedusaModel:
             langs = self.detect_language(win[first[:-1]])
         else:
             langs = list(language) if isinstance(language, (list, tuple)) else [language] * B
+        self._clip_languages = list(langs)
         rows, prompts = [None] * W, [None] * B
         wtt = [None] * W
         wsc: List[Optional[dict]] = [None] * W

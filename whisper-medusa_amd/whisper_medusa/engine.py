@@ -123,10 +123,14 @@ EXPORTS = ["wm_create", "wm_destroy", "wm_last_error", "wm_abi_version", "wm_bui
            "wm_logmel_long", "wm_gather_windows", "wm_set_sampling", "wm_sample_rows", "wm_set_sampling_filter", "wm_filter_rows",
            "wm_set_beam", "wm_get_beam_result", "wm_beam_rows", "wm_beam_reorder_kv",
            "wm_set_sequence_bias", "wm_seq_bias_rows", "wm_set_constraint", "wm_constraint_rows",
-           "wm_set_stream_prompts", "wm_detect_language", "wm_lang_pick_rows", "wm_merge_windows"]
+           "wm_set_stream_prompts", "wm_detect_language", "wm_lang_pick_rows", "wm_merge_windows",
+           "wm_set_word_table", "wm_word_spans"]
 
 LANG_MAX = 256                                             # WM_LANG_MAX (include/wm.h)
 MERGE_LEN_MAX, MERGE_WINDOWS_MAX = 512, 4096               # WM_MERGE_LEN_MAX, WM_MERGE_WINDOWS_MAX
+WORDS_SPACES, WORDS_UNICODE = 0, 1                         # WM_WORDS_SPACES, WM_WORDS_UNICODE
+WORDS_ROWS_MAX, WORDS_IDS_MAX = 65536, 4 << 20             # WM_WORDS_ROWS_MAX, WM_WORDS_IDS_MAX
+WORDS_TILE = 1024                                          # WW_TILE (csrc/wm_words.h): tokens of a row staged per round of k_word_spans
 
 _lib = {}
 
@@ -192,6 +196,8 @@ def load_library(path: Optional[str] = None, act_fp16: bool = False) -> C.CDLL:
     lib.wm_detect_language.argtypes = [vp, i32, i32p, i32, i32, i32p, f32p]
     lib.wm_lang_pick_rows.argtypes = [vp, i32, f32p, i32p, i32, i32p]
     lib.wm_merge_windows.argtypes = [vp, i32, i32p, i32p, i32, i32p, f32p, i32p, f32p]
+    lib.wm_set_word_table.argtypes = [vp, C.POINTER(C.c_uint8), i32p, i32]
+    lib.wm_word_spans.argtypes = [vp, i32, i32p, i32p, i32p, f32p, f32p, i32p, i32p, f32p, f32p, f32p]
     lib.wm_decode_run.argtypes = [vp, i32, i32p]
     lib.wm_get_tokens.argtypes = [vp, i32, i32p, i32, i32p]
     lib.wm_get_stats.argtypes = [vp, C.POINTER(WmStats)]
@@ -604,6 +610,61 @@ class Engine:
                                               _ip(keep), C.byref(ms)), "wm_merge_windows")
         self.last_merge_ms = ms.value
         return [[(int(keep[w, 0]), int(keep[w, 1])) for w in range(first[c], first[c + 1])] for c in range(len(windows_per_clip))]
+
+    def set_word_table(self, blob: np.ndarray, offsets: np.ndarray) -> None:
+        """wm_set_word_table: the bytes of every text id (``blob`` uint8, ``offsets`` int32 [n_tokens + 1]; whisper_medusa/words.py WordTable builds
+        them).  Uploaded once; a later call replaces the table."""
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        self._check(self.lib.wm_set_word_table(self.h, blob.ctypes.data_as(C.POINTER(C.c_uint8)), _ip(offsets), len(offsets) - 1), "wm_set_word_table")
+
+    def word_spans(self, rows, modes, times=None, logprobs=None):
+        """wm_word_spans: the words of every row of text ids — transformers' ``_combine_tokens_into_words`` as one kernel launch for all rows of the
+        call.  ``rows[r]``: text ids (below the table's n_tokens; may be empty, any length); ``modes[r]``: WORDS_SPACES or WORDS_UNICODE;
+        ``times[r]``: float32 [len, 2] (start, end) per id; ``logprobs[r]``: float32 [len].  Returns per row ``(word_first, word_times, word_logprobs)``:
+        int32 [n_words + 1] ascending starts ending in the row's length, float32 [n_words, 2] or None, float32 [n_words] or None.  Touches nothing
+        of the decode state; ``last_words_ms`` holds the hipEvent time of upload + kernel + download."""
+        R = len(rows)
+        if len(modes) != R or (times is not None and len(times) != R) or (logprobs is not None and len(logprobs) != R):
+            raise ValueError("word_spans: modes, times and logprobs must have one entry per row")
+        if R == 0:
+            self.last_words_ms = 0.0
+            return []
+        first = np.zeros(R + 1, dtype=np.int32)
+        first[1:] = np.cumsum([len(r) for r in rows])
+        N = int(first[R])
+        ids = np.zeros(max(N, 1), dtype=np.int32)
+        if N:
+            ids[:N] = np.concatenate([np.asarray(r, dtype=np.int64).reshape(-1) for r in rows])
+        md = np.ascontiguousarray([int(m) for m in modes], dtype=np.int32)
+        tm = lp = wt = wl = None
+        if times is not None:
+            tm = np.zeros((max(N, 1), 2), dtype=np.float32)
+            for r, t in enumerate(times):
+                t = np.asarray(t, dtype=np.float32).reshape(-1, 2)
+                if len(t) != len(rows[r]):
+                    raise ValueError("word_spans: times must have the shape of rows")
+                tm[first[r]: first[r + 1]] = t
+            wt = np.zeros_like(tm)
+        if logprobs is not None:
+            lp = np.zeros(max(N, 1), dtype=np.float32)
+            for r, t in enumerate(logprobs):
+                t = np.asarray(t, dtype=np.float32).reshape(-1)
+                if len(t) != len(rows[r]):
+                    raise ValueError("word_spans: logprobs must have the shape of rows")
+                lp[first[r]: first[r + 1]] = t
+            wl = np.zeros_like(lp)
+        nw = np.zeros(R, dtype=np.int32)
+        wf = np.zeros(N + R, dtype=np.int32)
+        ms = C.c_float(0)
+        self._check(self.lib.wm_word_spans(self.h, R, _ip(first), _ip(ids), _ip(md), None if tm is None else _fp(tm), None if lp is None else _fp(lp),
+                                           _ip(nw), _ip(wf), None if wt is None else _fp(wt), None if wl is None else _fp(wl), C.byref(ms)), "wm_word_spans")
+        self.last_words_ms = ms.value
+        out = []
+        for r in range(R):
+            b, n = int(first[r]), int(nw[r])
+            out.append((wf[b + r: b + r + n + 1].copy(), None if wt is None else wt[b: b + n].copy(), None if wl is None else wl[b: b + n].copy()))
+        return out
 
     def seq_bias_rows(self, entries, logits: np.ndarray, prefixes: Sequence[Sequence[int]]) -> np.ndarray:
         """Sequence-bias parity tap (wm_seq_bias_rows): rows ``logits [R, V]``, row r under ``prefixes[r]``, through k_seq_bias alone.  Returns the
