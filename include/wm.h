@@ -556,6 +556,65 @@ int wm_word_spans(wm_ctx* ctx, int R, const int32_t* first /* HOST [R+1] */, con
                   float* word_times /* HOST [first[R]][2]; may be NULL without times */,
                   float* word_logprobs /* HOST [first[R]]; may be NULL without logprobs */, float* ms /* may be NULL */);
 
+/* ---- speech windows of long recordings (additive to ABI v9; csrc/wm_vad.hip, csrc/wm_vad.h) ----
+ * The recipe WhisperX and faster-whisper (vad_filter=True) made standard — find the speech, cut only at pauses, pack the speech into windows of at
+ * most one model window — with an energy detector in the place of a trained VAD model: the contract below is the engine's own, as sampling_top_k's
+ * and allowed_sequences' are.
+ * Inputs: C recordings of 16 kHz mono float32 on the DEVICE, samples[c * n_max + i]; n_samples[c] (HOST, in [1, n_max]): samples behind it count as
+ * 0 and are not read.  T_c = ceil(n_samples[c] / 160) frames of 10 ms: the log-mel's hop, a frame index is a mel frame index.
+ * Parameters (wm_vad_params; WM_ERR_ARG names the cause): 0 < k_off <= k_on; 0 <= abs_off <= abs_on, finite; q_permille in [0, 1000];
+ * min_silence >= 1, min_speech >= 1, pad >= 0, F >= 2 (the longest window), all in frames and at most WM_VAD_FRAMES_MAX.
+ * Per recording:
+ *   1. Energy: E[t] = sum over k < 160 of x[160 t + k]^2 in float32, in this order: sixteen partial sums p_j = sum over i = 0..9 of
+ *      x[160 t + 16 i + j]^2, i ascending, every term a rounded multiply followed by a rounded add (no fused multiply-add); then p_j += p_{j+8},
+ *      p_j += p_{j+4}, p_j += p_{j+2}, p_0 += p_1.  A float32 numpy loop gives the same bits.
+ *   2. Loud level: R = the order statistic of rank (q_permille * (T - 1)) / 1000 (64-bit integer division) among E[0 .. T), values ordered by
+ *      their float32 bit patterns as unsigned integers (E >= +0: the numeric order); no interpolation.
+ *   3. Thresholds: thr_on = fmaxf(R * k_on, abs_on), thr_off = fmaxf(R * k_off, abs_off), one float32 multiply each.  The detector is relative to
+ *      the recording's loud level, not to a noise floor: a recording without pauses degrades to "all speech" (cut at its quietest frames by
+ *      step 6), never to "no speech"; digital silence (R = 0) falls under abs_on.
+ *   4. Hysteresis: s[-1] = 0; s[t] = 1 if E[t] >= thr_on, 0 if E[t] < thr_off, else s[t-1].
+ *   5. Regions: the maximal runs [a, b) of s = 1; neighbours whose gap a' - b < min_silence merge; merged regions with b - a < min_speech are
+ *      dropped; then padding: neighbours with gap g both move by pad if g >= 2 * pad, else both meet at b + g / 2 (integer division); the first
+ *      start is max(0, a - pad), the last stop min(T, b + pad).
+ *   6. Split: a region with b - a > F is cut at c, the frame of smallest E (bit-pattern order, the smallest t among equals) in
+ *      [a + F/2, a + F], ends inclusive: emit [a, c), a = c, repeat.
+ *   7. Pack, greedy over the pieces in order: a window opens at a piece's start u and absorbs following pieces while stop - u <= F; the window
+ *      is (u, last stop).  Every window is at most F frames, starts and ends inside a region, and every region frame lies in exactly one window.
+ * Outputs (HOST): n_regions[c] and n_windows[c]; the (start, stop) frame pairs back to back in the order of the recordings — the padded regions of
+ * step 5 (before splitting) in regions, the windows of step 7 in windows.  cap_regions / cap_windows: the pairs the caller's buffers hold; a result
+ * that does not fit is WM_ERR_ARG, the message names the needed counts, and no output is written.  Bounds a caller can size by: a recording has at
+ * most (T + min_silence) / (min_speech + min_silence) + 1 regions and at most that plus T / (F / 2) windows.
+ * Parity taps, each may be NULL: E [sum of T_c] back to back, R / thr_on / thr_off [C].
+ * Limits: WM_VAD_CLIPS_MAX recordings, WM_VAD_FRAMES_MAX frames per recording (46 h), WM_VAD_TOTAL_FRAMES_MAX frames per call,
+ * WM_VAD_WINDOWS_MAX windows per call (more: WM_ERR_ARG, "split the call").
+ * Kernels: all per-frame work is parallel over frames — the energy with 16 lanes per frame, R by a radix select over the bit patterns (LDS
+ * histograms merged with integer vector atomics), the hysteresis as a running maximum over "2 t + on if decisive, else -1", the run boundaries
+ * compacted by a prefix sum; scan state crosses blocks by chained launches (tile summaries, a scan of the summaries, apply), never by blocks
+ * waiting on each other.  The per-region stage walks on one lane per recording, the search of step 6 is a block-wide reduction.  Ten launches
+ * per call whatever C; integers and bit patterns only: two runs give the same bytes.
+ * On the context's stream, in a workspace and with an event pair of its own (allocated on first use, freed by wm_destroy).  Reads and writes
+ * nothing of the decode state: no wm_encode needed, no wm_decode_invalidate, the captured graphs and a decode in progress (between wm_decode_begin
+ * and wm_decode_run) are untouched.  *ms (may be NULL): hipEvent time of upload + kernels + download. */
+#define WM_VAD_CLIPS_MAX         4096
+#define WM_VAD_FRAMES_MAX        (1 << 24)      /* frames per recording */
+#define WM_VAD_TOTAL_FRAMES_MAX  (1 << 25)      /* frames per call, all recordings together */
+#define WM_VAD_WINDOWS_MAX       65536          /* windows per call */
+typedef struct wm_vad_params {
+    float k_on, k_off;                  /* thresholds relative to the loud level R */
+    float abs_on, abs_off;              /* absolute floors of the thresholds (frame energies) */
+    int32_t q_permille;                 /* the rank of R */
+    int32_t min_silence, min_speech;    /* frames */
+    int32_t pad;                        /* frames */
+    int32_t F;                          /* frames: the longest window */
+} wm_vad_params;
+int wm_vad_windows(wm_ctx* ctx, int C, const float* samples /* DEVICE [C][n_max] */, int64_t n_max, const int64_t* n_samples /* HOST [C] */,
+                   const wm_vad_params* params,
+                   int32_t* n_regions /* HOST [C] */, int32_t* regions /* HOST [cap_regions][2] */, int cap_regions,
+                   int32_t* n_windows /* HOST [C] */, int32_t* windows /* HOST [cap_windows][2] */, int cap_windows,
+                   float* E /* HOST [sum T_c] or NULL */, float* R /* HOST [C] or NULL */, float* thr_on /* HOST [C] or NULL */,
+                   float* thr_off /* HOST [C] or NULL */, float* ms /* may be NULL */);
+
 /* ---- parity taps (test-only views of intermediate state; no reference equivalent except
  * forward(), model.py:1223-1347) ---- */
 /* encoder output [B][n_ctx][d_model] as float32 to HOST */

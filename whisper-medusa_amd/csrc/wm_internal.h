@@ -346,6 +346,8 @@ struct wm_ctx {
     struct wm_merge_state* merge_state = nullptr;
     // wm_set_word_table / wm_word_spans (wm_words.hip): the vocabulary's bytes, a workspace and an event pair of their own; nothing of the decode state
     struct wm_words_state* words_state = nullptr;
+    // wm_vad_windows (wm_vad.hip): its workspace and event pair, allocated on first use; nothing of the decode state
+    struct wm_vad_state* vad_state = nullptr;
     int Bdec = 0;
     bool began = false, first_done = false;
     long long iters = 0;
@@ -432,6 +434,8 @@ void wm_constraint_free(wm_ctx* ctx);
 void wm_merge_free(wm_ctx* ctx);
 // implemented in wm_words.hip (grouping token ids into words; include/wm.h wm_set_word_table / wm_word_spans)
 void wm_words_free(wm_ctx* ctx);
+// implemented in wm_vad.hip (speech windows of long recordings; include/wm.h wm_vad_windows)
+void wm_vad_free(wm_ctx* ctx);
 // implemented in wm_align.hip
 void wm_align_free(wm_ctx* ctx);
 // implemented in wm_score.hip

@@ -30,6 +30,7 @@ from . import synth as _synth
 from . import timestamps as _timestamps
 from . import scores as _scores
 from . import words as _words
+from . import vad as _vad
 
 
 class EngineKVCache:
@@ -610,13 +611,7 @@ class WhisperMedusaModel:
         if len(clips) > self._max_batch:
             self.set_max_batch(len(clips))                          # wm_logmel checks B <= max_batch
         if not truncation:
-            mono = []
-            for c in clips:
-                if c.ndim == 2 or sampling_rate != 16000:
-                    t = torch.from_numpy(np.atleast_2d(c)[None]).to(self.device)     # [1, channels, n_in]
-                    mono.append(self.engine.resample(t, sampling_rate, 16000)[0])
-                else:
-                    mono.append(torch.from_numpy(c).to(self.device))
+            mono = self._wav_mono(clips, sampling_rate)
             n = max(160, -(-max(r.numel() for r in mono) // 160) * 160)
             buf = torch.zeros(len(mono), n, dtype=torch.float32, device=self.device)
             for i, r in enumerate(mono):
@@ -1165,6 +1160,8 @@ class WhisperMedusaModel:
                          time_precision, time_precision_features, return_token_timestamps, return_segments,
                          return_dict_in_generate, return_token_logprobs, top_logprobs, kwargs):
         """generate() behind its generation_config merge: the checks of every feature, the resolved call and the route that decodes it."""
+        # vad_longform (DESIGN.md §2q): speech windows cut at pauses; its refusals come first, each under its own message
+        plan = self._check_vad(kwargs, top_logprobs)
         # stride_length_s (DESIGN.md §2o): overlapping windows for chunk_longform, merged on the device; checked before every route's own refusals
         stride = None
         if kwargs.get("stride_length_s") is not None:
@@ -1269,7 +1266,8 @@ class WhisperMedusaModel:
         # (generate_from_wav with stride_length_s hands in the windows of all recordings, cut in the sample domain, and how many each one owns)
         counts = kwargs.get("_window_counts") if stride is not None else None
         if isinstance(language, (list, tuple)):
-            language = self._language_list(language, input_features.shape[0] if counts is None else len(counts))
+            language = self._language_list(language, len(plan["windows"]) if plan is not None else
+                                           input_features.shape[0] if counts is None else len(counts))
             if not self.config.is_multilingual:
                 language = None                         # ignored, as a scalar is (the prompt has no language slot)
         call = ResolvedCall(samp=samp, bias=bias, cons=cons, beam=beam, sc_req=sc_req, tt_req=tt_req, rep_pen=rep_pen, rep_g=rep_g,
@@ -1280,6 +1278,8 @@ class WhisperMedusaModel:
         detect = bool(language is None and self.config.is_multilingual and kwargs.get("detect_language", True))
         if kwargs.get("sequential_longform"):
             return self._generate_sequential(input_features, attention_mask, call, language, detect, time_precision_features)
+        if plan is not None:
+            return self._generate_vad(input_features, plan, call, language, detect)
         if counts is not None:
             return self._generate_strided(input_features, [int(c) for c in counts], stride, call, language, detect)
         if input_features.shape[-1] > self.config.n_mel_frames:
@@ -2043,19 +2043,7 @@ class WhisperMedusaModel:
         transformed on its own by wm_logmel, in groups of at most max_batch: HF's per-chunk features, the per-chunk ``max - 8`` clamp included."""
         F = self.config.n_mel_frames
         step = (F - stride[0] - stride[1]) * 160
-        if isinstance(wav, (list, tuple)):
-            clips = [np.asarray(w, dtype=np.float32) for w in wav]
-        else:
-            a = wav.detach().cpu().numpy() if isinstance(wav, torch.Tensor) else np.asarray(wav)
-            a = a.astype(np.float32)
-            clips = [a] if a.ndim == 1 else [r for r in a]
-        mono = []
-        for c in clips:
-            if c.ndim == 2 or sampling_rate != 16000:
-                t = torch.from_numpy(np.atleast_2d(c)[None]).to(self.device)
-                mono.append(self.engine.resample(t, sampling_rate, 16000)[0])
-            else:
-                mono.append(torch.from_numpy(c).to(self.device))
+        mono = self._wav_mono(wav, sampling_rate)
         counts, cuts = [], []
         for b, r in enumerate(mono):
             starts = self._window_plan(-(-r.numel() // 160), F, *stride)
@@ -2186,6 +2174,221 @@ class WhisperMedusaModel:
             return GenerateEncoderDecoderOutput(t, token_timestamps=_ts_tensor(all_tt).to(self.device), window_keep=window_keep, **(fields or {}))
         if rdg or (fields is not None and sreq["want"]):
             return GenerateEncoderDecoderOutput(t, window_keep=window_keep, **(fields or {}))
+        return t
+
+    # ---- VAD long-form: speech windows cut at pauses on the device, silence never decoded ----------------------------------
+    def _check_vad(self, kwargs, top_logprobs=None) -> Optional[dict]:
+        """What ``vad_longform=True`` refuses, each under its own name; returns the plan generate_from_wav handed in (None: not a VAD call)."""
+        if not kwargs.get("vad_longform"):
+            if kwargs.get("vad_options") is not None:
+                raise ValueError("vad_options is only valid together with vad_longform=True")
+            return None
+        for other in ("chunk_longform", "sequential_longform"):
+            if kwargs.get(other):
+                raise ValueError(f"vad_longform and {other} are alternatives: pass one of them")
+        if kwargs.get("stride_length_s") is not None:
+            raise ValueError("vad_longform and stride_length_s are alternatives: VAD windows are cut at pauses and do not overlap")
+        if kwargs.get("num_beams") not in (None, 1):
+            raise NotImplementedError("beam search (num_beams) is not supported with vad_longform (short-form only)")
+        if kwargs.get("sampling_seed") is not None or kwargs.get("do_sample"):
+            raise NotImplementedError("sampling (sampling_seed / do_sample) is not supported with vad_longform; use sequential_longform")
+        if top_logprobs is not None:
+            raise NotImplementedError("top_logprobs is not supported with vad_longform (short-form only)")
+        for names in (("sequence_bias", "bad_words_ids", "hotwords"), ("allowed_sequences", "allowed_phrases")):
+            given = [k for k in names if kwargs.get(k) is not None]
+            if given:
+                raise NotImplementedError(f"{' / '.join(given)} is not supported with vad_longform (short-form only)")
+        if kwargs.get("num_frames") is not None:
+            raise NotImplementedError("num_frames= is not supported together with vad_longform=True (the detector fixes the windows)")
+        if kwargs.get("streamer") is not None:
+            raise NotImplementedError("streamer= is not supported with vad_longform (the windows of a recording are decoded as one batch)")
+        plan = kwargs.get("_vad_plan")
+        if plan is None:
+            raise ValueError("vad_longform needs the waveform: call generate_from_wav(wav, vad_longform=True), not generate(input_features=...)")
+        return plan
+
+    def _wav_mono(self, wav, sampling_rate: int) -> List[torch.Tensor]:
+        """The audio front door of extract_features: every recording as 16 kHz mono float32 [n] on the GPU (downmix and resampling there).  Clips in
+        a list are mono [n] or multi-channel [channels, n]; a bare 2-D array is a batch of mono clips."""
+        if isinstance(wav, (list, tuple)):
+            clips = [np.asarray(w, dtype=np.float32) for w in wav]
+        else:
+            a = wav.detach().cpu().numpy() if isinstance(wav, torch.Tensor) else np.asarray(wav)
+            a = a.astype(np.float32)
+            clips = [a] if a.ndim == 1 else [r for r in a]
+        mono = []
+        for c in clips:
+            if c.ndim == 2 or sampling_rate != 16000:
+                t = torch.from_numpy(np.atleast_2d(c)[None]).to(self.device)     # [1, channels, n_in]
+                mono.append(self.engine.resample(t, sampling_rate, 16000)[0])
+            else:
+                mono.append(torch.from_numpy(c).to(self.device))
+        return mono
+
+    def _vad_detect(self, mono: List[torch.Tensor], vad_options) -> dict:
+        """ONE ``engine.vad_windows`` call for all recordings: the plan ``dict(regions, windows, params, ms_vad)`` in 10 ms frames."""
+        params = _vad.lower_options(vad_options, self.config.n_mel_frames)
+        if any(r.numel() < 1 for r in mono):
+            raise ValueError("vad_longform / detect_speech: a recording without samples")
+        buf = torch.zeros(len(mono), max(r.numel() for r in mono), dtype=torch.float32, device=self.device)
+        for i, r in enumerate(mono):
+            buf[i, : r.numel()] = r
+        eng = self.engine
+        regions, windows = eng.vad_windows(buf, [r.numel() for r in mono], params)
+        return dict(regions=regions, windows=windows, params=params, ms_vad=float(getattr(eng, "last_vad_ms", 0.0)))
+
+    def detect_speech(self, wav, sampling_rate: int = 16000, **vad_options) -> List[dict]:
+        """Where the speech of every recording lies and how ``generate_from_wav(vad_longform=True)`` would cut it: per recording
+        ``dict(regions=[(start, end)..], windows=[(start, end)..])`` in seconds (frames * 0.01).  An energy detector with hysteresis relative to
+        the recording's own loud level (include/wm.h wm_vad_windows), not a trained VAD model; ``vad_options``: onset_db,
+        offset_db, loud_percentile, min_level_dbfs, min_silence_ms, min_speech_ms, speech_pad_ms, max_window_s — the defaults are untuned."""
+        plan = self._vad_detect(self._wav_mono(wav, sampling_rate), vad_options or None)
+        sec = lambda pairs: [(a * 0.01, b * 0.01) for a, b in pairs]          # noqa: E731
+        return [dict(regions=sec(r), windows=sec(w)) for r, w in zip(plan["regions"], plan["windows"])]
+
+    def _vad_wav_windows(self, wav, sampling_rate: int, vad_options):
+        """Detect, then cut every window in the sample domain as [160 u, min(160 v, n)), zero-padded to the model's window and transformed on its
+        own by wm_logmel in groups of at most max_batch (the recipe of _strided_wav_windows).  A recording without a window contributes its first
+        window's worth of audio as one row, so that its language and prompt are defined; ``plan["first"]`` says which rows a recording owns."""
+        F = self.config.n_mel_frames
+        mono = self._wav_mono(wav, sampling_rate)
+        plan = self._vad_detect(mono, vad_options)
+        cuts, first = [], [0]
+        for b, ws in enumerate(plan["windows"]):
+            cuts += [(b, 160 * u, min(160 * v, mono[b].numel())) for u, v in ws] or [(b, 0, min(160 * F, mono[b].numel()))]
+            first.append(len(cuts))
+        feats = []
+        for g in range(0, len(cuts), self._max_batch):
+            grp = cuts[g: g + self._max_batch]
+            buf = torch.zeros(len(grp), F * 160, dtype=torch.float32, device=self.device)
+            for q, (b, lo, hi) in enumerate(grp):
+                buf[q, : hi - lo] = mono[b][lo:hi]
+            feats.append(self.engine.logmel(buf))
+        plan["first"] = first
+        return torch.cat(feats), plan
+
+    def _generate_vad(self, win, plan: dict, call: "ResolvedCall", language, detect: bool):
+        """`generate_from_wav(vad_longform=True)`: the rows ``win`` are the speech windows of all recordings (recording b owns the rows
+        ``plan["first"][b] .. plan["first"][b + 1]``; one placeholder row where it has no window), decoded like _generate_longform's — language
+        once per recording on its first row, one batch per language group — and assembled per recording: the prompt once, every window's ids
+        without EOS or padding, one EOS.  Window j of a recording starts at u_j * 0.01 s on the recording's clock: that start is added to the
+        window's segments and token timestamps.  A recording without speech returns prompt + EOS.  No conditioning across windows; times a
+        window emits beyond its own audio, in the zero padding, are not clamped."""
+        cfg = self.config
+        rdg, sreq, req = call.return_dict_in_generate, call.sc_req, call.tt_req
+        rseg, tprec, rts = call.return_segments, call.time_precision, call.return_timestamps
+        F, wins, first = cfg.n_mel_frames, plan["windows"], plan["first"]
+        B = len(wins)
+        counts = [len(w) for w in wins]
+        n = max(counts + [0])
+        if win.shape[0] != first[-1]:
+            raise ValueError(f"vad_longform: {win.shape[0]} rows for the plan's {first[-1]}")
+        win = win.to(self.device, torch.float32)
+        if detect:
+            langs = self.detect_language(win[first[:-1]])
+        else:
+            langs = list(language) if isinstance(language, (list, tuple)) else [language] * B
+        self._clip_languages = list(langs)
+        W = first[-1]
+        rows, prompts = [None] * W, [None] * B
+        wtt = [None] * W
+        wsc: List[Optional[dict]] = [None] * W
+        ms_tt = ms_sc = 0.0
+        for l in sorted(set(langs), key=lambda v: (v is None, v or "")):
+            clips = [b for b in range(B) if langs[b] == l]
+            # the windows of the group; a group of silent recordings alone decodes one placeholder row for its prompt
+            widx = [first[b] + j for b in clips for j in range(counts[b])] or [first[clips[0]]]
+            res = self._generate_short(win[widx], call, language=l)
+            o = self._pad(res.seqs, res.gp)
+            ms_tt += res.stats.get("ms_token_timestamps", 0.0)
+            ms_sc += res.stats.get("ms_token_logprobs", 0.0)
+            for q, wi in enumerate(widx):
+                rows[wi] = o[q]
+                if req is not None:
+                    wtt[wi] = res.token_timestamps[q].cpu()
+                if sreq is not None:
+                    wsc[wi] = {k: v[q].cpu() for k, v in res.scores.items() if not k.startswith("_")}
+            for b in clips:
+                prompts[b] = list(res.gp.prompt)
+        eos, pad = cfg.eos_token_id, cfg.pad_token_id
+        seqs, all_tt, all_lp = [], [], []
+        segs = [[] for _ in range(B)]
+        for b in range(B):
+            ids = list(prompts[b])
+            P = len(ids)
+            tts = [0.0] * P
+            lps, last_eos_lp = [0.0] * P, 0.0
+            for j in range(counts[b]):
+                wi = first[b] + j
+                if sreq is not None and "skipped" in wsc[wi] and bool(wsc[wi]["skipped"]):
+                    continue
+                t0 = wins[b][j][0] * 0.01                                  # the window's start on the recording's clock
+                start = torch.tensor(t0, dtype=torch.float32)              # (float32 sum, as the tensors hold it)
+                if rts and rseg:
+                    ws = _timestamps.row_segments(rows[wi].tolist(), P, eos, cfg.timestamp_begin, F, tprec, time_offset=t0, result=rows[wi])
+                    if req is not None:
+                        _segment_slices(ws, P, "token_timestamps", wtt[wi] + start)
+                    if sreq is not None:
+                        _segment_slices(ws, P, "token_logprobs", wsc[wi]["token_logprobs"])
+                    segs[b] += ws
+                for q, t in enumerate(rows[wi][P:].tolist()):
+                    if t == eos or t == pad:
+                        if sreq is not None:      # the recording's one EOS takes the score of the last kept window's
+                            last_eos_lp = float(wsc[wi]["token_logprobs"][P + q])
+                        break
+                    ids.append(t)
+                    if sreq is not None:
+                        lps.append(float(wsc[wi]["token_logprobs"][P + q]))
+                    if req is not None:
+                        tts.append(float(wtt[wi][P + q] + start))
+            seqs.append(ids + [eos])
+            all_tt.append(tts + [tts[-1]])
+            all_lp.append(lps + [last_eos_lp])
+        t = _ids_tensor(seqs, pad).to(self.device)
+        vad_windows = torch.full((B, n, 2), -1, dtype=torch.long)
+        for b in range(B):
+            if counts[b]:
+                vad_windows[b, : counts[b]] = torch.tensor(wins[b], dtype=torch.long).view(-1, 2)
+        vad_windows = vad_windows.to(self.device)
+        speech_regions = [[(a * 0.01, e * 0.01) for a, e in r] for r in plan["regions"]]
+        self.last_vad_windows, self.last_speech_regions = vad_windows, speech_regions
+        tmpl = next((w for w in wsc if w is not None), None)
+
+        def per_window(k, fill):
+            # window-level fields stay [B, n]: NaN / False behind a recording's last window
+            out = torch.full((B, n), fill, dtype=tmpl[k].dtype)
+            for b in range(B):
+                if counts[b]:
+                    out[b, : counts[b]] = torch.stack([wsc[w][k] for w in range(first[b], first[b] + counts[b])])
+            return out.to(self.device)
+
+        fields = None
+        if sreq is not None:
+            fields = self._clip_score_fields(all_lp, seqs, prompts)
+            for k in ("no_speech_prob", "skipped", "needs_fallback"):
+                if k in tmpl:
+                    fields[k] = per_window(k, False if tmpl[k].dtype == torch.bool else float("nan"))
+            fields["window_avg_logprob"] = per_window("avg_logprob", float("nan"))
+            self.last_scores = fields
+            res.stats["ms_token_logprobs"] = ms_sc
+        if req is not None:
+            res.stats["ms_token_timestamps"] = ms_tt
+        res.stats["ms_vad"] = plan["ms_vad"]
+        res.stats["longform_windows"] = list(counts)
+        self._publish(res, None)
+        extra = dict(vad_windows=vad_windows, speech_regions=speech_regions, **(fields or {}))
+        if req is not None:
+            out = GenerateEncoderDecoderOutput(t, token_timestamps=_ts_tensor(all_tt).to(self.device), **extra)
+            if rts and rseg:
+                out["segments"] = segs
+            return out
+        if rdg or (fields is not None and sreq["want"]):
+            out = GenerateEncoderDecoderOutput(t, **extra)
+            if rts and rseg:
+                out["segments"] = segs
+            return out
+        if rts and rseg:
+            return dict({"sequences": t, "segments": segs}, **extra)
         return t
 
     # ---- sequential long-form: HF's seek loop around the short-form path (DESIGN.md §2f) ---------------------------------------------
@@ -2408,7 +2611,15 @@ class WhisperMedusaModel:
 
     def generate_from_wav(self, wav, **kw) -> torch.Tensor:
         """log-mel on the GPU, then ``generate`` — the whole hot path of SURVEY.md §8a in one call.  ``sequential_longform=True``: the
-        log-mel of the whole recordings (``extract_features(truncation=False)``) and every clip's own length, then the sequential loop."""
+        log-mel of the whole recordings (``extract_features(truncation=False)``) and every clip's own length, then the sequential loop.
+        ``vad_longform=True[, vad_options={..}]``: the speech of every recording is found on the device, cut only at pauses
+        and packed into windows of at most the model's window, all windows of all recordings are decoded as batches, and the times go back
+        on the recording's clock; ``vad_windows`` / ``speech_regions`` in the dict forms, ``last_stats["ms_vad"]``."""
+        if kw.get("vad_longform") or kw.get("vad_options") is not None:
+            # speech windows cut at pauses (DESIGN.md §2q): detect on the device, cut in the sample domain, one log-mel per window
+            self._check_vad(dict(kw, _vad_plan={}), kw.get("top_logprobs"))
+            win, plan = self._vad_wav_windows(wav, kw.pop("sampling_rate", 16000), kw.pop("vad_options", None))
+            return self.generate(win, _vad_plan=plan, **kw)
         if kw.get("sequential_longform"):
             feats = self.extract_features(wav, kw.pop("sampling_rate", 16000), truncation=False)
             kw.setdefault("num_frames", self.last_num_frames)

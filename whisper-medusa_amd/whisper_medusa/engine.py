@@ -124,13 +124,21 @@ EXPORTS = ["wm_create", "wm_destroy", "wm_last_error", "wm_abi_version", "wm_bui
            "wm_set_beam", "wm_get_beam_result", "wm_beam_rows", "wm_beam_reorder_kv",
            "wm_set_sequence_bias", "wm_seq_bias_rows", "wm_set_constraint", "wm_constraint_rows",
            "wm_set_stream_prompts", "wm_detect_language", "wm_lang_pick_rows", "wm_merge_windows",
-           "wm_set_word_table", "wm_word_spans"]
+           "wm_set_word_table", "wm_word_spans", "wm_vad_windows"]
 
 LANG_MAX = 256                                             # WM_LANG_MAX (include/wm.h)
 MERGE_LEN_MAX, MERGE_WINDOWS_MAX = 512, 4096               # WM_MERGE_LEN_MAX, WM_MERGE_WINDOWS_MAX
 WORDS_SPACES, WORDS_UNICODE = 0, 1                         # WM_WORDS_SPACES, WM_WORDS_UNICODE
 WORDS_ROWS_MAX, WORDS_IDS_MAX = 65536, 4 << 20             # WM_WORDS_ROWS_MAX, WM_WORDS_IDS_MAX
 WORDS_TILE = 1024                                          # WW_TILE (csrc/wm_words.h): tokens of a row staged per round of k_word_spans
+VAD_HOP, VAD_TILE = 160, 1024                              # VAD_HOP (csrc/wm_vad.h), VAD_TILE (csrc/wm_vad.hip): samples per frame, frame positions per block
+VAD_CLIPS_MAX, VAD_FRAMES_MAX, VAD_TOTAL_FRAMES_MAX, VAD_WINDOWS_MAX = 4096, 1 << 24, 1 << 25, 65536      # WM_VAD_*_MAX
+
+
+class WmVadParams(C.Structure):
+    """wm_vad_params (include/wm.h), in the header's order."""
+    _fields_ = [("k_on", C.c_float), ("k_off", C.c_float), ("abs_on", C.c_float), ("abs_off", C.c_float),
+                ("q_permille", C.c_int32), ("min_silence", C.c_int32), ("min_speech", C.c_int32), ("pad", C.c_int32), ("F", C.c_int32)]
 
 _lib = {}
 
@@ -198,6 +206,8 @@ def load_library(path: Optional[str] = None, act_fp16: bool = False) -> C.CDLL:
     lib.wm_merge_windows.argtypes = [vp, i32, i32p, i32p, i32, i32p, f32p, i32p, f32p]
     lib.wm_set_word_table.argtypes = [vp, C.POINTER(C.c_uint8), i32p, i32]
     lib.wm_word_spans.argtypes = [vp, i32, i32p, i32p, i32p, f32p, f32p, i32p, i32p, f32p, f32p, f32p]
+    lib.wm_vad_windows.argtypes = [vp, i32, vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(WmVadParams), i32p, i32p, i32, i32p, i32p, i32,
+                                   f32p, f32p, f32p, f32p, f32p]
     lib.wm_decode_run.argtypes = [vp, i32, i32p]
     lib.wm_get_tokens.argtypes = [vp, i32, i32p, i32, i32p]
     lib.wm_get_stats.argtypes = [vp, C.POINTER(WmStats)]
@@ -665,6 +675,48 @@ class Engine:
             b, n = int(first[r]), int(nw[r])
             out.append((wf[b + r: b + r + n + 1].copy(), None if wt is None else wt[b: b + n].copy(), None if wl is None else wl[b: b + n].copy()))
         return out
+
+    def vad_windows(self, samples_dev: torch.Tensor, n_samples: Sequence[int], params, taps: bool = False):
+        """wm_vad_windows: the speech regions of every recording and the windows of at most ``F`` frames that hold them, cut only at pauses (or, in
+        speech without pauses, at the quietest frame) — one call, a fixed number of kernel launches, for all recordings.  ``samples_dev``: float32
+        [C, n_max] on the GPU, 16 kHz mono; ``n_samples[c]``: the recording's own length, what lies behind it is not read; ``params``: a
+        ``WmVadParams`` or a dict of its fields (include/wm.h states the contract).  Returns ``(regions, windows)``, per recording a list of
+        ``(start, stop)`` in 10 ms frames; with ``taps=True`` also ``dict(E=[float32 [T_c]..], R=, thr_on=, thr_off=float32 [C])``.  More than
+        VAD_WINDOWS_MAX windows: ``ValueError``, split the call.  Touches nothing of the decode state; ``last_vad_ms`` holds the hipEvent time."""
+        if not isinstance(params, WmVadParams):
+            params = WmVadParams(**dict(params))
+        x = samples_dev.to(self.device, torch.float32).contiguous()
+        if x.dim() != 2:
+            raise ValueError("vad_windows: samples_dev must be [C, n_max]")
+        Cn, n_max = x.shape
+        ns = np.ascontiguousarray([int(n) for n in n_samples], dtype=np.int64)
+        if len(ns) != Cn:
+            raise ValueError("vad_windows: n_samples must have one entry per recording")
+        T = (np.clip(ns, 0, None) + VAD_HOP - 1) // VAD_HOP
+        # the header's bounds: regions are at least min_speech long and min_silence apart, a cut piece is at least F / 2 frames
+        ms_, sp_, F_ = max(int(params.min_silence), 1), max(int(params.min_speech), 1), max(int(params.F), 2)
+        cap_r = int(np.sum((T + ms_) // (sp_ + ms_) + 1))
+        cap_w = cap_r + int(np.sum(T // (F_ // 2)))
+        nr, nw = np.zeros(Cn, dtype=np.int32), np.zeros(Cn, dtype=np.int32)
+        reg, win = np.zeros((max(cap_r, 1), 2), dtype=np.int32), np.zeros((max(cap_w, 1), 2), dtype=np.int32)
+        E = R = on = off = None
+        if taps:
+            E = np.zeros(max(int(T.sum()), 1), dtype=np.float32)
+            R, on, off = (np.zeros(Cn, dtype=np.float32) for _ in range(3))
+        ms = C.c_float(0)
+        self._inputs_ready()
+        self._check(self.lib.wm_vad_windows(self.h, Cn, C.c_void_p(x.data_ptr()), n_max, ns.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(params),
+                                            _ip(nr), _ip(reg), cap_r, _ip(nw), _ip(win), cap_w,
+                                            None if E is None else _fp(E), None if R is None else _fp(R), None if on is None else _fp(on),
+                                            None if off is None else _fp(off), C.byref(ms)), "wm_vad_windows")
+        self.last_vad_ms = ms.value
+        r0, w0 = np.concatenate([[0], np.cumsum(nr)]), np.concatenate([[0], np.cumsum(nw)])
+        regions = [[(int(a), int(b)) for a, b in reg[r0[c]: r0[c + 1]]] for c in range(Cn)]
+        windows = [[(int(a), int(b)) for a, b in win[w0[c]: w0[c + 1]]] for c in range(Cn)]
+        if not taps:
+            return regions, windows
+        t0 = np.concatenate([[0], np.cumsum(T)])
+        return regions, windows, dict(E=[E[t0[c]: t0[c + 1]].copy() for c in range(Cn)], R=R, thr_on=on, thr_off=off)
 
     def seq_bias_rows(self, entries, logits: np.ndarray, prefixes: Sequence[Sequence[int]]) -> np.ndarray:
         """Sequence-bias parity tap (wm_seq_bias_rows): rows ``logits [R, V]``, row r under ``prefixes[r]``, through k_seq_bias alone.  Returns the
