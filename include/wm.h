@@ -615,6 +615,58 @@ int wm_vad_windows(wm_ctx* ctx, int C, const float* samples /* DEVICE [C][n_max]
                    float* E /* HOST [sum T_c] or NULL */, float* R /* HOST [C] or NULL */, float* thr_on /* HOST [C] or NULL */,
                    float* thr_off /* HOST [C] or NULL */, float* ms /* may be NULL */);
 
+/* ---- live transcription: the agreement step of streaming sessions (additive to ABI v9; csrc/wm_stream.hip, csrc/wm_stream.h) ----
+ * The LocalAgreement-2 policy of Macháček et al., "Turning Whisper into Real-Time Transcription System" (2023), known from the whisper_streaming
+ * tool: a recording grows chunk by chunk, its rolling buffer is transcribed again on every tick, and a word is committed once two consecutive
+ * hypotheses agree on it.  One call decides that for the S sessions of a tick; the contract below is the engine's own, as wm_vad_windows' is.
+ * Word lists.  Each session has three lists of words, all given as token ids: new_list (this tick's hypothesis), prev_list (the uncommitted rest
+ * of the last tick's hypothesis) and tail_list (at most WM_STREAM_TAIL committed words, in order, newest last).  A list is three HOST arrays
+ * (wm_stream_list): words[S + 1], ascending from 0 — session s owns the words words[s] .. words[s + 1]); tok[words[S] + 1], ascending strictly
+ * from 0 — word w is the ids[tok[w] .. tok[w + 1]), at least one id per word; ids[tok[words[S]]], text ids below the n_tokens of wm_set_word_table.
+ * times: int32 (start, end) per word of new_list, in CENTISECONDS on the recording's clock.  last_cs[s]: the end of the session's last committed
+ * word, 0 before the first commit.  params (NULL: the defaults): late_cs >= 0 (WM_STREAM_LATE_CS), near_cs >= 0 (WM_STREAM_NEAR_CS), max_ngram in
+ * [1, WM_STREAM_TAIL] (default WM_STREAM_TAIL).
+ * Key of a word: the bytes of its tokens, concatenated in order, with every leading and every trailing byte 0x20 removed — no other whitespace,
+ * inner bytes are kept, an all-space word has the empty key.  Two words are equal iff their keys are byte-equal: case and punctuation count,
+ * tokenisation does not (" hel" + "lo" = " hello" = "hello").
+ * Per session, with n / P / C the words of new / prev / tail:
+ *   1. Late words: k0 = the smallest w with start[w] > last_cs - late_cs, or n if there is none (a prefix, not a filter).
+ *   2. Overlap with what is committed, only if k0 < n, C > 0 and |start[k0] - last_cs| < near_cs: for i = 1 .. min(C, n - k0, max_ngram), ascending,
+ *      test whether the last i words of tail equal new[k0 .. k0 + i) word for word; at the first i that matches, k0 += i and the loop stops.
+ *   3. Agreement: m = the largest m <= min(n - k0, P) with new[k0 + j] == prev[j] for all j < m.
+ *   4. Sentence end: ender = the largest w in [k0, k0 + m) whose key ends in one of . ? ! 。 (E3 80 82) ？ (EF BC 9F) ！ (EF BC 81), or -1.
+ * Outputs (HOST int32 [S] each): skip = k0, commit = m, ender.  The caller commits new[k0 .. k0 + m) and keeps new[k0 + m ..) as the next prev.
+ * k_stream_agree: one block of 256 threads per session, one launch.  Step 1 is a block minimum over the words, step 2 at most 15 word compares on
+ * one lane, step 3 a block minimum over the first mismatch — every lane walks the two byte streams of every 256th word pair through the table, a
+ * counter of pending spaces drops the trailing ones without look-ahead —, step 4 a block maximum; block barriers between the steps.  Integers
+ * and bytes only, no atomics, plain vector stores: two runs give the same bytes.
+ * One upload, one launch, one download on the context's stream, in a workspace and with an event pair of its own (allocated on first use, freed
+ * by wm_destroy).  Reads and writes nothing of the decode state: no wm_encode needed, no wm_decode_invalidate, the captured graphs and a decode in
+ * progress (between wm_decode_begin and wm_decode_run) are untouched.  *ms (may be NULL): hipEvent time of upload + kernel + download.
+ * WM_ERR_ARG (wm_last_error names the cause): a null pointer, S outside [1, WM_STREAM_SESSIONS_MAX], words or tok not ascending from 0, a word
+ * without ids, more than WM_STREAM_TAIL tail words for a session, an id outside the table, more than WM_STREAM_WORDS_MAX words or
+ * WM_STREAM_IDS_MAX ids in the three lists together, a parameter out of range.  WM_ERR_STATE: no table set. */
+#define WM_STREAM_TAIL          5               /* committed words per session in tail_list; the longest overlap tested */
+#define WM_STREAM_SESSIONS_MAX  4096            /* sessions per call */
+#define WM_STREAM_WORDS_MAX     (1 << 20)       /* words per call, the three lists together */
+#define WM_STREAM_IDS_MAX       (4 << 20)       /* ids per call, the three lists together */
+#define WM_STREAM_LATE_CS       10              /* default late_cs */
+#define WM_STREAM_NEAR_CS       100             /* default near_cs */
+typedef struct wm_stream_list {
+    const int32_t* words;               /* HOST [S+1] */
+    const int32_t* tok;                 /* HOST [words[S]+1] */
+    const int32_t* ids;                 /* HOST [tok[words[S]]] */
+} wm_stream_list;
+typedef struct wm_stream_params {
+    int32_t late_cs;                    /* words starting at or before last_cs - late_cs are dropped from the front */
+    int32_t near_cs;                    /* the overlap test applies when the first kept word starts within near_cs of last_cs */
+    int32_t max_ngram;                  /* the longest overlap tested, 1 .. WM_STREAM_TAIL */
+} wm_stream_params;
+int wm_stream_agree(wm_ctx* ctx, int S, const wm_stream_list* new_list, const wm_stream_list* prev_list, const wm_stream_list* tail_list,
+                    const int32_t* times /* HOST [new_list->words[S]][2] */, const int32_t* last_cs /* HOST [S] */,
+                    const wm_stream_params* params /* NULL: the defaults */,
+                    int32_t* skip /* HOST [S] */, int32_t* commit /* HOST [S] */, int32_t* ender /* HOST [S] */, float* ms /* may be NULL */);
+
 /* ---- parity taps (test-only views of intermediate state; no reference equivalent except
  * forward(), model.py:1223-1347) ---- */
 /* encoder output [B][n_ctx][d_model] as float32 to HOST */

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.environ.get("WM_CSRC", os.path.join(HERE, "csrc"))      # WM_CSRC: a patched copy of csrc/ (A/B variants of tests/microbench)
 OUT_DIR = os.path.join(HERE, "whisper_medusa")
 LIB = os.path.join(OUT_DIR, "libwm.so")
-SOURCES = ["wm_engine.hip", "wm_decoder.hip", "wm_encoder.hip", "wm_align.hip", "wm_score.hip", "wm_sample.hip", "wm_beam.hip", "wm_seq_bias.hip", "wm_constraint.hip", "wm_lang.hip", "wm_merge.hip", "wm_words.hip", "wm_vad.hip"]
+SOURCES = ["wm_engine.hip", "wm_decoder.hip", "wm_encoder.hip", "wm_align.hip", "wm_score.hip", "wm_sample.hip", "wm_beam.hip", "wm_seq_bias.hip", "wm_constraint.hip", "wm_lang.hip", "wm_merge.hip", "wm_words.hip", "wm_vad.hip", "wm_stream.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # gfx950 can hand the first kernel arguments to a wave in SGPRs at launch (kernarg preload): the decode chain's kernels then

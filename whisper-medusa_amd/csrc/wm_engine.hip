@@ -46,6 +46,7 @@ extern "C" void wm_destroy(wm_ctx* ctx)
     wm_merge_free(ctx);
     wm_words_free(ctx);
     wm_vad_free(ctx);
+    wm_stream_free(ctx);
     if (ctx->ev0) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) hipEventDestroy(ctx->ev1);
     if (ctx->own_stream && ctx->stream) hipStreamDestroy(ctx->stream);

@@ -348,6 +348,8 @@ struct wm_ctx {
     struct wm_words_state* words_state = nullptr;
     // wm_vad_windows (wm_vad.hip): its workspace and event pair, allocated on first use; nothing of the decode state
     struct wm_vad_state* vad_state = nullptr;
+    // wm_stream_agree (wm_stream.hip): its workspace and event pair, allocated on first use; nothing of the decode state
+    struct wm_stream_state* stream_state = nullptr;
     int Bdec = 0;
     bool began = false, first_done = false;
     long long iters = 0;
@@ -434,8 +436,12 @@ void wm_constraint_free(wm_ctx* ctx);
 void wm_merge_free(wm_ctx* ctx);
 // implemented in wm_words.hip (grouping token ids into words; include/wm.h wm_set_word_table / wm_word_spans)
 void wm_words_free(wm_ctx* ctx);
+// the device copy of the vocabulary table for the other kernels that read it (wm_stream.hip): n_tokens, 0 without a table
+int wm_words_table(const wm_ctx* ctx, const unsigned char** blob, const int** offsets);
 // implemented in wm_vad.hip (speech windows of long recordings; include/wm.h wm_vad_windows)
 void wm_vad_free(wm_ctx* ctx);
+// implemented in wm_stream.hip (the agreement step of live transcription; include/wm.h wm_stream_agree)
+void wm_stream_free(wm_ctx* ctx);
 // implemented in wm_align.hip
 void wm_align_free(wm_ctx* ctx);
 // implemented in wm_score.hip

@@ -23,6 +23,14 @@ struct wm_words_state {
 
 void wm_words_free(wm_ctx* ctx) { delete ctx->words_state; ctx->words_state = nullptr; }
 
+int wm_words_table(const wm_ctx* ctx, const unsigned char** blob, const int** offsets)
+{
+    const wm_words_state* S = ctx->words_state;
+    if (!S || S->n_tokens < 1) return 0;
+    *blob = S->blob; *offsets = S->offsets;
+    return S->n_tokens;
+}
+
 __global__ void __launch_bounds__(256)
 k_word_spans(const unsigned char* __restrict__ blob, const int* __restrict__ offsets, const int* __restrict__ first, const int* __restrict__ modes,
              const int* __restrict__ ids, const float* __restrict__ times /* null: none */, const float* __restrict__ logprobs /* null: none */,

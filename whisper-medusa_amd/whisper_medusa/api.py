@@ -2630,6 +2630,16 @@ class WhisperMedusaModel:
             return self.generate(win, _window_counts=counts, **kw)
         return self.generate(self.extract_features(wav), **kw)
 
+    def stream_sessions(self, n: int, *, tokenizer=None, word_table=None, min_chunk_s: float = 1.0, trim_s: Optional[float] = None,
+                        hard_trim_s: Optional[float] = None, late_s: float = 0.1, near_s: float = 1.0, **generate_kwargs):
+        """``n`` live transcription sessions (whisper_medusa/streaming.py): ``sessions.feed([chunk or None, ...])`` appends 16 kHz
+        audio to every session's rolling buffer, transcribes the sessions that received ``min_chunk_s`` of audio since their last decode as ONE
+        ``generate(return_word_timestamps=True)`` batch, and commits the words on which two consecutive hypotheses agree (LocalAgreement-2,
+        one HIP launch per tick for all sessions), with times on the recording's clock.  ``generate_kwargs`` go to every generate() call."""
+        from .streaming import StreamSessions
+        return StreamSessions(self, n, max_batch=self._max_batch, tokenizer=tokenizer, word_table=word_table, min_chunk_s=min_chunk_s, trim_s=trim_s,
+                              hard_trim_s=hard_trim_s, late_s=late_s, near_s=near_s, **generate_kwargs)
+
     # ---- forward ----------------------------------------------------------------------------
     @torch.no_grad()
     def forward(self, input_features: Optional[torch.Tensor] = None, attention_mask=None,

@@ -6,6 +6,7 @@ There is NO fallback: if the HIP library is missing or there is no GPU, construc
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 import os
 from typing import List, Optional, Sequence, Tuple
 
@@ -124,7 +125,7 @@ EXPORTS = ["wm_create", "wm_destroy", "wm_last_error", "wm_abi_version", "wm_bui
            "wm_set_beam", "wm_get_beam_result", "wm_beam_rows", "wm_beam_reorder_kv",
            "wm_set_sequence_bias", "wm_seq_bias_rows", "wm_set_constraint", "wm_constraint_rows",
            "wm_set_stream_prompts", "wm_detect_language", "wm_lang_pick_rows", "wm_merge_windows",
-           "wm_set_word_table", "wm_word_spans", "wm_vad_windows"]
+           "wm_set_word_table", "wm_word_spans", "wm_vad_windows", "wm_stream_agree"]
 
 LANG_MAX = 256                                             # WM_LANG_MAX (include/wm.h)
 MERGE_LEN_MAX, MERGE_WINDOWS_MAX = 512, 4096               # WM_MERGE_LEN_MAX, WM_MERGE_WINDOWS_MAX
@@ -133,6 +134,18 @@ WORDS_ROWS_MAX, WORDS_IDS_MAX = 65536, 4 << 20             # WM_WORDS_ROWS_MAX, 
 WORDS_TILE = 1024                                          # WW_TILE (csrc/wm_words.h): tokens of a row staged per round of k_word_spans
 VAD_HOP, VAD_TILE = 160, 1024                              # VAD_HOP (csrc/wm_vad.h), VAD_TILE (csrc/wm_vad.hip): samples per frame, frame positions per block
 VAD_CLIPS_MAX, VAD_FRAMES_MAX, VAD_TOTAL_FRAMES_MAX, VAD_WINDOWS_MAX = 4096, 1 << 24, 1 << 25, 65536      # WM_VAD_*_MAX
+STREAM_TAIL, STREAM_SESSIONS_MAX, STREAM_WORDS_MAX, STREAM_IDS_MAX = 5, 4096, 1 << 20, 4 << 20         # WM_STREAM_*
+STREAM_LATE_CS, STREAM_NEAR_CS = 10, 100                   # WM_STREAM_LATE_CS, WM_STREAM_NEAR_CS
+
+
+class WmStreamList(C.Structure):
+    """wm_stream_list (include/wm.h)."""
+    _fields_ = [("words", C.POINTER(C.c_int32)), ("tok", C.POINTER(C.c_int32)), ("ids", C.POINTER(C.c_int32))]
+
+
+class WmStreamParams(C.Structure):
+    """wm_stream_params (include/wm.h), in the header's order."""
+    _fields_ = [("late_cs", C.c_int32), ("near_cs", C.c_int32), ("max_ngram", C.c_int32)]
 
 
 class WmVadParams(C.Structure):
@@ -208,6 +221,8 @@ def load_library(path: Optional[str] = None, act_fp16: bool = False) -> C.CDLL:
     lib.wm_word_spans.argtypes = [vp, i32, i32p, i32p, i32p, f32p, f32p, i32p, i32p, f32p, f32p, f32p]
     lib.wm_vad_windows.argtypes = [vp, i32, vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(WmVadParams), i32p, i32p, i32, i32p, i32p, i32,
                                    f32p, f32p, f32p, f32p, f32p]
+    lib.wm_stream_agree.argtypes = [vp, i32, C.POINTER(WmStreamList), C.POINTER(WmStreamList), C.POINTER(WmStreamList), i32p, i32p,
+                                    C.POINTER(WmStreamParams), i32p, i32p, i32p, f32p]
     lib.wm_decode_run.argtypes = [vp, i32, i32p]
     lib.wm_get_tokens.argtypes = [vp, i32, i32p, i32, i32p]
     lib.wm_get_stats.argtypes = [vp, C.POINTER(WmStats)]
@@ -675,6 +690,56 @@ class Engine:
             b, n = int(first[r]), int(nw[r])
             out.append((wf[b + r: b + r + n + 1].copy(), None if wt is None else wt[b: b + n].copy(), None if wl is None else wl[b: b + n].copy()))
         return out
+
+    @staticmethod
+    def _stream_list(name: str, sessions):
+        """One word list of a stream_agree call as (words, tok, ids) int32 arrays: ``sessions[s]`` is a list of words, a word a list of ids."""
+        words = np.zeros(len(sessions) + 1, dtype=np.int32)
+        words[1:] = np.cumsum([len(w) for w in sessions])
+        flat = [w for ws in sessions for w in ws]           # one pass over the words, one over the ids: no array per word
+        lens = list(map(len, flat))
+        if 0 in lens:
+            raise ValueError(f"stream_agree: {name}: every word needs at least one id")
+        tok = np.zeros(len(lens) + 1, dtype=np.int32)
+        tok[1:] = np.cumsum(lens)
+        n = int(tok[-1])
+        ids = np.zeros(max(n, 1), dtype=np.int32)
+        if n:
+            ids[:n] = np.fromiter(itertools.chain.from_iterable(flat), dtype=np.int64, count=n)
+        return words, tok, ids
+
+    def stream_agree(self, new, prev, tail, times, last_cs, late_cs: int = STREAM_LATE_CS, near_cs: int = STREAM_NEAR_CS, max_ngram: int = STREAM_TAIL):
+        """wm_stream_agree: the LocalAgreement-2 decision for all live sessions of a tick as one kernel launch (include/wm.h states the contract).
+        ``new[s]`` / ``prev[s]`` / ``tail[s]``: the session's hypothesis of this tick, the uncommitted rest of the last one and its last (at most
+        STREAM_TAIL) committed words — lists of words, a word a list of text ids; ``times[s]``: int [n, 2] (start, end) of the words of ``new[s]``
+        in centiseconds on the recording's clock; ``last_cs[s]``: the end of the last committed word.  Returns ``(skip, commit, ender)``, int32
+        [S] each: the session commits ``new[s][skip: skip + commit]``.  Needs the table of ``set_word_table``; touches nothing of the decode
+        state; ``last_stream_ms`` holds the hipEvent time of upload + kernel + download."""
+        S = len(new)
+        if len(prev) != S or len(tail) != S or len(times) != S or len(last_cs) != S:
+            raise ValueError("stream_agree: new, prev, tail, times and last_cs must have one entry per session")
+        if S == 0:
+            self.last_stream_ms = 0.0
+            z = np.zeros(0, dtype=np.int32)
+            return z, z.copy(), z.copy()
+        if any(len(t) > STREAM_TAIL for t in tail):
+            raise ValueError(f"stream_agree: tail holds at most STREAM_TAIL = {STREAM_TAIL} words per session")
+        arrs = [self._stream_list(nm, l) for nm, l in (("new", new), ("prev", prev), ("tail", tail))]
+        if any(len(t) != len(w) for t, w in zip(times, new)):
+            raise ValueError("stream_agree: times must have one (start, end) per word of new")
+        n_new = int(arrs[0][0][-1])
+        tm = np.zeros((max(n_new, 1), 2), dtype=np.int32)
+        if n_new:
+            tm[:n_new] = np.fromiter(itertools.chain.from_iterable(itertools.chain.from_iterable(times)), dtype=np.int64, count=2 * n_new).reshape(-1, 2)
+        last = np.ascontiguousarray([int(x) for x in last_cs], dtype=np.int32)
+        lists = [WmStreamList(_ip(w), _ip(t), _ip(i)) for w, t, i in arrs]
+        params = WmStreamParams(int(late_cs), int(near_cs), int(max_ngram))
+        skip, commit, ender = (np.zeros(S, dtype=np.int32) for _ in range(3))
+        ms = C.c_float(0)
+        self._check(self.lib.wm_stream_agree(self.h, S, C.byref(lists[0]), C.byref(lists[1]), C.byref(lists[2]), _ip(tm), _ip(last), C.byref(params),
+                                             _ip(skip), _ip(commit), _ip(ender), C.byref(ms)), "wm_stream_agree")
+        self.last_stream_ms = ms.value
+        return skip, commit, ender
 
     def vad_windows(self, samples_dev: torch.Tensor, n_samples: Sequence[int], params, taps: bool = False):
         """wm_vad_windows: the speech regions of every recording and the windows of at most ``F`` frames that hold them, cut only at pauses (or, in
