@@ -34,7 +34,9 @@ bf16-representable; in the ENCODER every GEMM input is rounded to bf16 (MFMA pre
 in the DECODER GEMM/attention operands are carried as a bf16 hi/lo pair (x = hi + lo,
 ~17 mantissa bits, ``_rd``) so they are effectively unrounded; the self/cross KV cache
 and the encoder output are stored in bf16; all accumulation / LayerNorm / softmax /
-residual arithmetic is fp32.
+residual arithmetic is fp32.  With ``act="f16"`` a decoder layer's LayerNorm + linear is restated as the engine folds it
+(``_lin_ln``: the operand is the raw row times the gain, the statistics are one fp32 pass); ``fold_hilo=True`` does the same for hi / lo.
+``dtype=torch.float64`` (with ``sim="fp32"``) runs the reference arithmetic in fp64: the truth tests measure the contracts against.
 """
 from __future__ import annotations
 
@@ -51,6 +53,12 @@ HEAD_DIM = 64
 
 def _bf16(x: torch.Tensor) -> torch.Tensor:
     return x.to(torch.bfloat16).to(torch.float32)
+
+
+def fold_gain_shift(gamma: torch.Tensor) -> int:
+    """s of the folded LayerNorm's operand scaling (csrc/wm_decoder.hip fold_scaled_gain): the smallest s >= 0 with max|gamma| 2^-s < 2."""
+    mx = float(gamma[torch.isfinite(gamma)].abs().max()) if bool(torch.isfinite(gamma).any()) else 0.0
+    return max(0, math.frexp(mx)[1] - 1)
 
 
 # --------------------------------------------------------------------------------------
@@ -287,8 +295,17 @@ class Oracle:
     """Functional Whisper-Medusa over a plain state dict (reference key layout)."""
 
     def __init__(self, cfg, sd: Dict[str, torch.Tensor], sim: str = "fp32", dec_fp8: bool = False, enc_fp8: bool = False, act: Optional[str] = None,
-                 xkv_fp8: bool = False):
-        if act is None:         # the contract the engine defaults to in this process (whisper_medusa.engine.default_act_fp16: WM_ACT)
+                 xkv_fp8: bool = False, dtype: torch.dtype = torch.float32, fold_hilo: bool = False):
+        # dtype=torch.float64 (sim="fp32" only): the same passes with parameters and every intermediate in fp64 — the truth the contracts'
+        # errors are measured against (tests/fold_ref.py); no rounding point exists in that mode, and the decoder's LayerNorm + linear is
+        # F.layer_norm then a matmul (never the folded algebra of _lin_ln below)
+        assert dtype == torch.float32 or (dtype == torch.float64 and sim == "fp32" and not (dec_fp8 or enc_fp8 or xkv_fp8))
+        self.dtype = dtype
+        # fold_hilo (act="hilo" only): restate the engine's folded LayerNorm for the hi / lo operand as well (_lin_ln).  Off by default: hi / lo
+        # carries ~17 bits and the two forms agree closely on rows whose |mean| / std stays in the single digits; the difference shows at
+        # |mean| / std in the tens and beyond (tests/fold_ref.py, tests/test_fold_contract_cpu.py)
+        self.fold_hilo = fold_hilo
+        if act is None:        # the contract the engine defaults to in this process (whisper_medusa.engine.default_act_fp16: WM_ACT)
             import os as _os
             act = "f16" if _os.environ.get("WM_ACT", "f16").lower() in ("f16", "fp16") else "hilo"
         assert sim in ("fp32", "bf16") and act in ("hilo", "f16")
@@ -305,7 +322,7 @@ class Oracle:
         # scale per (kv layer, head) for K and one for V: scale = max|x| / 448 over the head's S x 64 stored (bf16) values, q = rne_e4m3(x / scale)
         self.xkv_fp8 = xkv_fp8
         self.w8: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
-        self.sd = {k: v.detach().to(torch.float32).cpu() for k, v in sd.items()}
+        self.sd = {k: v.detach().to(dtype).cpu() for k, v in sd.items()}
         self.H = cfg.d_model // HEAD_DIM
         if "whisper_model.proj_out.weight" not in self.sd:
             self.sd["whisper_model.proj_out.weight"] = self.sd["whisper_model.model.decoder.embed_tokens.weight"]
@@ -349,11 +366,14 @@ class Oracle:
         return y
 
     def _lin_ln(self, h, ln_prefix, prefix, bias=True):
-        """linear(LayerNorm(h)) of a decoder layer (HF:modeling_whisper.py:416-505, pre-LN).  fp32 / hi-lo contract: exactly that.  fp16
-        single-plane contract (act="f16"): the engine's rounding point — it multiplies the operand fp16(gamma o h) and applies the row statistics
-        to the product (csrc/wm_common.h "LayerNorm folded into the GEMM it feeds"):  rstd (W fp16(gamma o h) - mean W gamma) + (b + W beta),
-        the same algebra with the rounding where the engine has it (hi / lo carries ~17 bits either way: no visible rounding point there)."""
-        if not (self.sim == "bf16" and self.act == "f16"):
+        """linear(LayerNorm(h)) of a decoder layer (HF:modeling_whisper.py:416-505, pre-LN).  fp32 and the hi / lo contract: exactly that.
+        act="f16" — and hi / lo with fold_hilo — under sim="bf16": the engine's rounding points — it multiplies the operand round(gamma' o h) (ONE fp16 plane with act="f16", a bf16 hi / lo
+        pair otherwise) and applies the row statistics to the product (csrc/wm_common.h "LayerNorm folded into the GEMM it feeds"):
+        rstd 2^s (W round(gamma' o h) - mean W gamma') + (b + W beta), gamma' = gamma 2^-s with s = the smallest s >= 0 with max|gamma| 2^-s < 2
+        (a power of two: exact, it only keeps the fp16 plane in range under a large gain), the statistics in ONE fp32 pass, var = E[h^2] - mean^2
+        clamped at 0.  The operand is the RAW row, so a row with a large mean is rounded at the size of its mean, not of LN(h): hi / lo carries
+        ~17 bits and shows that only at |mean| / std in the tens (tests/test_fold_contract_cpu.py)."""
+        if not (self.sim == "bf16" and (self.act == "f16" or self.fold_hilo)):
             return self._lin(self._ln(h, ln_prefix), prefix, bias=bias, dec=True)
         g, b = self.sd[ln_prefix + ".weight"], self.sd[ln_prefix + ".bias"]
         if prefix in self.q8:
@@ -361,10 +381,12 @@ class Oracle:
             W = q * scale[:, None]
         else:
             W = self.sd[prefix + ".weight"]
-        z = (h * g).to(torch.float16).to(torch.float32)
+        s = fold_gain_shift(g)
+        g = g * 2.0 ** -s
+        z = self._rg(h * g)
         mean = h.mean(dim=-1, keepdim=True)
         var = ((h * h).mean(dim=-1, keepdim=True) - mean * mean).clamp_min(0.0)
-        rstd = torch.rsqrt(var + 1e-5)
+        rstd = torch.rsqrt(var + 1e-5) * 2.0 ** s
         y = rstd * (z @ W.t() - mean * (W @ g)[None, :]) + (W @ b)[None, :]
         if bias and (prefix + ".bias") in self.sd:
             y = y + self.sd[prefix + ".bias"]
@@ -484,8 +506,8 @@ class Oracle:
         return h
 
     def new_state(self, enc: torch.Tensor) -> dict:
-        empty = torch.zeros(self.H, 0, HEAD_DIM)
-        return dict(cross_kv=self.cross_kv(enc), kv_len=0,
+        empty = torch.zeros(self.H, 0, HEAD_DIM, dtype=self.dtype)
+        return dict(cross_kv=self.cross_kv(enc.to(self.dtype)), kv_len=0,
                     self_kv=[(empty, empty) for _ in range(self.cfg.n_kv_layers)])
 
     def _res_head(self, k, x):

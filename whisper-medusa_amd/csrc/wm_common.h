@@ -208,7 +208,9 @@ __device__ __forceinline__ void st_hilo4(bf16_t* hi, bf16_t* lo, float4 y)
 // refuses a wm_config.act_fp16 that is not the build's).
 //   hi / lo (rounds 1-5): an activation is a bf16 PAIR x = hi + lo (~17 mantissa bits) in two planes; two v_mfma_f32_16x16x32_bf16 per weight
 //     fragment; decoder matrices bf16.
-//   f16 (round 6): ONE fp16 plane (11 mantissa bits — the precision the reference's own fp16 / bf16 inference carries); one
+//   f16 (round 6): ONE fp16 plane (11 mantissa bits — what the reference's own fp16 inference carries, on the same VALUES only outside a folded
+//     LayerNorm: there the plane holds the raw row gamma o x, not LN(x), so a row mean of rho standard deviations costs about rho / 7 times that
+//     rounding (measured, rho = 17 .. 271) and |x| must stay below 32752 — DESIGN.md §2 "Domain of validity of the f16 contract"; act_fp16 = 0 has neither limit); one
 //     v_mfma_f32_16x16x32_f16 per weight fragment; decoder matrices held as fp16 (exact from bf16 for |w| >= 2^-17, e4m3 exactly).  Half the
 //     L2 -> CU bytes and half the MFMAs of every token operand: the 32-stream step is bound by exactly that (profiles/r06_upper_bounds.md).
 // Storage stays a raw 16-bit container (bf16_t) either way: same packed layout, same plane arithmetic (plane unused with one plane).
@@ -294,8 +296,11 @@ __device__ __forceinline__ wfrag_t ld_wfrag(const bf16_t* W, size_t elem) {
 // pass), no statistics -> barrier -> normalise prologue in the single-stream launches.  c and b' are computed once in wm_create (fp64 sums).
 // Partial table layout: stats[tile][row] (float2; row stride `ld` = row capacity, a multiple of 16): a finishing wave stores 16 rows x 8 B = one
 // 128-B line per tile.
+// Range of the one-plane operand: the producers multiply x by gamma * 2^-s, s = the smallest s >= 0 with max|gamma| * 2^-s < 2 (wm_create), c is
+// built from the same scaled gamma and the consumer multiplies rstd by rs = 2^s once per row: exact in binary, so s = 0 (every gain below 2) is the
+// unscaled form bit for bit, and a large gain no longer carries fp16(gamma o x) past 65504 — |x| < 32752 is what the fp16 plane then asks of a row.
 struct FoldIn {
-    const float2* stats; const float* c; int T16; int ld; float inv_d;
+    const float2* stats; const float* c; int T16; int ld; float inv_d; float rs;
 };
 
 // the thread's share of a block's row statistics: partial group `grp` (tiles 8 grp .. 8 grp + 7, summed in order) of row `row`
@@ -312,12 +317,12 @@ __device__ __forceinline__ float2 fold_part_sum(const FoldPart& fp) {
     return make_float2(s, q);
 }
 // mean / rstd of a row from its G group partials in LDS (part[grp * nrows + r]), summed in group order
-__device__ __forceinline__ float2 fold_row_stat(const float2* part, int r, int nrows, int G, float inv_d) {
+__device__ __forceinline__ float2 fold_row_stat(const float2* part, int r, int nrows, int G, float inv_d, float rs) {
     float s = 0.f, q = 0.f;
     for (int g2 = 0; g2 < G; ++g2) { const float2 p = part[g2 * nrows + r]; s += p.x; q += p.y; }
     // (explicit fma / nofuse: every kernel rounds these the same way whatever the compiler would contract around them — see nofuse above)
     const float mean = s * inv_d;
-    return make_float2(mean, rsqrtf(fmaxf(__builtin_fmaf(-mean, mean, q * inv_d), 0.f) + 1e-5f));
+    return make_float2(mean, rsqrtf(fmaxf(__builtin_fmaf(-mean, mean, q * inv_d), 0.f) + 1e-5f) * rs);      // (rs = 2^s: an exact product)
 }
 __device__ __forceinline__ f32x4_t fold_apply(f32x4_t v, float2 mr, float4 c) {
     return f32x4_t{nofuse(mr.y * __builtin_fmaf(-mr.x, c.x, v[0])), nofuse(mr.y * __builtin_fmaf(-mr.x, c.y, v[1])),

@@ -5,6 +5,7 @@
 // static shape, so the whole iteration is captured once as a hipGraph and replayed (wm_engine.hip).
 #include "wm_internal.h"
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <type_traits>
 #include "wm_skinny_gemm.h"
@@ -1392,7 +1393,7 @@ static inline int xattn_blocks_per_head(int NS, int heads_total)
 // (Templates only to keep this change's device image the parent's byte for byte: a template's body is instantiated where it is first called, so
 // the kernels named here are emitted in dec_layer's launch order, as when dec_layer named the launchers itself.  Nothing depends on it: as plain
 // functions they merely move the GEMM kernels in front of the attention kernels in the code object — profiles/explicit_launch_state.md.)
-static inline FoldIn layer_fold_in(const wm_ctx* ctx, const float* c) { return FoldIn{ctx->lnstats, c, ctx->d / 16, ctx->Rcap, 1.0f / (float)ctx->d}; }
+static inline FoldIn layer_fold_in(const wm_ctx* ctx, const float* c, float rs) { return FoldIn{ctx->lnstats, c, ctx->d / 16, ctx->Rcap, 1.0f / (float)ctx->d, rs}; }
 
 // LN1 + QKV: q rows to ctx->qbuf, k rows / transposed v rows straight into the cache slabs kc / vc of the pass's first stream, Mper rows per
 // stream from position base[stream]; rowinfo != nullptr: the merged-step schedule's dense rows (EpQKVDecDense)
@@ -1403,10 +1404,10 @@ template <int = 0> static hipError_t gemm_qkv(wm_ctx* ctx, const DecLayerW& w, i
     const size_t xpl = (size_t)ctx->Rcap * d;
     const WRef W{w.qkv_w, w.qkv_s};
     if (ctx->ln_fold && rowinfo)
-        return launch_skinny_fold(ctx->lp, W, 3 * d / 16, K32, R, ctx->xn, xpl, layer_fold_in(ctx, w.qkv_c),
+        return launch_skinny_fold(ctx->lp, W, 3 * d / 16, K32, R, ctx->xn, xpl, layer_fold_in(ctx, w.qkv_c, w.ln1_rs),
                                   EpQKVDecDense{ctx->qbuf, kc, vc, w.qkv_bf, base, Mper, d, H, ctx->Tal, R, rowinfo}, pc);
     if (ctx->ln_fold)
-        return launch_skinny_fold(ctx->lp, W, 3 * d / 16, K32, R, ctx->xn, xpl, layer_fold_in(ctx, w.qkv_c),
+        return launch_skinny_fold(ctx->lp, W, 3 * d / 16, K32, R, ctx->xn, xpl, layer_fold_in(ctx, w.qkv_c, w.ln1_rs),
                                   EpQKVDec{ctx->qbuf, kc, vc, w.qkv_bf, base, Mper, d, H, ctx->Tal, R}, pc);
     if (rowinfo)
         return launch_skinny_norm(ctx->lp, W, 3 * d / 16, K32, h, w.ln1_w, w.ln1_b, d, R, 1, 0, 1,
@@ -1416,7 +1417,7 @@ template <int = 0> static hipError_t gemm_qkv(wm_ctx* ctx, const DecLayerW& w, i
 }
 
 // h += X W^T + bias (X: packed rows of K = 32 * Kc32 features); fold: also the operand gnext o h and the statistics partials of the LayerNorm
-// that follows (gnext = its gamma; nullptr: a final LayerNorm launch follows, the unfolded epilogue)
+// that follows (gnext = its scaled gamma, DecLayerW::ln*_g; nullptr: a final LayerNorm launch follows, the unfolded epilogue)
 template <int = 0> static hipError_t gemm_residual(wm_ctx* ctx, WRef W, const float* bias, int Kc32, const bf16_t* X, size_t plane, int R, float* h, const float* gnext,
                                 const PfCarry& pc)
 {
@@ -1430,7 +1431,7 @@ template <int = 0> static hipError_t gemm_residual(wm_ctx* ctx, WRef W, const fl
 // self-attention out_proj + residual
 template <int = 0> static hipError_t gemm_out(wm_ctx* ctx, const DecLayerW& w, int R, float* h, const PfCarry& pc = PfCarry{})
 {
-    return gemm_residual(ctx, WRef{w.out_w, w.out_s}, w.out_b, ctx->d / 32, ctx->xbuf, (size_t)ctx->Rcap * ctx->d, R, h, w.ln2_w, pc);
+    return gemm_residual(ctx, WRef{w.out_w, w.out_s}, w.out_b, ctx->d / 32, ctx->xbuf, (size_t)ctx->Rcap * ctx->d, R, h, w.ln2_g, pc);
 }
 // LN2 + cross-attention q (scaled) -> ctx->qbuf
 template <int = 0> static hipError_t gemm_cross_q(wm_ctx* ctx, const DecLayerW& w, int R, float* h, const PfCarry& pc = PfCarry{})
@@ -1438,14 +1439,14 @@ template <int = 0> static hipError_t gemm_cross_q(wm_ctx* ctx, const DecLayerW& 
     const int d = ctx->d, K32 = d / 32;
     const size_t xpl = (size_t)ctx->Rcap * d;
     if (ctx->ln_fold)
-        return launch_skinny_fold(ctx->lp, WRef{w.cq_w, w.cq_s}, d / 16, K32, R, ctx->xn, xpl, layer_fold_in(ctx, w.cq_c), EpF32{ctx->qbuf, w.cq_bf, d, R, 0.125f}, pc);
+        return launch_skinny_fold(ctx->lp, WRef{w.cq_w, w.cq_s}, d / 16, K32, R, ctx->xn, xpl, layer_fold_in(ctx, w.cq_c, w.ln2_rs), EpF32{ctx->qbuf, w.cq_bf, d, R, 0.125f}, pc);
     return launch_skinny_norm(ctx->lp, WRef{w.cq_w, w.cq_s}, d / 16, K32, h, w.ln2_w, w.ln2_b, d, R, 1, 0, 1, EpF32{ctx->qbuf, w.cq_b, d, R, 0.125f},
                               ctx->xbuf, xpl, pc);
 }
 // cross-attention out_proj + residual
 template <int = 0> static hipError_t gemm_cross_out(wm_ctx* ctx, const DecLayerW& w, int R, float* h, const PfCarry& pc = PfCarry{})
 {
-    return gemm_residual(ctx, WRef{w.cout_w, w.cout_s}, w.cout_b, ctx->d / 32, ctx->xbuf, (size_t)ctx->Rcap * ctx->d, R, h, w.ln3_w, pc);
+    return gemm_residual(ctx, WRef{w.cout_w, w.cout_s}, w.cout_b, ctx->d / 32, ctx->xbuf, (size_t)ctx->Rcap * ctx->d, R, h, w.ln3_g, pc);
 }
 // LN3 + fc1 + GELU -> ctx->fbuf (packed).  pf_extra: unfolded batched passes, the matrix the LayerNorm launch pulls in besides FC1's (FC2's)
 template <int = 0> static hipError_t gemm_fc1(wm_ctx* ctx, const DecLayerW& w, int R, float* h, const PfCarry& pc = PfCarry{}, const void* pf_extra = nullptr)
@@ -1453,7 +1454,7 @@ template <int = 0> static hipError_t gemm_fc1(wm_ctx* ctx, const DecLayerW& w, i
     const int d = ctx->d, K32 = d / 32, F32 = ctx->ffn / 32;
     const size_t xpl = (size_t)ctx->Rcap * d, fpl = (size_t)ctx->Rcap * ctx->ffn;
     if (ctx->ln_fold)
-        return launch_skinny_fold(ctx->lp, WRef{w.fc1_w, w.fc1_s}, ctx->ffn / 16, K32, R, ctx->xn, xpl, layer_fold_in(ctx, w.fc1_c),
+        return launch_skinny_fold(ctx->lp, WRef{w.fc1_w, w.fc1_s}, ctx->ffn / 16, K32, R, ctx->xn, xpl, layer_fold_in(ctx, w.fc1_c, w.ln3_rs),
                                   EpPackedAct<1>{ctx->fbuf, ctx->fbuf + fpl, w.fc1_bf, F32, R}, pc);
     return launch_skinny_norm(ctx->lp, WRef{w.fc1_w, w.fc1_s}, ctx->ffn / 16, K32, h, w.ln3_w, w.ln3_b, d, R, 1, 0, 1,
                               EpPackedAct<1>{ctx->fbuf, ctx->fbuf + fpl, w.fc1_b, F32, R}, ctx->xbuf, xpl, pc, pf_extra);
@@ -1611,7 +1612,7 @@ static int dec_layer(wm_ctx* ctx, const DecLayerW& w, int slot, float* h, int b0
     // 8. fc2 + residual (fold: + the operand of the NEXT layer's LN1 + QKV; the last layer's rows go to the final LayerNorm launch instead)
     const PfCarry c8 = next ? carry_for(next->qkv_w, 3 * d / 16, K32, true) : PfCarry{};
     TL_SET(lp, slot * 16 + 8 + 8192 * Mper);
-    WM_HIP(gemm_fc2(ctx, w, R, h, next ? next->ln1_w : nullptr, c8));
+    WM_HIP(gemm_fc2(ctx, w, R, h, next ? next->ln1_g : nullptr, c8));
     return WM_OK;
 }
 
@@ -1637,21 +1638,50 @@ __global__ void k_fold_vectors(const bf16_t* __restrict__ W, const float* __rest
     if (lane == 0) { c[n] = (float)sc; bf[n] = (float)((double)bias[n] + sb); }
 }
 
+// The gains the folded operand is written with: gamma * 2^-s, s = the smallest s >= 0 with max|gamma| * 2^-s < 2, and rs = 2^s for the consumer's rstd
+// (wm_common.h FoldIn: exact in binary; a LayerNorm whose gains all lie below 2 keeps s = 0, its operand and its products bit for bit).  All gains of
+// the context come to the host in one batch of copies and go back scaled in one (two stream synchronisations per wm_create).
 int wm_dec_fold_init(wm_ctx* ctx)
 {
     hipStream_t st = ctx->stream;
     const int d = ctx->d, ffn = ctx->ffn;
+    const size_t nl = ctx->dec.size();
+    float* gdev = ctx->foldv + nl * 2 * (size_t)(4 * d + ffn);            // [layer][3][d] scaled gains, behind the c / b' vectors
+    std::vector<float> g(nl * 3 * (size_t)d);
+    for (size_t l = 0; l < nl; ++l) {
+        const float* src[3] = {ctx->dec[l].ln1_w, ctx->dec[l].ln2_w, ctx->dec[l].ln3_w};
+        for (int i = 0; i < 3; ++i)
+            WM_HIP(hipMemcpyAsync(g.data() + (l * 3 + i) * d, src[i], (size_t)d * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    WM_HIP(hipStreamSynchronize(st));
+    std::vector<float> rs(nl * 3);
+    for (size_t j = 0; j < nl * 3; ++j) {
+        float* v = g.data() + j * d;
+        float mx = 0.f;
+        for (int k = 0; k < d; ++k) if (std::isfinite(v[k])) mx = std::max(mx, std::fabs(v[k]));
+        int e = 0;
+        std::frexp(mx, &e);                        // mx = m 2^e, m in [0.5, 1): mx 2^-(e - 1) lies in [1, 2)
+        const int s = std::max(0, e - 1);
+        for (int k = 0; k < d; ++k) v[k] = std::ldexp(v[k], -s);
+        rs[j] = std::ldexp(1.0f, s);
+    }
+    WM_HIP(hipMemcpyAsync(gdev, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice, st));
     float* p = ctx->foldv;
-    for (auto& w : ctx->dec) {
+    for (size_t l = 0; l < nl; ++l) {
+        DecLayerW& w = ctx->dec[l];
         float* v[6];
         const int len[6] = {3 * d, 3 * d, d, d, ffn, ffn};
         for (int i = 0; i < 6; ++i) { v[i] = p; p += len[i]; }
-        hipLaunchKernelGGL(k_fold_vectors, dim3((3 * d + 3) / 4), dim3(256), 0, st, w.qkv_w, w.qkv_s, w.ln1_w, w.ln1_b, w.qkv_b, 3 * d, d, v[0], v[1]);
-        hipLaunchKernelGGL(k_fold_vectors, dim3((d + 3) / 4), dim3(256), 0, st, w.cq_w, w.cq_s, w.ln2_w, w.ln2_b, w.cq_b, d, d, v[2], v[3]);
-        hipLaunchKernelGGL(k_fold_vectors, dim3((ffn + 3) / 4), dim3(256), 0, st, w.fc1_w, w.fc1_s, w.ln3_w, w.ln3_b, w.fc1_b, ffn, d, v[4], v[5]);
+        w.ln1_g = gdev + (l * 3 + 0) * d; w.ln2_g = gdev + (l * 3 + 1) * d; w.ln3_g = gdev + (l * 3 + 2) * d;
+        w.ln1_rs = rs[l * 3 + 0]; w.ln2_rs = rs[l * 3 + 1]; w.ln3_rs = rs[l * 3 + 2];
+        // c from the SCALED gains (the operand's), b' from the unscaled beta
+        hipLaunchKernelGGL(k_fold_vectors, dim3((3 * d + 3) / 4), dim3(256), 0, st, w.qkv_w, w.qkv_s, w.ln1_g, w.ln1_b, w.qkv_b, 3 * d, d, v[0], v[1]);
+        hipLaunchKernelGGL(k_fold_vectors, dim3((d + 3) / 4), dim3(256), 0, st, w.cq_w, w.cq_s, w.ln2_g, w.ln2_b, w.cq_b, d, d, v[2], v[3]);
+        hipLaunchKernelGGL(k_fold_vectors, dim3((ffn + 3) / 4), dim3(256), 0, st, w.fc1_w, w.fc1_s, w.ln3_g, w.ln3_b, w.fc1_b, ffn, d, v[4], v[5]);
         WM_HIP(hipGetLastError());
         w.qkv_c = v[0]; w.qkv_bf = v[1]; w.cq_c = v[2]; w.cq_bf = v[3]; w.fc1_c = v[4]; w.fc1_bf = v[5];
     }
+    WM_HIP(hipStreamSynchronize(st));      // the host vector goes out of scope
     return WM_OK;
 }
 
@@ -1667,7 +1697,7 @@ int wm_dec_stage_layers(wm_ctx* ctx, int b0, int nb, int Mper, int mode)
     const int* base = (mode == 0 ? ctx->kvlen : ctx->L) + b0;          // mode 2: positions come from rowinfo / sinfo
     if (R > ctx->Rcap || Mper > ctx->Mmax) { ctx->err = "decode pass exceeds the row capacity of the context"; return WM_ERR_ARG; }
     // LayerNorm fold: the embed launch also writes layer 0's QKV operand (gamma_ln1 o h) and the rows' statistics partials
-    const float* eg = ctx->ln_fold ? ctx->dec[0].ln1_w : nullptr;
+    const float* eg = ctx->ln_fold ? ctx->dec[0].ln1_g : nullptr;
     const size_t expl = (size_t)ctx->Rcap * d;
     // node tables of a verify pass: the candidate tree, or the chain + sibling leaves of a single-stream pass that carries them (Mper > K + 1)
     const TreeDev* ptree = ctx->tn ? ctx->tree : ((mode == 1 && ctx->gp.sib > 0 && Mper == ctx->K + 1 + ctx->gp.sib) ? ctx->sibtree : nullptr);
@@ -1713,7 +1743,7 @@ static int replay_tile(wm_ctx* ctx, int b0, int nb, int pos0, int Mper, int n_la
     const int d = ctx->d, R = nb * Mper;
     const int* base = ctx->kvlen + b0;
     if (R > ctx->Rcap || Mper > 16 || Mper < 1 || n_layers > ctx->cfg.dec_layers) { ctx->err = "replay pass exceeds the row capacity of the context"; return WM_ERR_ARG; }
-    const float* eg = ctx->ln_fold ? ctx->dec[0].ln1_w : nullptr;
+    const float* eg = ctx->ln_fold ? ctx->dec[0].ln1_g : nullptr;
     hipLaunchKernelGGL(k_embed, dim3(R), dim3(256), 0, st, ctx->h, ctx->tok_emb, ctx->dec_pos, base,
                        ctx->ids + (size_t)b0 * ctx->gp.Tids, ctx->gp.Tids, 1, Mper, d, ctx->V, ctx->Tmax, (const int*)nullptr,
                        (const int4*)nullptr, (const int*)nullptr, 0, eg, ctx->xn, (size_t)ctx->Rcap * d, ctx->lnstats, ctx->Rcap);
@@ -1775,7 +1805,7 @@ int wm_dec_stage_final(wm_ctx* ctx, int b0, int nb, int Mper, int mode, int medu
     hipLaunchKernelGGL(k_rows_norm, dim3((R + 3) / 4), dim3(256), 0, st, ctx->h, 1, 0, ctx->dec_lnf_w, ctx->dec_lnf_b, 1,
                        hf, ctx->block ? ctx->hblk : nullptr, nullptr, (size_t)0, K32, 1, 0, d, R,
                        (mode == 0 && Mper == 1 && ctx->dev_carry) ? ctx->carry + b0 : nullptr, ctx->hf_keep + (size_t)b0 * d,
-                       bfold ? ctx->dec[ctx->nkv - 1].ln1_w : nullptr, ctx->xn, (size_t)ctx->Rcap * d, ctx->lnstats, ctx->Rcap);
+                       bfold ? ctx->dec[ctx->nkv - 1].ln1_g : nullptr, ctx->xn, (size_t)ctx->Rcap * d, ctx->lnstats, ctx->Rcap);
     WM_HIP(hipGetLastError());
     ctx->hf_cur = hf;
     if (ctx->block && !ctx->gp.vanilla) {
@@ -2148,7 +2178,7 @@ int wm_dec_profile(wm_ctx* ctx, int kernel, int rows, int reps, float* ms, doubl
         if (all || kernel == 3) WM_HIP(gemm_cross_q(ctx, w, R, ctx->h));
         if (all || kernel == 4) WM_HIP(gemm_cross_out(ctx, w, R, ctx->h));
         if (all || kernel == 5) WM_HIP(gemm_fc1(ctx, w, R, ctx->h));
-        if (all || kernel == 6) WM_HIP(gemm_fc2(ctx, w, R, ctx->h, w.ln1_w));
+        if (all || kernel == 6) WM_HIP(gemm_fc2(ctx, w, R, ctx->h, w.ln1_g));
         if (kernel == 7)
             WM_HIP(launch_skinny_rows(ctx->lp, ctx->vocab_w, ctx->Vpad / 16, K32, R, ctx->ybuf, xpl, EpLogits{ctx->logits, nullptr, ctx->Vpad, R, 1.0f}));
         return WM_OK;

@@ -239,7 +239,7 @@ extern "C" int wm_create(const wm_config* cfg, const wm_weights* w, int device, 
     if (ctx->ln_fold) {
         CREATE_HIP(dev_alloc(&ctx->xn, 2 * RW * d, st));
         CREATE_HIP(dev_alloc(&ctx->lnstats, RW * (d / 16), st));
-        CREATE_HIP(dev_alloc(&ctx->foldv, (size_t)ctx->nkv * 2 * (4 * d + ctx->ffn), st));
+        CREATE_HIP(dev_alloc(&ctx->foldv, (size_t)ctx->nkv * (2 * (4 * d + ctx->ffn) + 3 * d), st));      // c, b' of three GEMMs + three scaled gains per layer
     }
     CREATE_HIP(dev_alloc(&ctx->fbuf, 2 * RW * ctx->ffn, st));
     CREATE_HIP(dev_alloc(&ctx->ybuf, 2 * RW * d, st));

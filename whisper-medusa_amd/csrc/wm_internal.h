@@ -30,6 +30,9 @@ struct DecLayerW {
     const float *qkv_s = nullptr, *out_s = nullptr, *cq_s = nullptr, *cout_s = nullptr, *fc1_s = nullptr, *fc2_s = nullptr;
     // LayerNorm folded into the three LayerNorm-fed GEMMs (wm_common.h; computed in wm_create by wm_dec_fold_init): c = W gamma, bf = b + W beta
     const float *qkv_c = nullptr, *qkv_bf = nullptr, *cq_c = nullptr, *cq_bf = nullptr, *fc1_c = nullptr, *fc1_bf = nullptr;
+    // ... and the gains the producers of the folded operand multiply by: gamma * 2^-s with rs = 2^s applied to rstd by the consumer (wm_common.h FoldIn)
+    const float *ln1_g = nullptr, *ln2_g = nullptr, *ln3_g = nullptr;
+    float ln1_rs = 1.0f, ln2_rs = 1.0f, ln3_rs = 1.0f;
 };
 
 // scalars every decode kernel may need (passed by value)

@@ -449,14 +449,14 @@ k_skinny_gemm(const bf16_t* __restrict__ W, const void* __restrict__ la, const v
                 s[0] += p.x; s[1] += p.y; s[2] += p.z; s[3] += p.w;
             }
             if constexpr (W8) s = scale4v(s, wsc);
-            if constexpr (FOLD) s = fold_apply(s, fold_row_stat(fpart, em, 16, fold.T16 >> 3, fold.inv_d), fc4);
+            if constexpr (FOLD) s = fold_apply(s, fold_row_stat(fpart, em, 16, fold.T16 >> 3, fold.inv_d, fold.rs), fc4);
             ep.fin(em, en, s, pre);
         }
     } else {
         if constexpr (FOLD) __syncthreads();
         if (edo) {
             if constexpr (W8) acc[0] = scale4v(acc[0], wsc);
-            if constexpr (FOLD) acc[0] = fold_apply(acc[0], fold_row_stat(fpart, em, 16, fold.T16 >> 3, fold.inv_d), fc4);
+            if constexpr (FOLD) acc[0] = fold_apply(acc[0], fold_row_stat(fpart, em, 16, fold.T16 >> 3, fold.inv_d, fold.rs), fc4);
             ep.fin(em, en, acc[0], pre);
         }
     }
@@ -624,7 +624,7 @@ k_rows_gemm(const bf16_t* __restrict__ W, const bf16_t* __restrict__ X, size_t p
             if (rt0 + i < N16 && mt0 + j < MT) {
                 if constexpr (W8) sacc = scale4(sacc, wscale, (rt0 + i) * 16 + 4 * (l2 >> 4));
                 if constexpr (FOLD)
-                    sacc = fold_apply(sacc, fold_row_stat(fpart, j * 16 + (l2 & 15), TT * 16, fold.T16 >> 3, fold.inv_d),
+                    sacc = fold_apply(sacc, fold_row_stat(fpart, j * 16 + (l2 & 15), TT * 16, fold.T16 >> 3, fold.inv_d, fold.rs),
                                       *reinterpret_cast<const float4*>(fold.c + (rt0 + i) * 16 + 4 * (l2 >> 4)));
                 ep.store4((mt0 + j) * 16 + (l2 & 15), (rt0 + i) * 16 + 4 * (l2 >> 4), sacc);
             }
@@ -639,7 +639,7 @@ k_rows_gemm(const bf16_t* __restrict__ W, const bf16_t* __restrict__ X, size_t p
             for (int j = 0; j < TT; ++j)
                 if (rt0 + i < N16 && mt0 + j < MT) {
                     if constexpr (W8) acc[i][j] = scale4(acc[i][j], wscale, (rt0 + i) * 16 + 4 * (lane >> 4));
-                    acc[i][j] = fold_apply(acc[i][j], fold_row_stat(fpart, j * 16 + (lane & 15), TT * 16, fold.T16 >> 3, fold.inv_d),
+                    acc[i][j] = fold_apply(acc[i][j], fold_row_stat(fpart, j * 16 + (lane & 15), TT * 16, fold.T16 >> 3, fold.inv_d, fold.rs),
                                            *reinterpret_cast<const float4*>(fold.c + (rt0 + i) * 16 + 4 * (lane >> 4)));
                     ep.store4((mt0 + j) * 16 + (lane & 15), (rt0 + i) * 16 + 4 * (lane >> 4), acc[i][j]);
                 }
@@ -761,7 +761,7 @@ k_skinny2_gemm(const bf16_t* __restrict__ W, const bf16_t* __restrict__ X, size_
                 s[0] += p.x; s[1] += p.y; s[2] += p.z; s[3] += p.w;
             }
             if constexpr (W8) s = scale4v(s, wsc);
-            if constexpr (FOLD) s = fold_apply(s, fold_row_stat(fpart, (wave & 1) * 16 + (lane & 15), 32, fold.T16 >> 3, fold.inv_d), fc4);
+            if constexpr (FOLD) s = fold_apply(s, fold_row_stat(fpart, (wave & 1) * 16 + (lane & 15), 32, fold.T16 >> 3, fold.inv_d, fold.rs), fc4);
             ep.fin((wave & 1) * 16 + (lane & 15), en, s, pre0);
         }
     } else {
@@ -772,8 +772,8 @@ k_skinny2_gemm(const bf16_t* __restrict__ W, const bf16_t* __restrict__ X, size_
                 acc1 = scale4v(acc1, wsc);
             }
             if constexpr (FOLD) {
-                acc0 = fold_apply(acc0, fold_row_stat(fpart, lane & 15, 32, fold.T16 >> 3, fold.inv_d), fc4);
-                acc1 = fold_apply(acc1, fold_row_stat(fpart, 16 + (lane & 15), 32, fold.T16 >> 3, fold.inv_d), fc4);
+                acc0 = fold_apply(acc0, fold_row_stat(fpart, lane & 15, 32, fold.T16 >> 3, fold.inv_d, fold.rs), fc4);
+                acc1 = fold_apply(acc1, fold_row_stat(fpart, 16 + (lane & 15), 32, fold.T16 >> 3, fold.inv_d, fold.rs), fc4);
             }
             ep.fin(lane & 15, en, acc0, pre0);
             ep.fin(16 + (lane & 15), en, acc1, pre1);
