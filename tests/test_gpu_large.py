@@ -508,11 +508,17 @@ def test_large_fp8_mfma_encoder_and_decode_loop(gpu):
     _check_run(eng, orc, enc, gp, got, "fp8 mfma linear")
     wavs = np.stack([synth.synth_clip(80 + i, n) for i in range(12)])
     wavs[0] = wav
-    eng.encode(model.extract_features(wavs))
-    many = eng.encoder_output(12)[0]
-    dm = (many - enc).abs()
+    feats12 = model.extract_features(wavs)
+    eng.encode(feats12)
+    many = eng.encoder_output(12)
+    dm = (many[0] - enc).abs()
     print(f"large fp8 encoder 12-batch (256-tile kernel) vs alone: max|d| {float(dm.max()):.4f} mean|d| {float(dm.mean()):.6f}")
     assert dm.max() <= 0.5 and dm.mean() <= 1.5e-2
+    # the last clip too: row tiles 66 .. 71, the far end of the 256-tile kernel's XCD strip order
+    eng.encode(feats12[11:12].contiguous())
+    d11 = (many[11] - eng.encoder_output(1)[0]).abs()
+    print(f"large fp8 encoder 12-batch clip 11 vs alone: max|d| {float(d11.max()):.4f} mean|d| {float(d11.mean()):.6f}")
+    assert torch.isfinite(many[11]).all() and d11.max() <= 0.5 and d11.mean() <= 1.5e-2
     eng.close()
 
 
